@@ -8,9 +8,13 @@ on that region; `value_device_resident` is the same pass with the file already i
 holds its own coordinate slice (same read count) of one big coordinate-sorted BAM, the per-rank tables are
 exchanged with one RCCL all-gather of packed rows and merged.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel: the
-DEFLATE kernel, timed with HIP events on the pipeline's own stream) and `cpu_baseline` (the real
-reference built into oracle/_ref when present, else the oracle port; rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...).  --full adds everything else to the line, each in runs of its own after the
+timed steps: `roofline` (dominant kernel: the DEFLATE kernel, timed with HIP events on the pipeline's own
+stream), `cpu_baseline` (the real reference built into oracle/_ref when present, else the oracle port;
+rank 0, N=1 only), the device-resident and sustained passes, the cold CLI process, the other workloads and,
+for N > 1, the line's own cross-checks.  --dump-outputs DIR writes the last timed step's junction table as
+.npy files (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -35,6 +39,52 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s 
 # the whole-file launch of the DEFLATE kernel the pipeline runs above 2048 members (kernels.hip launch_inflate; REGTOOLS_AMD_INFLATE overrides)
 INFLATE_KERNEL = {"lane": "rgx::k_inflate<false, false, 1>", "ring": "rgx::k_inflate_ring<false>", "wave": "rgx::k_inflate_wave"}.get(
     os.environ.get("REGTOOLS_AMD_INFLATE", ""), "rgx::k_inflate_coop<false, false, 1>")
+
+
+DUMP_COLUMNS = ("tid", "start", "end", "thick_start", "thick_end", "read_count", "name_index", "strand", "left_ok", "right_ok")
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(table, out_dir):
+    """--dump-outputs: the junction table a caller of the timed path receives (rgx_junction_table), one float64 array per row column
+    (DIR/<column>.npy; strand as its character code), DIR/row_index.npy (the rows written) and DIR/totals.npy (rows, records, junction
+    events).  A table whose columns would pass 64 MB is written as an evenly spaced sample of its rows: the same rows for the same table."""
+    import numpy as np
+    t = table.contents
+    n = int(t.n)
+    k = min(n, (DUMP_BYTES - 4096) // (8 * (len(DUMP_COLUMNS) + 1)))
+    idx = np.arange(k, dtype=np.int64) * n // max(k, 1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "totals.npy"), np.array([n, t.n_records, t.n_events], dtype=np.float64))
+    for name in DUMP_COLUMNS:
+        ptr = C.cast(t.strand, C.POINTER(C.c_uint8)) if name == "strand" else getattr(t, name)
+        col = np.ctypeslib.as_array(ptr, shape=(n,))[idx] if n else np.zeros(0)
+        np.save(os.path.join(out_dir, name + ".npy"), col.astype(np.float64))
+
+
+def multi_gpu_host(backend, world):
+    return {"host": "one process per GPU (torchrun), torch.distributed backend %s" % backend, "rccl_ranks": world if backend == "nccl" else 0,
+            "exchange": "all_gather_into_tensor of the ranks' packed 48-byte rows into HBM + rgx_table_merge_device on every rank" if backend == "nccl"
+                        else "all_gather of packed rows on the host + rgx_table_merge (test backend)"}
+
+
+def headline(args, world, n_reads, total_reads, total_events, dt, s, rows, t_gen, host_binding):
+    """The fields of the line that come from the timed steps alone (a plain run prints only these)."""
+    return {
+        "metric": "alignments/sec + junctions/sec, junctions extract, 1/2/4/8 MI355X",
+        "value": total_reads * args.steps / dt, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8/u32 integer", "data": "synthetic",
+        "config": {"workload": ("configs[1]: synthetic %d-read 101 bp BAM per GPU, ~15%% reads with one N-op, junctions extract -s XS%s" % (n_reads, " (realistic payload)" if args.realistic else "")) if args.shape == "short" else
+                               "configs[4]-shape: synthetic %d long reads per GPU (l_qseq 1000-10000, n_cigar <= 64, 5-20 N ops), junctions extract -s XS" % n_reads,
+                   "reads_per_gpu": n_reads, "shape": args.shape, "seed": args.seed, "sharding": "coordinate slice per GPU, all-gather of packed junction rows" if world > 1 else "single GPU", "host_binding_rank0": host_binding,
+                   "bgzf_members": s["n_members"], "compressed_bytes_per_gpu": s["compressed_bytes"], "inflated_bytes_per_gpu": s["inflated_bytes"],
+                   "bytes_per_alignment": {"compressed": s["compressed_bytes"] / n_reads, "inflated": s["inflated_bytes"] / n_reads}},
+        "junction_events_per_s": total_events * args.steps / dt,
+        "timed_region": "file bytes in page-locked host memory -> sorted junction table in host memory (SURVEY.md 8d): chunked H2D upload inside every step, overlapped with the inflate",
+        "junction_rows": rows,
+        "input_generation_s": round(t_gen, 2)}
 
 
 def inflate_kernel_for(compressed, inflated):
@@ -305,6 +355,9 @@ def main():
     ap.add_argument("--reads", type=int, default=50_000_000, help="reads per GPU (config 2: 50M)")
     ap.add_argument("--shape", default="short", choices=["short", "long"])
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run and report everything beside the headline (the passes, baselines, "
+                    "workloads and checks the --no-* options below switch off one by one); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes the last timed step's junction table to DIR/<column>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the other workloads reported beside the headline (realistic payload, config 5 long reads, config 4 identify)")
     ap.add_argument("--host-only", action="store_true", help="(profiling) only the timed host-bytes pass; the roofline line then quotes the overlapped launches")
@@ -316,6 +369,8 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the pass with two files in flight (value_sustained)")
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes (the line then quotes the committed measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.multi_host == "cpp" and args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         return main_cpp_host(args)
 
@@ -390,10 +445,30 @@ def main():
     fence()
     dt = time.time() - t0
     n_events = je.stats["n_events"]
-    bed_host_path = je.bed12() if world == 1 else None
     if args.dump_bed and rank == 0:
         with open(args.dump_bed, "wb") as f:
             f.write(je.bed12() if world == 1 else last.bed12())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last if world == 1 else last.table, args.dump_outputs)
+    if not args.full:
+        total_reads, total_events = float(n_reads), float(n_events)
+        if world > 1:                          # the slowest rank's time, all ranks' reads and junction events
+            tt = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            cnt = torch.tensor([float(n_reads), float(n_events)], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+            dt, total_reads, total_events = float(tt[0].item()), cnt[0].item(), cnt[1].item()
+        if rank == 0:
+            line = headline(args, world, n_reads, total_reads, total_events, dt, je.stats, je.stats["n_junctions"] if world == 1 else int(last.n), t_gen, host_binding)
+            if world > 1:
+                line["multi_gpu"] = multi_gpu_host(backend, world)
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        ctx.close()
+        return
+    bed_host_path = je.bed12() if world == 1 else None
     # N > 1: what every rank spent where, for a scaling line that checks itself (one small all-gather, outside the timed region)
     rank_report = None
     if world > 1:
@@ -542,31 +617,17 @@ def main():
                 or committed_traffic("long10M" if args.shape == "long" else "realistic" if args.realistic else "default", kname, alg_bytes)
         traffic, traffic_note, traffic_source = tr.get("traffic"), tr.get("traffic_note"), tr.get("traffic_source")
         k_in_step = [x for x in launch_ms_in_step if x > 0]
-        line = {
-            "metric": "alignments/sec + junctions/sec, junctions extract, 1/2/4/8 MI355X",
-            "value": aln_per_s, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8/u32 integer", "data": "synthetic",
-            "config": {"workload": ("configs[1]: synthetic %d-read 101 bp BAM per GPU, ~15%% reads with one N-op, junctions extract -s XS%s" % (n_reads, " (realistic payload)" if args.realistic else "")) if args.shape == "short" else
-                                   "configs[4]-shape: synthetic %d long reads per GPU (l_qseq 1000-10000, n_cigar <= 64, 5-20 N ops), junctions extract -s XS" % n_reads,
-                       "reads_per_gpu": n_reads, "shape": args.shape, "seed": args.seed, "sharding": "coordinate slice per GPU, all-gather of packed junction rows" if world > 1 else "single GPU", "host_binding_rank0": host_binding,
-                       "bgzf_members": s["n_members"], "compressed_bytes_per_gpu": s["compressed_bytes"], "inflated_bytes_per_gpu": s["inflated_bytes"],
-                       "bytes_per_alignment": {"compressed": s["compressed_bytes"] / n_reads, "inflated": s["inflated_bytes"] / n_reads}},
-            "junction_events_per_s": total_events * args.steps / dt,
-            "timed_region": "file bytes in page-locked host memory -> sorted junction table in host memory (SURVEY.md 8d): chunked H2D upload inside every step, overlapped with the inflate",
+        line = headline(args, world, n_reads, total_reads, total_events, dt, s, s["n_junctions"] if world == 1 else int(last.n), t_gen, host_binding)
+        line.update({
             "value_device_resident": total_reads * args.steps / dt_res, "ms_per_step_device_resident": 1e3 * dt_res / args.steps,
             "value_sustained": (total_reads * 1e3 / sustained["ms_per_file"]) if sustained and "ms_per_file" in sustained else None, "sustained": sustained,
-            "junction_rows": s["n_junctions"] if world == 1 else int(last.n),
-            "multi_gpu": None if world == 1 else {"host": "one process per GPU (torchrun), torch.distributed backend %s" % backend, "rccl_ranks": world if backend == "nccl" else 0,
-                                                  "exchange": "all_gather_into_tensor of the ranks' packed 48-byte rows into HBM + rgx_table_merge_device on every rank" if backend == "nccl"
-                                                              else "all_gather of packed rows on the host + rgx_table_merge (test backend)",
-                                                  "merge_ms": round(max(r["gather_and_merge_ms"] for r in rank_report), 3),
-                                                  "merge_is": "serial behind the extraction in the timed step; in the sustained pass it runs under the next file's upload",
-                                                  "upload_GBps_all_ranks_at_once": [r["upload_GBps_all_ranks_at_once"] for r in rank_report],
-                                                  "bound_hint": "host link" if min(r["upload_GBps_all_ranks_at_once"] for r in rank_report) < 35 else "device",
-                                                  "checks": multi_checks, "per_rank": rank_report},
+            "multi_gpu": None if world == 1 else dict(multi_gpu_host(backend, world),
+                                                      merge_ms=round(max(r["gather_and_merge_ms"] for r in rank_report), 3),
+                                                      merge_is="serial behind the extraction in the timed step; in the sustained pass it runs under the next file's upload",
+                                                      upload_GBps_all_ranks_at_once=[r["upload_GBps_all_ranks_at_once"] for r in rank_report],
+                                                      bound_hint="host link" if min(r["upload_GBps_all_ranks_at_once"] for r in rank_report) < 35 else "device",
+                                                      checks=multi_checks, per_rank=rank_report),
             "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
-            "input_generation_s": round(t_gen, 2),
             "roofline": {"bound": "hbm", "kernel": inflate_kernel_for(s["compressed_bytes"], s["inflated_bytes"]), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_uncorrected": tr.get("traffic_uncorrected"), "traffic_source": traffic_source, "traffic_note": traffic_note,
                          "kernel_ms": k_ms, "kernel_ms_is": "the whole-file launch of the device-resident pass (HIP events on the pipeline's stream): what achieved / frac are quoted on",
@@ -579,7 +640,7 @@ def main():
                          "algorithmic_bytes": alg_bytes,
                          "note": "DEFLATE is a serial bit stream per member: one lane per member (long matches copied by the wave), bound by per-lane dependent ALU/LDS chains, the L1's rate of scattered per-lane accesses and one memory round trip per symbol trip, far below the HBM line (SURVEY 8d; DESIGN.md 5)",
                          "pipeline_frac": aln_per_s / world * (alg_bytes / n_reads) / (HBM_PEAK_GBS * 1e9)},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             with tempfile.TemporaryDirectory() as td:
                 path = os.path.join(td, "bench.bam")
@@ -660,19 +721,23 @@ def main_cpp_host(args):
     if args.dump_bed:
         with open(args.dump_bed, "wb") as f:
             f.write(m.bed12())
+    if args.dump_outputs:
+        dump_outputs(m.table, args.dump_outputs)
     tc = m.table.contents
-    # the line checks itself (outside the timed region): every record of the file was decoded by some shard, and the merged table is the table
-    # ONE device makes of the same file (one more extraction, on the first device, of the whole file)
     from regtools_amd import _ffi
     exchange = _ffi.lib().rgx_multi_exchange_kind().decode()
-    assert int(tc.n_records) == st["n_reads"], ("records lost", int(tc.n_records), st["n_reads"])
-    ctx1 = regtools_amd.Context(devices[0])
-    je1 = regtools_amd.JunctionsExtractor(strandness=0, ctx=ctx1)
-    je1.identify_junctions_from_BAM(bai_bytes=bai, host_ptr=pin.ptr, host_len=len(bam))
-    checks = dict(records_conserved=True, merged_rows=int(tc.n), single_device_rows=int(je1.stats["n_junctions"]), bed12_equals_single_device=bool(m.bed12() == je1.bed12()))
-    assert checks["merged_rows"] == checks["single_device_rows"] and checks["bed12_equals_single_device"], checks
-    del je1
-    ctx1.close()
+    checks = None
+    if args.full:
+        # the line checks itself (outside the timed region): every record of the file was decoded by some shard, and the merged table is the table
+        # ONE device makes of the same file (one more extraction, on the first device, of the whole file)
+        assert int(tc.n_records) == st["n_reads"], ("records lost", int(tc.n_records), st["n_reads"])
+        ctx1 = regtools_amd.Context(devices[0])
+        je1 = regtools_amd.JunctionsExtractor(strandness=0, ctx=ctx1)
+        je1.identify_junctions_from_BAM(bai_bytes=bai, host_ptr=pin.ptr, host_len=len(bam))
+        checks = dict(records_conserved=True, merged_rows=int(tc.n), single_device_rows=int(je1.stats["n_junctions"]), bed12_equals_single_device=bool(m.bed12() == je1.bed12()))
+        assert checks["merged_rows"] == checks["single_device_rows"] and checks["bed12_equals_single_device"], checks
+        del je1
+        ctx1.close()
     line = {"metric": "alignments/sec + junctions/sec, junctions extract, 1/2/4/8 MI355X", "value": st["n_reads"] * args.steps / dt, "unit": "alignments/s",
             "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "u8/u32 integer", "data": "synthetic",

@@ -108,7 +108,7 @@ def test_config2_at_full_size_400M_reads_in_eight_shards(gpu_ctx, tmp_path):
     bed8 = str(tmp_path / "ranks8.bed")
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", "29633",
-                        os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "0", "--reads", str(reads), "--seed", str(seed),
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--reads", str(reads), "--seed", str(seed),
                         "--no-cpu-baseline", "--no-extras", "--dump-bed", bed8], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -578,7 +578,7 @@ def test_bench_multi_rank_path_on_one_gpu(gpu_ctx, tmp_path):
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     bed2 = str(tmp_path / "ranks2.bed")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29617",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "200000", "--no-cpu-baseline", "--no-extras", "--dump-bed", bed2],
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "200000", "--no-cpu-baseline", "--no-extras", "--dump-bed", bed2],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -603,7 +603,7 @@ def test_bench_multi_rank_path_on_one_gpu(gpu_ctx, tmp_path):
     assert open(bed2, "rb").read() == want
     # ... and bench.py's C++ host mode: one file of 2 x 200000 reads over the device list [0, 0] == the single-GPU table of that file
     bedc = str(tmp_path / "cpp.bed")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--multi-host", "cpp", "--steps", "1", "--warmup", "1", "--reads", "200000", "--dump-bed", bedc],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--multi-host", "cpp", "--steps", "1", "--warmup", "1", "--reads", "200000", "--dump-bed", bedc],
                        env=os.environ, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     linec = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

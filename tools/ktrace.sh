@@ -2,7 +2,7 @@
 # usage: tools/ktrace.sh <outdir> [bench args...]  -- rocprofv3 kernel trace of one bench run, per-kernel summary
 OUT=$1; shift
 R=$PWD; export TMPDIR=/tmp; mkdir -p $R/$OUT; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/$OUT -o kt -- python $R/bench.py --no-cpu-baseline "$@" > $R/$OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/$OUT -o kt -- python $R/bench.py --full --no-cpu-baseline "$@" > $R/$OUT/bench.log 2>&1
 cd $R
 python3 - <<PY
 import csv,glob,collections

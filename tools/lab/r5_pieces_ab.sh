@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../.."
 one() { # label, env, extra bench args
   echo -n "$1 $2: "
-  env $2 python bench.py --steps ${STEPS:-12} --warmup 3 --no-extras --no-cpu-baseline --no-live-traffic $3 2>/dev/null | python -c "
+  env $2 python bench.py --full --steps ${STEPS:-12} --warmup 3 --no-extras --no-cpu-baseline --no-live-traffic $3 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -5,8 +5,8 @@
 cd "$(dirname "$0")/../.."
 O=gpurun_out/r6/occ2; mkdir -p $O
 for occ in 3 2 3 2; do
-  echo "REGTOOLS_AMD_INFLATE_OCC=$occ bench.py --no-extras --no-cpu-baseline --no-live-traffic" >> $O/ab.txt
-  REGTOOLS_AMD_INFLATE_OCC=$occ timeout 600 python bench.py --no-extras --no-cpu-baseline --no-live-traffic 2>> $O/ab.err | python -c "
+  echo "REGTOOLS_AMD_INFLATE_OCC=$occ bench.py --full --no-extras --no-cpu-baseline --no-live-traffic" >> $O/ab.txt
+  REGTOOLS_AMD_INFLATE_OCC=$occ timeout 600 python bench.py --full --no-extras --no-cpu-baseline --no-live-traffic 2>> $O/ab.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'ms_per_step': round(d['ms_per_step'],3), 'resident': round(d['ms_per_step_device_resident'],3), 'sustained': d['sustained']['ms_per_file'] if d.get('sustained') else None, 'kernel_ms': round(d['roofline']['kernel_ms'],3), 'in_step': round(d['roofline']['kernel_ms_in_step'],3), 'stage_ms': d['stage_ms']}))" >> $O/ab.txt

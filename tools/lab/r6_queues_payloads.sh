@@ -11,7 +11,7 @@ echo "realistic GPU_MAX_HW_QUEUES=16" >> $O/ab.txt
 GPU_MAX_HW_QUEUES=16 timeout 600 python tools/sustained_ab.py --realistic --files 8 --depths 2,3 2>> $O/ab.err >> $O/ab.txt
 for q in 4 16; do
   echo "long reads (10 M) GPU_MAX_HW_QUEUES=$q: bench.py's own lines" >> $O/ab.txt
-  GPU_MAX_HW_QUEUES=$q timeout 900 python bench.py --no-extras --no-cpu-baseline --no-live-traffic --shape long --reads 10000000 --steps 3 2>> $O/ab.err | python -c "
+  GPU_MAX_HW_QUEUES=$q timeout 900 python bench.py --full --no-extras --no-cpu-baseline --no-live-traffic --shape long --reads 10000000 --steps 3 2>> $O/ab.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'ms_per_step': round(d['ms_per_step'],3), 'resident': round(d['ms_per_step_device_resident'],3), 'sustained': d['sustained']}))" >> $O/ab.txt

@@ -3,7 +3,7 @@
 # (k_seg_walk, k_decode_seg, k_emit_short, the radix passes) against their algorithmic bytes.  usage: tools/pmc_tail.sh <outdir>
 R=$(cd "$(dirname "$0")/.." && pwd); OUT=${1:-gpurun_out/r3/pmc_tail}; mkdir -p $R/$OUT; export TMPDIR=/tmp; cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/$c -o p -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras > $R/$OUT/$c.log 2>&1
+  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/$c -o p -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras > $R/$OUT/$c.log 2>&1
 done
 cd $R
 python - "$OUT" <<'PY'

@@ -7,7 +7,7 @@ for pmc in "GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT
            "TCP_TOTAL_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum" \
            "TCP_GATE_EN1_sum TCP_TA_TCP_STATE_READ_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $R/$OUT/q$i -o p -- python $R/bench.py --reads $READS --steps 1 --warmup 0 --no-cpu-baseline > $R/$OUT/q$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $R/$OUT/q$i -o p -- python $R/bench.py --full --reads $READS --steps 1 --warmup 0 --no-cpu-baseline > $R/$OUT/q$i.log 2>&1
 done
 cd $R
 python3 - <<PY

@@ -6,7 +6,7 @@ hipcc --offload-arch=gfx950 -O3 $R/tools/ubench_unaligned.hip -o /tmp/ub 2>/dev/
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/cal_$c -o p -- /tmp/ub > $R/$OUT/cal_$c.log 2>&1
-  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/bench_$c -o p -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras > $R/$OUT/bench_$c.log 2>&1
+  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/bench_$c -o p -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras > $R/$OUT/bench_$c.log 2>&1
 done
 cd $R
 python3 - <<PY
