@@ -218,6 +218,72 @@ size_t rgx_table_format_bed12(const rgx_junction_table *t, int only_anchored, ch
  * `cis-splice-effects identify -b` writes: its extractor never collects any, identifier.cc:288, :239-241). */
 size_t rgx_table_format_barcodes(const rgx_junction_table *t, int only_anchored, char *buf, size_t cap);
 
+/* =====================================================================================================
+ * Cohort matrix: the union of the junctions of many samples with one read-count column per sample.
+ * Replaces the per-sample loop plus the merge a cohort run makes after junctions_main.cc:45-59 -- N BED files joined by a script; the reference has
+ * no counterpart.  A cohort is an ordered list of samples (0..S-1 in the order added), each one junction table plus a name.
+ *   rows that take part   only_anchored: the rows with both anchors, i.e. the lines of that sample's `junctions extract` BED12 (print_all_junctions,
+ *                         junctions_extractor.cc:267), computed from the row's own numbers -- start - thick_start >= min_anchor && thick_end - end >=
+ *                         min_anchor, unsigned 32-bit -- never from the flag bytes; otherwise every row
+ *   contigs               matched by NAME: the cohort's list is the samples' header names in order of first appearance; one name with two lengths is
+ *                         RGX_ERR_ARG (the message names the contig and both samples)
+ *   key                   (cohort tid, start, end, strand class: '+' 0, '-' 1, anything else 2), the reference's own (junctions_extractor.cc:180-194);
+ *                         a sample has at most one row per key
+ *   per junction          n_with = samples that have it, total = sum of their read counts (64 bit), thick_start = min, thick_end = max, strand = the
+ *                         character of the highest-numbered sample that has it; the per-sample counts as a CSR image
+ *   order and names       rows ascend by (cohort tid, start, end, class); row i is JUNC%08d of i + 1 (the cohort's own rule)
+ *   filters               rows below min_samples or min_total are dropped before naming
+ * ===================================================================================================== */
+typedef struct rgx_cohort rgx_cohort;
+typedef struct { int32_t only_anchored; uint32_t min_samples; uint64_t min_total; } rgx_cohort_params;
+/* Replaces nothing in the reference (see above): the finished matrix, structure-of-arrays, owned by the library (rgx_cohort_matrix_free). */
+typedef struct {
+    int32_t    n_ref;           /* the cohort's contig table */
+    char     **ref_name;
+    uint32_t  *ref_len;
+    uint32_t   n_samples;
+    char     **sample_name;
+    uint64_t   n;               /* rows */
+    uint32_t  *tid;             /* index into ref_name */
+    uint32_t  *start, *end, *thick_start, *thick_end;
+    char      *strand;
+    uint32_t  *n_with;          /* samples that have the row */
+    uint64_t  *total;           /* sum of their read counts */
+    uint64_t  *row_begin;       /* n + 1: row i owns col_sample / val_count [row_begin[i], row_begin[i + 1]) */
+    uint32_t  *col_sample;      /* ascending within a row */
+    uint32_t  *val_count;
+    /* statistics */
+    double     ms_add_total;    /* host time spent inside the adds so far (device path: a scan of the host table and an enqueue) */
+    double     ms_finish;       /* this finish, wall, up to the rows being in host memory */
+    uint64_t   n_triples;       /* (junction, sample, count) triples accumulated */
+} rgx_cohort_matrix;
+void rgx_cohort_params_default(rgx_cohort_params *p);                       /* 1, 1, 1 */
+/* The accumulator lives in the HBM of ctx's device (blocks of 4 M triples, 28 bytes each; blocks are added, never re-copied).  Fewer than 2^24 samples
+ * and at most 2^32 - 2^16 triples (RGX_ERR_ARG beyond either); RGX_ERR_DEVICE when HBM runs out. */
+int  rgx_cohort_create(rgx_ctx *ctx, const rgx_cohort_params *p, rgx_cohort **out, char *err, size_t errlen);
+/* src_ctx: the context t came from (rgx_pipeline_ctx of the ticket for a pipeline's table), or NULL.  When t is still the last table of src_ctx on
+ * the cohort's device the rows go device to device -- on the cohort's own stream, behind src_ctx's last kernel by an event, no host wait; src_ctx's
+ * next call waits for that copy the same way, so add a pipeline's file k BEFORE submitting file k + depth.  Otherwise they are uploaded from t.  Same result. */
+int  rgx_cohort_add(rgx_cohort *co, rgx_ctx *src_ctx, const rgx_junction_table *t, uint32_t min_anchor,
+                    const char *sample_name, uint32_t *sample_index, char *err, size_t errlen);
+int  rgx_cohort_add_path(rgx_cohort *co);   /* statistics: 1 = the last add took the device path, 0 = the upload */
+/* One key-carrying radix sort of the triples, head flags, scans and single-writer segmented passes on the device; one copy of the matrix comes back.
+ * May be called again after more adds. */
+int  rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *err, size_t errlen);
+void rgx_cohort_destroy(rgx_cohort *co);
+void rgx_cohort_matrix_free(rgx_cohort_matrix *m);
+/* Host twin of add + finish (as rgx_table_merge is of rgx_table_merge_device): plain C++ on host tables, its own code path, no device.  NOT a fallback:
+ * it is what the device result is checked against.  min_anchor[k] and names[k] belong to tables[k]. */
+int  rgx_cohort_merge_host(const rgx_junction_table *const *tables, const uint32_t *min_anchor, const char *const *names, int n,
+                           const rgx_cohort_params *p, rgx_cohort_matrix **out, char *err, size_t errlen);
+/* BED12 of the cohort, one line per row laid out as Junction::print does (junctions_extractor.h:90-98): chromStart/End and thickStart/End are the
+ * cohort's thick bounds, the score is total, the blocks start - thick_start, thick_end - end and 0, end - thick_start.  Buffer protocol of
+ * rgx_table_format_bed12. */
+size_t rgx_cohort_format_bed12(const rgx_cohort_matrix *m, char *buf, size_t cap);
+/* The counts table: "chrom\tstart\tend\tstrand" and one "\t<sample name>" per sample, then one line per row with the junction's own start / end and
+ * S dense counts (0 where a sample lacks the key).  Same buffer protocol. */
+size_t rgx_cohort_format_counts(const rgx_cohort_matrix *m, char *buf, size_t cap);
+
 /* Library/build identification: "regtools_amd <version> gfx950". */
 const char *rgx_version(void);
 

@@ -49,7 +49,23 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_associate", "rgx_variants_annotate", "rgx_junctions_annotate", "rgx_junctions_annotate_opts", "rgx_table_merge_device", "rgx_window_join", "rgx_window_rows_free", "rgx_last_table_pack_device",
            "rgx_host_alloc", "rgx_host_free", "rgx_extract_multi", "rgx_extract_multi_mem", "rgx_multi_exchange_kind", "rgx_k_inflate_form", "rgx_table_merge_barcodes",
            "rgx_table_pack_barcodes", "rgx_table_unpack_barcodes", "rgx_identify_multi", "rgx_ctx_arena_trials",
-           "rgx_pipeline_create", "rgx_pipeline_depth", "rgx_pipeline_ctx", "rgx_extract_submit", "rgx_extract_wait", "rgx_pipeline_destroy"]
+           "rgx_pipeline_create", "rgx_pipeline_depth", "rgx_pipeline_ctx", "rgx_extract_submit", "rgx_extract_wait", "rgx_pipeline_destroy",
+           "rgx_cohort_params_default", "rgx_cohort_create", "rgx_cohort_add", "rgx_cohort_add_path", "rgx_cohort_finish", "rgx_cohort_destroy",
+           "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts"]
+
+
+class CohortParams(C.Structure):
+    _fields_ = [("only_anchored", C.c_int32), ("min_samples", C.c_uint32), ("min_total", C.c_uint64)]
+
+
+class CohortMatrix(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("ref_name", C.POINTER(C.c_char_p)), ("ref_len", C.POINTER(C.c_uint32)),
+                ("n_samples", C.c_uint32), ("sample_name", C.POINTER(C.c_char_p)), ("n", C.c_uint64),
+                ("tid", C.POINTER(C.c_uint32)), ("start", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32)),
+                ("thick_start", C.POINTER(C.c_uint32)), ("thick_end", C.POINTER(C.c_uint32)), ("strand", C.POINTER(C.c_char)),
+                ("n_with", C.POINTER(C.c_uint32)), ("total", C.POINTER(C.c_uint64)), ("row_begin", C.POINTER(C.c_uint64)),
+                ("col_sample", C.POINTER(C.c_uint32)), ("val_count", C.POINTER(C.c_uint32)),
+                ("ms_add_total", C.c_double), ("ms_finish", C.c_double), ("n_triples", C.c_uint64)]
 
 
 class IdentifyParams(C.Structure):
@@ -172,6 +188,19 @@ def lib():
         L.rgx_junction_annot_free.argtypes = [P(JunctionAnnot)]
         L.rgx_window_join.argtypes = [C.c_void_p, C.c_char_p, P(ExtractParams), C.c_uint64, P(C.c_char_p), P(C.c_int32), P(C.c_int32), P(P(WindowRows)), C.c_char_p, C.c_size_t]
         L.rgx_window_rows_free.argtypes = [P(WindowRows)]
+        L.rgx_cohort_params_default.argtypes = [P(CohortParams)]
+        L.rgx_cohort_create.argtypes = [C.c_void_p, P(CohortParams), P(C.c_void_p), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_add.argtypes = [C.c_void_p, C.c_void_p, P(JunctionTable), C.c_uint32, C.c_char_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_add_path.argtypes = [C.c_void_p]
+        L.rgx_cohort_finish.argtypes = [C.c_void_p, P(P(CohortMatrix)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_destroy.argtypes = [C.c_void_p]
+        L.rgx_cohort_matrix_free.argtypes = [P(CohortMatrix)]
+        L.rgx_cohort_merge_host.argtypes = [P(P(JunctionTable)), P(C.c_uint32), P(C.c_char_p), C.c_int, P(CohortParams), P(P(CohortMatrix)),
+                                            C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_bed12.argtypes = [P(CohortMatrix), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_bed12.restype = C.c_size_t
+        L.rgx_cohort_format_counts.argtypes = [P(CohortMatrix), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_counts.restype = C.c_size_t
         _lib = L
     return _lib
 

@@ -1,0 +1,222 @@
+"""The cohort junction-by-sample count matrix (rgx_cohort_* in include/regtools_amd.h): the union of many samples' junctions with one read-count
+column per sample -- the table a cohort run builds after its loop around `regtools junctions extract` (junctions_main.cc:45-59); the reference has
+no counterpart.  Rows are accumulated and merged in HBM (csrc/cohort_kernels.hip); `merge_host` is the library's plain C++ twin of the same contract.
+"""
+import ctypes as C
+import os
+
+from . import _ffi
+from .extractor import Context, PinnedBuffer, Pipeline, RegtoolsError
+
+
+def _params(only_anchored, min_samples, min_total):
+    p = _ffi.CohortParams()
+    _ffi.lib().rgx_cohort_params_default(C.byref(p))
+    p.only_anchored, p.min_samples, p.min_total = (1 if only_anchored else 0), min_samples, min_total
+    return p
+
+
+def _text(fn, handle):
+    n = fn(handle, None, 0)
+    buf = C.create_string_buffer(n + 1)
+    fn(handle, buf, n)
+    return buf.raw[:n]
+
+
+class CohortMatrix(object):
+    """rgx_cohort_matrix.  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+
+    def __init__(self, handle):
+        import numpy as np               # (only the matrix needs it: importing the package does not)
+        self._lib = _ffi.lib()
+        self._h = handle
+        m = handle.contents
+        self.n, self.n_samples, self.n_triples = int(m.n), int(m.n_samples), int(m.n_triples)
+        self.ms_add_total, self.ms_finish = m.ms_add_total, m.ms_finish
+        self.ref_name = [m.ref_name[i].decode() for i in range(m.n_ref)]
+        self.ref_len = [int(m.ref_len[i]) for i in range(m.n_ref)]
+        self.sample_name = [m.sample_name[i].decode() for i in range(m.n_samples)]
+        nnz = int(m.row_begin[self.n])
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        self.tid, self.start, self.end = view(m.tid, self.n, np.uint32), view(m.start, self.n, np.uint32), view(m.end, self.n, np.uint32)
+        self.thick_start, self.thick_end = view(m.thick_start, self.n, np.uint32), view(m.thick_end, self.n, np.uint32)
+        self.n_with, self.total = view(m.n_with, self.n, np.uint32), view(m.total, self.n, np.uint64)
+        self.strand = np.frombuffer(C.string_at(m.strand, self.n), dtype="S1") if self.n else np.zeros(0, "S1")
+        self.row_begin = np.ctypeslib.as_array(m.row_begin, shape=(self.n + 1,))
+        self.col_sample, self.val_count = view(m.col_sample, nnz, np.uint32), view(m.val_count, nnz, np.uint32)
+
+    def csr(self):
+        return self.row_begin, self.col_sample, self.val_count
+
+    def dense(self):
+        """n x S uint32, 0 where a sample lacks the junction."""
+        import numpy as np
+        d = np.zeros((self.n, self.n_samples), np.uint32)
+        rows = np.repeat(np.arange(self.n), np.diff(self.row_begin).astype(np.int64))
+        d[rows, self.col_sample] = self.val_count
+        return d
+
+    def bed12(self):
+        return _text(self._lib.rgx_cohort_format_bed12, self._h)
+
+    def counts_tsv(self):
+        return _text(self._lib.rgx_cohort_format_counts, self._h)
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_matrix_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1):
+    """rgx_cohort_merge_host over the tables the extractors hold (each with its own min_anchor_length_): no device involved."""
+    lib = _ffi.lib()
+    n = len(extractors)
+    tabs = (C.POINTER(_ffi.JunctionTable) * max(n, 1))(*[je.table for je in extractors])
+    anchors = (C.c_uint32 * max(n, 1))(*[je.min_anchor_length_ & 0xffffffff for je in extractors])
+    nm = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    p = _params(only_anchored, min_samples, min_total)
+    out = C.POINTER(_ffi.CohortMatrix)()
+    err = C.create_string_buffer(512)
+    rc = lib.rgx_cohort_merge_host(tabs, anchors, nm, n, C.byref(p), C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortMatrix(out)
+
+
+def _index_bytes(path):
+    """hts_idx_load's order (hts.c:2031-2042): <fn>.csi, <stem>.csi, <fn>.bai, <stem>.bai."""
+    stem = os.path.splitext(path)[0]
+    for cand in (path + ".csi", stem + ".csi", path + ".bai", stem + ".bai"):
+        if os.path.exists(cand):
+            with open(cand, "rb") as f:
+                return f.read()
+    raise RegtoolsError(2, "Unable to open BAM/SAM index. Make sure alignments are indexed\n\n")
+
+
+class Cohort(object):
+    """rgx_cohort: samples are numbered in the order they are added."""
+
+    def __init__(self, ctx=None, device=0, only_anchored=True, min_samples=1, min_total=1):
+        self._lib = _ffi.lib()
+        self._ctx = ctx if ctx is not None else Context(device)
+        self._device = device
+        self._h = C.c_void_p()
+        self.add_paths = []                      # per add: 1 = device to device, 0 = uploaded (rgx_cohort_add_path)
+        p = _params(only_anchored, min_samples, min_total)
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_create(self._ctx._h, C.byref(p), C.byref(self._h), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+
+    def add(self, je, name):
+        """je: a JunctionsExtractor that holds a table.  Its context goes along, so a table that is still that context's last one (a
+        Pipeline.wait result before the file `depth` tickets later is submitted; a sequential extraction) never leaves HBM."""
+        idx = C.c_uint32()
+        err = C.create_string_buffer(512)
+        src = je._ctx._h if je._ctx is not None else None
+        rc = self._lib.rgx_cohort_add(self._h, src, je.table, je.min_anchor_length_ & 0xffffffff, name.encode(), C.byref(idx), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        self.add_paths.append(self._lib.rgx_cohort_add_path(self._h))
+        return idx.value
+
+    def finish(self):
+        out = C.POINTER(_ffi.CohortMatrix)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_finish(self._h, C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        return CohortMatrix(out)
+
+    def run(self, files, depth=2, **extract_kw):
+        """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own
+        JunctionsExtractor arguments over extract_kw; the default name is the base name without ".bam".  File k is added BEFORE file k + depth is
+        submitted: that submit is what overwrites file k's rows in HBM.  When a file fails, the files in front of it are still added (the cohort
+        stays usable), the ones behind it that were in flight are dropped, and the file's error is raised."""
+        items = []
+        for it in files:
+            it = (it,) if isinstance(it, str) else tuple(it)
+            path = it[0]
+            base = os.path.basename(path)
+            name = it[1] if len(it) > 1 and it[1] else (base[:-4] if base.endswith(".bam") else base)
+            kw = dict(extract_kw)
+            if len(it) > 2:
+                kw.update(it[2])
+            items.append((path, name, kw))
+        pl = Pipeline(self._device, depth)
+        flight = {}                              # file index -> (ticket, PinnedBuffer, index bytes): this run's own references, until wait returns
+
+        def submit(k):
+            path, _, kw = items[k]
+            try:
+                with open(path, "rb") as f:
+                    data = f.read()
+            except OSError:
+                raise RegtoolsError(1, "[E::hts_open_format] fail to open file '%s'\nUnable to open BAM/SAM file.\n\n" % path)
+            bai = _index_bytes(path)
+            buf = PinnedBuffer(data)
+            flight[k] = (pl.submit(bai_bytes=bai, host_ptr=buf.ptr, host_len=buf.size, bam=path, **kw), buf, bai)
+
+        def wait(k, add):
+            ticket, buf, _ = flight[k]
+            try:
+                je = pl.wait(ticket)
+            finally:
+                del flight[k]
+                buf.close()
+            if add:
+                self.add(je, items[k][1])
+
+        try:
+            failed, error = None, None
+            nxt = 0
+            try:
+                while nxt < min(depth, len(items)):
+                    submit(nxt)
+                    nxt += 1
+            except RegtoolsError as e:
+                failed, error = nxt, e
+            k = 0
+            while k < len(items) and (failed is None or k < failed):
+                try:
+                    wait(k, True)
+                except RegtoolsError as e:
+                    failed, error = k, e
+                    break
+                k += 1
+                if failed is None and nxt < len(items):
+                    try:
+                        submit(nxt)
+                        nxt += 1
+                    except RegtoolsError as e:
+                        failed, error = nxt, e
+            for j in sorted(flight):             # behind a failed file: run to their end (their buffers were promised), results dropped
+                try:
+                    wait(j, False)
+                except RegtoolsError:
+                    pass
+            if error is not None:
+                raise error
+        finally:
+            pl.close()
+        return self
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -237,6 +237,197 @@ int junctions_annotate(int argc, char **argv) {
     return 0;
 }
 
+// ---- junctions cohort: many BAMs -> one junction-by-sample table.  The reference has no such command (a cohort run there is the loop around
+// `junctions extract`, junctions_main.cc:45-59, and a script); it is not listed in the usage texts the reference pins. --------------------------------
+void cohort_usage(std::ostream &out) {
+    out << "Usage:\t\tregtools-amd junctions cohort [options] -s STRANDNESS [-L list.txt] [a.bam b.bam ...]\n"
+        << "\t\tThe union of the samples' junctions (the lines of each sample's `junctions extract`) with one read-count column per sample.\n"
+        << "Options:\n"
+        << "\t\t-a INT\tMinimum anchor length, as in extract. [8]\n"
+        << "\t\t-m INT\tMinimum intron length. [70]\n"
+        << "\t\t-M INT\tMaximum intron length. [500000]\n"
+        << "\t\t-r STR\tThe region to identify junctions in, as in extract. Entire BAM by default.\n"
+        << "\t\t-s INT\tStrandness mode: XS, RF, FR. REQUIRED\n"
+        << "\t\t-t STR\tTag used in bam to label strand. [XS]\n"
+        << "\t\t-o FILE\tThe cohort's junctions as BED12; the score is the summed read count. [STDOUT]\n"
+        << "\t\t-c FILE\tThe counts table: chrom, start, end, strand and one column per sample.\n"
+        << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
+        << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
+        << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
+        << "\t\t-L FILE\tOne BAM path per line, optionally a tab and the sample's name.\n"
+        << "\t\t\t A sample's name is its file's base name without .bam unless the list gives one; names must differ.\n\n";
+}
+
+struct CohortInput { std::string path, name; };
+
+std::string cohort_default_name(const std::string &path) {
+    std::string b = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
+    if (b.size() > 4 && b.compare(b.size() - 4, 4, ".bam") == 0) b.resize(b.size() - 4);
+    return b;
+}
+
+// a whole file into page-locked memory (rgx_host_alloc): the form under which a pipeline's upload overlaps the inflate
+bool cohort_read_pinned(const std::string &path, void **out, size_t *len) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    bool ok = fseek(f, 0, SEEK_END) == 0;
+    const long n = ok ? ftell(f) : -1;
+    ok = ok && n >= 0 && fseek(f, 0, SEEK_SET) == 0;
+    void *p = ok ? rgx_host_alloc((size_t)n + 64) : nullptr;
+    ok = ok && p && (n == 0 || fread(p, 1, (size_t)n, f) == (size_t)n);
+    fclose(f);
+    if (!ok) { if (p) rgx_host_free(p); return false; }
+    *out = p; *len = (size_t)n;
+    return true;
+}
+
+// hts_idx_load's order (hts.c:2031-2042): <fn>.csi, <stem>.csi, <fn>.bai, <stem>.bai
+bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
+    const size_t dot = bam.find_last_of('.');
+    const std::string stem = dot == std::string::npos || dot == 0 ? bam : bam.substr(0, dot);
+    for (const std::string &cand : {bam + ".csi", stem + ".csi", bam + ".bai", stem + ".bai"}) {
+        FILE *f = fopen(cand.c_str(), "rb");
+        if (!f) continue;
+        out.clear();
+        char chunk[1 << 16]; size_t k;
+        while ((k = fread(chunk, 1, sizeof chunk, f)) > 0) out.insert(out.end(), chunk, chunk + k);
+        fclose(f);
+        return true;
+    }
+    return false;
+}
+
+int junctions_cohort(int argc, char **argv) {
+    try {
+        ExtractOptions o;
+        std::string counts = "NA";
+        rgx_cohort_params cp;
+        rgx_cohort_params_default(&cp);
+        std::vector<CohortInput> in;
+        optind = 1;
+        int c;
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:")) != -1) {
+            switch (c) {
+                case 'h': cohort_usage(std::cout); return 0;
+                case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
+                case 'm': o.min_intron = (uint32_t)atoi(optarg); break;
+                case 'M': o.max_intron = (uint32_t)atoi(optarg); break;
+                case 'r': o.region = optarg; break;
+                case 't': o.tag = optarg; break;
+                case 'o': o.output = optarg; break;
+                case 'c': counts = optarg; break;
+                case 'A': cp.only_anchored = 0; break;
+                case 'n': cp.min_samples = (uint32_t)atoi(optarg); break;
+                case 'N': cp.min_total = (uint64_t)atoll(optarg); break;
+                case 's': {
+                    std::string s = optarg;
+                    if (s == "XS") o.strandness = 0; else if (s == "RF") o.strandness = 1; else if (s == "FR") o.strandness = 2;
+                    else throw std::runtime_error("Unrecognized strandness argument!\n\n");
+                    break;
+                }
+                case 'L': {
+                    FILE *f = fopen(optarg, "r");
+                    if (!f) { cohort_usage(std::cerr); throw std::runtime_error(std::string("Unable to read the list of BAM files ") + optarg + "\n\n"); }
+                    char *line = nullptr; size_t cap = 0; ssize_t k;
+                    while ((k = getline(&line, &cap, f)) >= 0) {
+                        std::string s(line, (size_t)k);
+                        while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
+                        if (s.empty()) continue;
+                        const size_t tab = s.find('\t');
+                        CohortInput ci; ci.path = s.substr(0, tab);
+                        if (tab != std::string::npos) ci.name = s.substr(tab + 1);
+                        in.push_back(ci);
+                    }
+                    free(line); fclose(f);
+                    break;
+                }
+                default: cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(1)\n\n");
+            }
+        }
+        for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
+        if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
+        if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
+        for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
+        for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
+            throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
+
+        char err[512] = {0};
+        int device = 0; if (const char *d = getenv("REGTOOLS_AMD_DEVICE")) device = atoi(d);
+        // two files in flight: file k + 1 goes up and inflates under file k's tail, on the runtime's default hardware queues
+        rgx_pipeline *pl = nullptr;
+        if (rgx_pipeline_create(device, 2, &pl, err, sizeof err) != RGX_OK) throw std::runtime_error(err);
+        rgx_cohort *co = nullptr;
+        if (rgx_cohort_create(rgx_pipeline_ctx(pl, 1), &cp, &co, err, sizeof err) != RGX_OK) { rgx_pipeline_destroy(pl); throw std::runtime_error(err); }
+        rgx_extract_params p;
+        rgx_extract_params_default(&p);
+        p.region = o.region.c_str(); p.strandness = o.strandness;
+        p.strand_tag[0] = o.tag.size() > 0 ? o.tag[0] : 0; p.strand_tag[1] = o.tag.size() > 1 ? o.tag[1] : 0;
+        p.min_anchor = o.min_anchor; p.min_intron = o.min_intron; p.max_intron = o.max_intron;
+
+        struct Flight { void *bam = nullptr; size_t bam_len = 0; std::vector<char> index; uint64_t ticket = 0; };
+        std::vector<Flight> fl(in.size());
+        std::string failure;
+        auto submit = [&](size_t k) {
+            if (!cohort_read_pinned(in[k].path, &fl[k].bam, &fl[k].bam_len)) {
+                failure = "[E::hts_open_format] fail to open file '" + in[k].path + "'\nUnable to open BAM/SAM file.\n\n"; return false; }
+            if (!cohort_read_index(in[k].path, fl[k].index)) { failure = "Unable to open BAM/SAM index. Make sure alignments are indexed\n\n"; return false; }
+            if (rgx_extract_submit(pl, fl[k].bam, fl[k].bam_len, fl[k].index.data(), fl[k].index.size(), &p, &fl[k].ticket, err, sizeof err) != RGX_OK) {
+                failure = err; return false; }
+            return true;
+        };
+        size_t submitted = 0;
+        bool ok = true;
+        while (ok && submitted < std::min<size_t>(2, in.size())) ok = submit(submitted++);
+        int rc_abort = RGX_OK;
+        for (size_t k = 0; ok && k < in.size(); ++k) {
+            rgx_junction_table *t = nullptr;
+            int rc = rgx_extract_wait(pl, fl[k].ticket, &t, err, sizeof err);
+            rgx_host_free(fl[k].bam); fl[k].bam = nullptr;       // (the wait is over: the pipeline no longer reads the file)
+            if (rc == RGX_OK) rc = rgx_cohort_add(co, rgx_pipeline_ctx(pl, fl[k].ticket), t, o.min_anchor, in[k].name.c_str(), nullptr, err, sizeof err);
+            if (t) rgx_table_free(t);
+            if (rc != RGX_OK) { failure = err; rc_abort = rc; ok = false; break; }
+            // file k is added: the context it ran on may take the next file (whose rows overwrite file k's in HBM)
+            if (submitted < in.size()) ok = submit(submitted++);
+        }
+        rgx_cohort_matrix *m = nullptr;
+        if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        if (!ok) {
+            rgx_pipeline_destroy(pl);                       // (runs what is still queued to its end: the buffers below were promised to it)
+            for (Flight &f : fl) if (f.bam) rgx_host_free(f.bam);
+            rgx_cohort_destroy(co);
+            if (rc_abort == RGX_ERR_ABORT) { std::cerr.flush(); fflush(nullptr); abort(); }
+            throw std::runtime_error(failure);
+        }
+        // the texts first, the files after: a failure above leaves no output behind
+        const size_t nb = rgx_cohort_format_bed12(m, nullptr, 0);
+        std::unique_ptr<char[]> bed(new char[nb + 1]);
+        rgx_cohort_format_bed12(m, bed.get(), nb);
+        size_t nc = 0; std::unique_ptr<char[]> tsv;
+        if (counts != "NA") { nc = rgx_cohort_format_counts(m, nullptr, 0); tsv.reset(new char[nc + 1]); rgx_cohort_format_counts(m, tsv.get(), nc); }
+        bool short_write = false;
+        FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
+        if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
+        short_write = fwrite(bed.get(), 1, nb, f) != nb; if (f != stdout) short_write |= fclose(f) != 0; else short_write |= fflush(f) != 0;
+        if (counts != "NA") {
+            FILE *g = fopen(counts.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + counts + "\n\n");
+            short_write |= fwrite(tsv.get(), 1, nc, g) != nc; short_write |= fclose(g) != 0;
+        }
+        if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
+        if (getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
+                    (unsigned long long)m->n_triples, (unsigned long long)m->n, m->ms_add_total, m->ms_finish);
+        rgx_cohort_matrix_free(m);
+        rgx_cohort_destroy(co);
+        rgx_pipeline_destroy(pl);
+        for (Flight &fb : fl) if (fb.bam) rgx_host_free(fb.bam);
+    } catch (const std::runtime_error &e) {
+        std::cerr << e.what() << std::endl;
+        return 1;
+    }
+    return 0;
+}
+
 int junctions_usage(std::ostream &out) {
     out << "Usage:\t\tregtools junctions <command> [options]\n"
         << "Command:\textract\t\tIdentify exon-exon junctions from alignments.\n"
@@ -250,6 +441,7 @@ int junctions_main(int argc, char **argv) {
         std::string sub = argv[1];
         if (sub == "extract") return junctions_extract(argc - 1, argv + 1);
         if (sub == "annotate") return junctions_annotate(argc - 1, argv + 1);
+        if (sub == "cohort") return junctions_cohort(argc - 1, argv + 1);
     }
     return junctions_usage(std::cout);
 }

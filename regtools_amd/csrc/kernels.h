@@ -300,4 +300,26 @@ void launch_merge_pack(MergeUnique u, const uint32_t *order, const uint32_t *nam
 // the merged rows in the result table's host block layout (see launch_rows_table)
 void launch_merge_table(MergeUnique u, const uint32_t *order, const uint32_t *name_rank, uint32_t n, uint32_t min_anchor, uint8_t *out, hipStream_t st);
 
+// ---- cohort junction-by-sample matrix (cohort_kernels.hip; host side in cohort.cpp) ---------------------------------------------------------
+// The accumulator: blocks of kCohortBlockRows triples, seven u32 columns each (cohort tid, start, end, thick_start, thick_end, read_count,
+// strand char << 24 | sample index); triple k lies in block k >> kCohortBlockLog2.  `blocks` is the device table of the blocks' addresses.
+constexpr uint32_t kCohortBlockLog2 = 22, kCohortBlockRows = 1u << kCohortBlockLog2, kCohortColumns = 7;
+struct CohortSorted { uint32_t *tid, *start, *end, *ts, *te, *count, *ss; };                    // the triples in key order, n entries each
+struct CohortRows { uint32_t *ts, *te, *keep, *kept_nnz; unsigned long long *total; };           // one entry per distinct key
+// the finished matrix as it lies in the host block (cohort.cpp MatrixLayout): written on the device, copied once
+struct CohortImage { unsigned long long *total, *row_begin; uint32_t *tid, *start, *end, *ts, *te, *n_with, *col_sample, *val_count; uint8_t *strand; };
+// src: u32 columns `stride` words apart, strand at column strand_col; *fill = triples accumulated so far (one atomicAdd per wave); cap = rows the blocks hold
+void launch_cohort_append(const uint32_t *src, uint32_t n, size_t stride, uint32_t strand_col, const uint32_t *tid_map, uint32_t n_map, uint32_t min_anchor,
+                          bool only_anchored, uint32_t sample, uint32_t *fill, uint32_t cap, uint32_t *const *blocks, hipStream_t st);
+// out[i] = key word `which` (0 tid, 1 start, 2 end, 3 strand class) of triple perm[i] (null = i)
+void launch_cohort_key(uint32_t *const *blocks, const uint32_t *perm, uint32_t n, uint32_t which, uint32_t *out, hipStream_t st);
+// the triples in the order of perm, and head[i] = 1 where position i starts a new key
+void launch_cohort_gather(uint32_t *const *blocks, const uint32_t *perm, uint32_t n, CohortSorted s, uint32_t *head, hipStream_t st);
+void launch_cohort_row_start(const uint32_t *head, const uint32_t *seg_excl, uint32_t n, uint32_t *row_start /* rows + 1 */, hipStream_t st);
+void launch_cohort_reduce(CohortSorted s, const uint32_t *row_start, uint32_t n, uint32_t n_rows, uint32_t min_samples, uint64_t min_total, CohortRows r,
+                          hipStream_t st);
+// out_row / nnz_excl = exclusive scans of r.keep / r.kept_nnz
+void launch_cohort_out(CohortSorted s, const uint32_t *head, const uint32_t *seg_excl, const uint32_t *row_start, CohortRows r, const uint32_t *out_row,
+                       const uint32_t *nnz_excl, uint32_t n, uint32_t n_rows, uint32_t n_nnz_kept, CohortImage o, hipStream_t st);
+
 }  // namespace rgx

@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""Measure the cohort junction-by-sample matrix (rgx_cohort_*) on one MI355X.  Prints one JSON line per part.
+
+  --part pipeline   what accumulation costs the pipeline: sustained ms per file of a depth-2 Pipeline over --files submissions of one
+                    configs[1]-shaped file (--reads), WITHOUT Cohort.add after each wait (the yardstick: the pipeline as it was) and WITH it,
+                    alternating in one process, --reps times each; the two sets of times are printed whole
+  --part finish     rgx_cohort_finish (ms_finish) beside rgx_cohort_merge_host on the same rows, for every SAMPLESxROWS of --sizes; the matrices
+                    are compared; bytes moved per triple (counted from the passes, see finish_bytes_per_triple) over ms_finish against 8 TB/s
+
+Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ANCHOR = 8
+
+
+class Sample(object):
+    """What Cohort.add and cohort.merge_host read of an extractor, over a table made with numpy."""
+
+    def __init__(self, table):
+        self.table, self.min_anchor_length_, self._ctx = table, ANCHOR, None
+
+
+MIXES = {"sparse": (5, 5, 10 / 3.0),      # a fifth of a sample's keys are in every sample, a fifth in no other, the rest drawn from a pool of 2 x rows
+         "shared": (6, 150, 5.0)}          # a sixth in every sample, 1 in 150 private, the rest from a pool of 5 x as many: most keys are in dozens of samples
+
+
+def make_sample(g, rows, rng, mix):
+    """`rows` rows of sample g (tests/test_gpu_cohort.py builds its samples the same way)."""
+    from regtools_amd import _ffi
+    c, p, pool = MIXES[mix]
+    common, private = rows // c, max(1, rows // p)
+    draw = rows - common - private
+    n_pool = int(draw * pool)
+    ids = np.concatenate([np.arange(common), common + rng.choice(n_pool, draw, replace=False),
+                          common + n_pool + g * private + np.arange(private)]).astype(np.int64)
+    ids = rng.permutation(ids)
+    t = np.zeros((rows, 12), np.uint32)
+    start = 1000 + 3 * (ids // 23) + 40 * (ids % 2)
+    end = start + 100 + ids % 50
+    t[:, 0], t[:, 1], t[:, 2] = ids % 23, start, end
+    t[:, 3] = start - ANCHOR - (ids * 3 + g * 5) % 20
+    t[:, 4] = end + ANCHOR + (ids * 7 + g * 11) % 20
+    t[:, 5] = 1 + (ids * 7 + g) % 9
+    t[:, 10] = np.where(ids % 3 == 0, ord("-"), ord("+"))
+    proto = _ffi.JunctionTable()
+    arr = (C.c_char_p * 23)(*[b"c%02d" % k for k in range(23)])
+    lens = (C.c_uint32 * 23)(*([250_000_000] * 23))
+    proto.n_ref, proto.ref_name, proto.ref_len = 23, arr, lens
+    out = C.POINTER(_ffi.JunctionTable)()
+    assert _ffi.lib().rgx_table_unpack(t.tobytes(), rows, C.byref(proto), C.byref(out)) == 0
+    return out
+
+
+def finish_bytes_per_triple(start_bits, end_bits, tid_bits):
+    """HBM bytes per triple that finish's passes read and write: per key word one gather (permutation 4 + word 4 in, 4 out) and per
+    8-bit pass a histogram read of the key (4) and a scatter (key + permutation in and out, 16); then the gather of the seven columns (4 + 28 in,
+    28 out), the head flags (16 in, 4 out), their scan (4 in twice, 4 out), the row starts (8 in), the reduction (12 in) and the CSR image
+    (4 x 4 in, 8 out).  Per-row words and the copy to the host are not counted."""
+    passes = 1 + (end_bits + 7) // 8 + (start_bits + 7) // 8 + (tid_bits + 7) // 8
+    return 4 * 12 + passes * 20 + 60 + 20 + 12 + 8 + 12 + 24
+
+
+def part_finish(a):
+    import regtools_amd
+    from regtools_amd import _ffi, cohort
+    ctx = regtools_amd.Context(0)
+    for size in a.sizes.split(","):
+        shape, _, mix = size.partition(":")
+        mix = mix or "sparse"
+        n_samples, rows = [int(x) for x in shape.lower().split("x")]
+        rng = np.random.default_rng(3)
+        t0 = time.time()
+        tables = [make_sample(g, rows, rng, mix) for g in range(n_samples)]
+        samples, names = [Sample(t) for t in tables], ["s%04d" % g for g in range(n_samples)]
+        t_gen = time.time() - t0
+        co = regtools_amd.Cohort(ctx=ctx)
+        t0 = time.time()
+        for s, nm in zip(samples, names):
+            co.add(s, nm)
+        t_add = time.time() - t0
+        ms = []
+        for _ in range(a.reps):                      # (the first finish grows the cohort's workspace and the page-locked result block)
+            m = co.finish()
+            ms.append(round(m.ms_finish, 3))
+        bits = (int(m.start.max()).bit_length(), int(m.end.max()).bit_length(), max(1, (len(m.ref_name) - 1).bit_length()))
+        bpt = finish_bytes_per_triple(*bits)
+        best = min(ms[1:] or ms)
+        line = {"part": "finish", "mix": mix, "samples": n_samples, "rows_per_sample": rows, "triples": m.n_triples, "rows": m.n, "mean_samples_per_row": round(m.n_triples / max(1, m.n), 2),
+                "ms_finish": ms, "ms_finish_best_warm": best, "s_generate": round(t_gen, 2), "ms_add_wall_upload_path": round(1e3 * t_add, 1),
+                "bytes_per_triple_counted": bpt, "TBps_over_ms_finish": round(bpt * m.n_triples / best / 1e9, 3),
+                "share_of_8TBps": round(bpt * m.n_triples / best / 1e9 / 8.0, 4)}
+        if not a.no_host:
+            t0 = time.time()
+            h = cohort.merge_host(samples, names)
+            line["ms_merge_host_wall"] = round(1e3 * (time.time() - t0), 1)
+            line["ms_merge_host"] = round(h.ms_finish, 1)
+            line["device_over_host"] = round(h.ms_finish / best, 1)
+            same = (m.n, m.n_triples) == (h.n, h.n_triples) and all(np.array_equal(getattr(m, k), getattr(h, k)) for k in
+                    ("tid", "start", "end", "thick_start", "thick_end", "strand", "n_with", "total", "row_begin", "col_sample", "val_count"))
+            line["identical_to_host"] = bool(same)
+            assert same, "the device matrix differs from the host twin's"
+            h.close()
+        m.close()
+        co.close()
+        for t in tables:
+            _ffi.lib().rgx_table_free(t)
+        print(json.dumps(line), flush=True)
+
+
+def part_pipeline(a):
+    import regtools_amd
+    from regtools_amd import synth
+    t0 = time.time()
+    bam, bai, st = synth.generate(a.reads, shape="short", seed=1, threads=min(16, os.cpu_count() or 8))
+    t_gen = time.time() - t0
+    pin = regtools_amd.PinnedBuffer(bam)
+    ctx = regtools_amd.Context(0)
+    pl = regtools_amd.Pipeline(0, 2)
+
+    def run(nf, co):
+        """nf files, two in flight; file k is added (when there is a cohort) before file k + 2 is submitted.  Returns the seconds from the first
+        submit to the last wait's return (bench.py's sustained pass).  An add is an enqueue; the finish that follows OUTSIDE the window drains the
+        cohort's stream and shows that every append ran."""
+        t = time.time()
+        tickets = [pl.submit(bai_bytes=bai, host_ptr=pin.ptr, host_len=len(bam), strandness=0) for _ in range(min(2, nf))]
+        rows = 0
+        for k in range(nf):
+            je = pl.wait(tickets[k])
+            rows = je.table.contents.n
+            if co is not None:
+                co.add(je, "f%d" % len(co.add_paths))
+            if k + 2 < nf:
+                tickets.append(pl.submit(bai_bytes=bai, host_ptr=pin.ptr, host_len=len(bam), strandness=0))
+        return time.time() - t, rows
+
+    run(4, None)                                     # both contexts' first calls: their workspaces
+    warm = regtools_amd.Cohort(ctx=ctx)
+    run(4, warm)
+    warm.finish().close(); warm.close()
+    without, with_, paths, finish_ms, rows = [], [], [], [], 0
+    for _ in range(a.reps):
+        dt, rows = run(a.files, None)
+        without.append(round(1e3 * dt / a.files, 3))
+        co = regtools_amd.Cohort(ctx=ctx)
+        dt, rows = run(a.files, co)
+        with_.append(round(1e3 * dt / a.files, 3))
+        paths.append(sum(co.add_paths))
+        m = co.finish()                              # (outside the window; also proves every append ran)
+        assert m.n_samples == a.files and m.n_triples > 0
+        finish_ms.append(round(m.ms_finish, 3)); add_ms = m.ms_add_total
+        m.close(); co.close()
+    pl.close()
+    overlap = min(with_) <= max(without) and min(without) <= max(with_)
+    print(json.dumps({"part": "pipeline", "reads": st["n_reads"], "file_MB": round(len(bam) / 1e6, 1), "rows_per_file": int(rows), "files": a.files,
+                      "in_flight": 2, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", ""), "s_generate": round(t_gen, 1),
+                      "ms_per_file_without_cohort": without, "ms_per_file_with_cohort_add": with_, "ranges_overlap": bool(overlap),
+                      "device_path_adds_per_run": paths, "ms_in_add_per_file_host": round(add_ms / a.files, 4), "ms_finish_of_the_run": finish_ms}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", default="all", choices=["all", "pipeline", "finish"])
+    ap.add_argument("--reads", type=int, default=50_000_000)
+    ap.add_argument("--files", type=int, default=24)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", default="64x100000:sparse,512x300000:shared", help="SAMPLESxROWS[:sparse|shared], comma separated")
+    ap.add_argument("--no-host", action="store_true", help="skip rgx_cohort_merge_host (profiling runs)")
+    a = ap.parse_args()
+    if a.part in ("all", "pipeline"):
+        part_pipeline(a)
+    if a.part in ("all", "finish"):
+        part_finish(a)
+
+
+if __name__ == "__main__":
+    main()
