@@ -380,41 +380,31 @@ extern "C" int rgx_table_merge_device(rgx_ctx *c, const void *d_rows, uint64_t s
     uint32_t rk = 0; for (uint32_t r : rank_of_tid) rk = std::max(rk, r);
 
     DevBuf &b = c->buf("merge"), &sc = c->buf("scalars");
-    HIP_TRY(sc.ensure(512));
+    HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t Nn = N, P = (size_t)n_parts, R = rank_of_tid.size();
     const size_t tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;
     HIP_TRY(b.ensure((Nn * (10 + 2 + 2 + 9 + 4 + 13) + 64 + 2 * P + R + tmp_words) * 4 + 1024));
-    uint32_t *w = b.as<uint32_t>();
-    MergeSoA m; m.tid = w; w += Nn; m.start = w; w += Nn; m.end = w; w += Nn; m.ts = w; w += Nn; m.te = w; w += Nn; m.count = w; w += Nn;
-    m.cls = w; w += Nn; m.first = w; w += Nn; m.shard = w; w += Nn; m.strand = w; w += Nn;
-    uint32_t *perm[2] = {w, w + Nn}; w += 2 * Nn;
-    uint32_t *head = w; w += Nn; uint32_t *seg = w; w += Nn;
-    MergeUnique u; u.tid = w; w += Nn; u.start = w; w += Nn; u.end = w; w += Nn; u.ts = w; w += Nn; u.te = w; w += Nn; u.count = w; w += Nn;
-    u.first = w; w += Nn; u.last_shard = w; w += Nn; u.strand = w; w += Nn;
-    uint32_t *name_rank = w; w += Nn; uint32_t *crank = w; w += Nn; uint32_t *uperm[2] = {w, w + Nn}; w += 2 * Nn;
-    uint32_t *packed = w; w += Nn * 13 + 64;          // the merged table's device image (51 bytes per row + padding)
-    uint32_t *d_rows_n = w; w += P; uint32_t *d_base = w; w += P; uint32_t *d_rank = w; w += R;
-    uint32_t *tmp = w;
-    uint32_t *d_total = sc.as<uint32_t>() + 70;
+    Carve w(b);
+    MergeSoA m; m.tid = w.u32(Nn); m.start = w.u32(Nn); m.end = w.u32(Nn); m.ts = w.u32(Nn); m.te = w.u32(Nn); m.count = w.u32(Nn);
+    m.cls = w.u32(Nn); m.first = w.u32(Nn); m.shard = w.u32(Nn); m.strand = w.u32(Nn);
+    uint32_t *perm0 = w.u32(Nn), *perm1 = w.u32(Nn), *head = w.u32(Nn), *seg = w.u32(Nn);
+    MergeUnique u; u.tid = w.u32(Nn); u.start = w.u32(Nn); u.end = w.u32(Nn); u.ts = w.u32(Nn); u.te = w.u32(Nn); u.count = w.u32(Nn);
+    u.first = w.u32(Nn); u.last_shard = w.u32(Nn); u.strand = w.u32(Nn);
+    uint32_t *name_rank = w.u32(Nn), *crank = w.u32(Nn), *uperm0 = w.u32(Nn), *uperm1 = w.u32(Nn);
+    uint32_t *packed = w.u32(Nn * 13 + 64);           // the merged table's device image (51 bytes per row + padding)
+    uint32_t *d_rows_n = w.u32(P), *d_base = w.u32(P), *d_rank = w.u32(R), *tmp = w.u32(tmp_words); CARVE_TRY(w, "merge");
+    uint32_t *d_total = &sc.as<Scalars>()->merge_unique;
     HIP_TRY(hipMemcpyAsync(d_rows_n, h_rows.data(), P * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_base, h_base.data(), P * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_rank, rank_of_tid.data(), R * 4, hipMemcpyHostToDevice, st));
     launch_merge_unpack((const uint32_t *)d_rows, (uint32_t)stride_rows, (uint32_t)n_parts, d_rows_n, d_base, m, st);
     // stable LSD radix sort by (tid, start, end, class); rows of one key end up in shard order
-    int pc = -1;
-    auto sort_word = [&](const uint32_t *word, uint32_t nbits, uint32_t n, uint32_t **pp, int &cur) {
-        for (uint32_t sh = 0; sh < nbits; sh += 8) {
-            const uint32_t bits = std::min<uint32_t>(8, nbits - sh);
-            const int nxt = cur < 0 ? 0 : cur ^ 1;
-            launch_radix_pass(word, sh, bits, cur < 0 ? nullptr : pp[cur], pp[nxt], n, tmp, st);
-            cur = nxt;
-        }
-    };
-    sort_word(m.cls, 2, N, perm, pc);
-    sort_word(m.end, 32, N, perm, pc);
-    sort_word(m.start, 32, N, perm, pc);
-    sort_word(m.tid, std::max<uint32_t>(1, bitlen((uint32_t)std::max<int32_t>(1, names_from->n_ref))), N, perm, pc);
-    const uint32_t *sorted = perm[pc];
+    RadixSort by_key{{perm0, perm1}, tmp, N, st};
+    by_key.by(m.cls, 2);
+    by_key.by(m.end, 32);
+    by_key.by(m.start, 32);
+    by_key.by(m.tid, std::max<uint32_t>(1, bitlen((uint32_t)std::max<int32_t>(1, names_from->n_ref))));
+    const uint32_t *sorted = by_key.sorted();
     mark("unpack + key sort");
     launch_merge_heads(m, sorted, N, head, st);
     launch_scan_u32(head, seg, N, d_total, tmp, st);
@@ -425,17 +415,17 @@ extern "C" int rgx_table_merge_device(rgx_ctx *c, const void *d_rows, uint64_t s
     launch_fill_u32(u.te, 0u, U, st); launch_fill_u32(u.count, 0u, U, st); launch_fill_u32(u.last_shard, 0u, U, st);
     launch_merge_reduce(m, sorted, head, seg, N, u, st);
     // first-seen naming: rank by (first shard that has the key, the row's rank inside that shard)
-    int upc = -1;
-    sort_word(u.first, 32, U, uperm, upc);
-    launch_merge_rank(uperm[upc], U, name_rank, st);
+    RadixSort rows{{uperm0, uperm1}, tmp, U, st};
+    rows.by(u.first, 32);
+    launch_merge_rank(rows.sorted(), U, name_rank, st);
     // output order (junctions_extractor.h:117-140): chrom string rank, thick_start, thick_end, name
     launch_gather_u32(U, d_rank, u.tid, crank, st);
-    upc = -1;
-    sort_word(name_rank, std::max<uint32_t>(1, bitlen(U)), U, uperm, upc);
-    sort_word(u.te, 32, U, uperm, upc);
-    sort_word(u.ts, 32, U, uperm, upc);
-    sort_word(crank, std::max<uint32_t>(1, bitlen(rk)), U, uperm, upc);
-    launch_merge_table(u, uperm[upc], name_rank, U, min_anchor, (uint8_t *)packed, st);      // the packed area doubles as the table's device image
+    rows.reset();
+    rows.by(name_rank, std::max<uint32_t>(1, bitlen(U)));
+    rows.by(u.te, 32);
+    rows.by(u.ts, 32);
+    rows.by(crank, std::max<uint32_t>(1, bitlen(rk)));
+    launch_merge_table(u, rows.sorted(), name_rank, U, min_anchor, (uint8_t *)packed, st);      // the packed area doubles as the table's device image
     mark("reduce + name + order");
     rgx_junction_table *t = table_alloc(h, U, /*zero=*/false, /*pinned=*/true);
     if (!t) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result table\n"); }

@@ -42,7 +42,7 @@ int EventsRun::calibrate_arena() {
     // (one calibration at a time per DEVICE: the arenas of different devices have nothing to do with one another)
     static std::mutex trial_mu[16];
     std::lock_guard<std::mutex> trial_lock(trial_mu[(unsigned)c->device % 16u]);
-    if (!inflate_takes_coop(n_range) || h_sc[0] != 0xffffffffu) return RGX_OK;
+    if (!inflate_takes_coop(n_range) || h_sc->inflate.first_bad != 0xffffffffu) return RGX_OK;
     DevBuf &b_arena = c->buf("arena"), &b_lens = c->buf("inflate_scratch");
     if (!b_arena.p || b_arena.cap < total + 256) return RGX_OK;
     auto room_for_one = [&] {                                  // (a challenger AND what the call -- or a co-tenant of the device -- may still allocate)
@@ -50,11 +50,11 @@ int EventsRun::calibrate_arena() {
         return hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= b_arena.cap + b_arena.cap / 8 + ((size_t)16 << 30);
     };
     const int plan = inflate_plan_for(bam_len, total_all);
-    uint32_t *d_dummy = d_sc + 100;                            // (the trial launches' verdicts: not looked at -- the call's own launch gave the verdict)
+    uint32_t *d_dummy = &d_sc->trial_inflate.first_bad;         // (the trial launches' verdicts: not looked at -- the call's own launch gave the verdict)
     auto time_into = [&](uint8_t *arena_p, float &ms) -> hipError_t {
         float t[3] = {0, 0, 0};
         for (int k = 0; k < 4; ++k) {                          // (the first launch into a fresh allocation also pays for its pages: not timed)
-            hipError_t e = hipMemsetAsync(d_dummy, 0xff, 8, st);
+            hipError_t e = hipMemsetAsync(d_dummy, 0xff, sizeof d_sc->trial_inflate, st);
             if (e != hipSuccess) return e;
             if ((e = hipEventRecord(c->ev_trial[0], st)) != hipSuccess) return e;
             launch_inflate(d_bam, d_members + m_lo, n_range, arena_p, upos_lo, b_lens.as<uint32_t>(), d_dummy, st, 0, 0, false, 0, nullptr, plan);
@@ -241,17 +241,14 @@ int EventsRun::stage_upload() {
         } else HIP_TRY(hipMemcpyAsync(b.p, h_bam, bam_len, hipMemcpyHostToDevice, st));
     }
     DevBuf &b_scalars = c->buf("scalars");
-    HIP_TRY(b_scalars.ensure(512));
-    // u32 scalars: [0]=first bad member [1]=its status [2]=changed [3]=n_rec [4]=n_events [5]=n_long [6]=n_unique [8..9]=n_iterated(u64)
-    //              [12..13]=header inflate status [16]=n_cand [17]=n_members [18]=stop [20..21]=total inflated (u64)
-    //              [24..26]=q_index [32..37]=q_upos (u64 x3) [40..45]=q_coff (u64 x3)
-    d_sc = b_scalars.as<uint32_t>();
-    h_sc = (uint32_t *)c->pinned;
-    HIP_TRY(hipMemsetAsync(d_sc, 0, 512, st));
-    HIP_TRY(hipMemsetAsync(d_sc, 0xff, 4, st));
-    HIP_TRY(hipMemsetAsync(d_sc + 12, 0xff, 4, st));
-    HIP_TRY(hipMemsetAsync(d_sc + 18, 0xff, 4, st));
-    HIP_TRY(hipMemsetAsync(d_sc + kStatusEarly, 0xff, 4, st));
+    HIP_TRY(b_scalars.ensure(sizeof(Scalars)));
+    d_sc = b_scalars.as<Scalars>();
+    h_sc = (Scalars *)c->pinned;
+    HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(Scalars), st));
+    HIP_TRY(hipMemsetAsync(&d_sc->inflate.first_bad, 0xff, 4, st));
+    HIP_TRY(hipMemsetAsync(&d_sc->hdr_inflate.first_bad, 0xff, 4, st));
+    HIP_TRY(hipMemsetAsync(&d_sc->stop, 0xff, 4, st));
+    HIP_TRY(hipMemsetAsync(&d_sc->inflate_early.first_bad, 0xff, 4, st));
 
     return kGoOn;
 }
@@ -273,18 +270,18 @@ int EventsRun::stage_members() {
             c->pinned_members_cap = need + need / 4;
         }
         memcpy(c->pinned_members, hm.data(), (size_t)n_cand * sizeof(Member));
-        h_sc[17] = n_cand; memcpy(h_sc + 20, &hm_total, 8);
-        HIP_TRY(hipMemcpyAsync(d_sc + 17, h_sc + 17, 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sc + 20, h_sc + 20, 8, hipMemcpyHostToDevice, st));
+        h_sc->n_members = n_cand; h_sc->total_inflated = hm_total;
+        HIP_TRY(hipMemcpyAsync(&d_sc->n_members, &h_sc->n_members, 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(&d_sc->total_inflated, &h_sc->total_inflated, 8, hipMemcpyHostToDevice, st));
     } else {
     const uint32_t n_tiles = (uint32_t)((bam_len + kMagicTile - 1) / kMagicTile);
     HIP_TRY(b_disc.ensure((size_t)n_tiles * 4 + scan_tmp_words(n_tiles) * 4 + 256));
     uint32_t *tile_cnt = b_disc.as<uint32_t>(), *tile_tmp = tile_cnt + n_tiles;
     launch_magic_count(d_bam, bam_len, n_tiles, tile_cnt, st);
-    launch_scan_u32(tile_cnt, tile_cnt, n_tiles, d_sc + 16, tile_tmp, st);
-    HIP_TRY(hipMemcpyAsync(h_sc + 16, d_sc + 16, 4, hipMemcpyDeviceToHost, st));
+    launch_scan_u32(tile_cnt, tile_cnt, n_tiles, &d_sc->n_cand, tile_tmp, st);
+    HIP_TRY(fetch(h_sc->n_cand));
     HIP_TRY(hipStreamSynchronize(st));
-    n_cand = h_sc[16];
+    n_cand = h_sc->n_cand;
     if (n_cand == 0) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);
     DevBuf &b_cand = c->buf("cand");
     {
@@ -384,33 +381,31 @@ int EventsRun::stage_members() {
         if (overlap) {
             // the member list is on the host (scan_members_parallel): what k_member_query / k_member_stop would answer, without a round trip
             const uint32_t nm = (uint32_t)hm.size();
-            uint64_t q_up[3];
             for (int k = 0; k < 3; ++k) {
                 uint32_t lo_ = 0, hi_ = nm;
                 while (lo_ < hi_) { const uint32_t mid = lo_ + (hi_ - lo_) / 2; if (hm[mid].cpos < q[k] + 18) lo_ = mid + 1; else hi_ = mid; }
                 const bool hit = lo_ < nm && hm[lo_].cpos == q[k] + 18;
-                h_sc[24 + k] = hit ? lo_ : nm; q_up[k] = hit ? hm[lo_].upos : ~0ull;
+                h_sc->q_index[k] = hit ? lo_ : nm; h_sc->q_upos[k] = hit ? hm[lo_].upos : ~0ull;
             }
-            memcpy(h_sc + 32, q_up, sizeof q_up);
             uint32_t stop_ = 0xffffffffu;
-            for (uint32_t i = h_sc[24]; i < nm; ++i) if (hm[i].isize == 0 || hm[i].isize > kBgzfMaxBlock) { stop_ = i; break; }
-            h_sc[18] = stop_; h_sc[17] = nm; memcpy(h_sc + 20, &hm_total, 8);
+            for (uint32_t i = h_sc->q_index[0]; i < nm; ++i) if (hm[i].isize == 0 || hm[i].isize > kBgzfMaxBlock) { stop_ = i; break; }
+            h_sc->stop = stop_; h_sc->n_members = nm; h_sc->total_inflated = hm_total;
             return hipSuccess;
         }
-        memcpy(h_sc + 40, q, sizeof q);
-        hipError_t e = hipMemcpyAsync(d_sc + 40, h_sc + 40, sizeof q, hipMemcpyHostToDevice, st);
+        memcpy(h_sc->q_coff, q, sizeof q);
+        hipError_t e = hipMemcpyAsync(d_sc->q_coff, h_sc->q_coff, sizeof q, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(d_sc + 18, 0xff, 4, st);
+        e = hipMemsetAsync(&d_sc->stop, 0xff, 4, st);
         if (e != hipSuccess) return e;
-        launch_member_query(d_members, d_sc + 17, (const uint64_t *)(d_sc + 40), 3, d_sc + 24, (uint64_t *)(d_sc + 32), st);
+        launch_member_query(d_members, &d_sc->n_members, d_sc->q_coff, 3, d_sc->q_index, d_sc->q_upos, st);
         // the stream ends at the first empty (or oversized = corrupt) member at/after the first one read (bgzf.c:548-578)
-        launch_member_stop(d_members, n_cand, d_sc + 17, d_sc + 24, d_sc + 18, st);
-        e = hipMemcpyAsync(h_sc, d_sc, 256, hipMemcpyDeviceToHost, st);
+        launch_member_stop(d_members, n_cand, &d_sc->n_members, d_sc->q_index, &d_sc->stop, st);
+        e = hipMemcpyAsync(h_sc, d_sc, kScalarsQueryPart, hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) return e;
         return hipStreamSynchronize(st);
     };
     HIP_TRY(query());
-    if (overlap && seek && (seek_voff >> 16) != 0 && h_sc[24] >= h_sc[17]) {
+    if (overlap && seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
         // the index points at something that is no member of this (well-formed) file: the device's discovery decides what that means
         up.th.join();
         HIP_TRY(complete_upload());
@@ -420,13 +415,13 @@ int EventsRun::stage_members() {
         P.t_begin = t_begin;
         return rc2;
     }
-    if (seek && (seek_voff >> 16) != 0 && h_sc[24] >= h_sc[17]) {
+    if (seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
         // the seek target is no member of the chain from offset 0: something in front of it is broken.  bgzf_seek (hts_itr_next, hts.c:1935)
         // goes there regardless -- take it as a second chain root.  (Only damaged files get here.)
         chain(seek_voff >> 16);
         HIP_TRY(query());
         mark("second chain root");
-        if (h_sc[24] >= h_sc[17]) {
+        if (h_sc->q_index[0] >= h_sc->n_members) {
             // there is no BGZF member at the seek target at all (a truncated file, an index that belongs to another file): the
             // reference's read after bgzf_seek fails and the iterator returns nothing.  Keep the head of the file for the header only.
             chain(UINT64_MAX);
@@ -434,12 +429,12 @@ int EventsRun::stage_members() {
             HIP_TRY(query());
         }
     }
-    n_members_all = h_sc[17];
+    n_members_all = h_sc->n_members;
     if (n_members_all == 0) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);     // offset 0 is not a BGZF member
-    memcpy(&total_all, h_sc + 20, 8);
-    first_member = seek ? h_sc[24] : 0;                                    // == n_members_all when the seek target is no member
-    stop = std::min(h_sc[18], n_members_all);
-    memcpy(q_upos, h_sc + 32, sizeof q_upos);
+    total_all = h_sc->total_inflated;
+    first_member = seek ? h_sc->q_index[0] : 0;                                    // == n_members_all when the seek target is no member
+    stop = std::min(h_sc->stop, n_members_all);
+    memcpy(q_upos, h_sc->q_upos, sizeof q_upos);
     mark("member discovery (2 syncs)");
 
     return kGoOn;
@@ -449,11 +444,11 @@ int EventsRun::stage_range_and_inflate() {
     // -- member range of this call ---------------------------------------------------------------------------------------------
     std::vector<Member> &hm = c->hm_scratch;
     DevBuf &b_arena = c->buf("arena");
-    m_lo = cut_lo ? h_sc[25] : 0;
+    m_lo = cut_lo ? h_sc->q_index[1] : 0;
     if (m_lo <= 4) m_lo = 0;        // keep the file head (BAM header) in the same launch: a lone lane needs milliseconds per member
     m_hi = stop;                                                  // exclusive
     if (cut_hi != UINT64_MAX) {
-        const uint32_t mh = h_sc[26];
+        const uint32_t mh = h_sc->q_index[2];
         const uint32_t hi_m = (mh < n_members_all && (cut_hi & 0xffff)) ? mh + 1 : mh;
         // a region's chunks: each is a seek of its own, so an empty member between two of them ends nothing (the chunks' own limits do
         // that, below); two members more than the index asks for, for the records of a stale index that run past their chunk's end
@@ -502,8 +497,8 @@ int EventsRun::stage_range_and_inflate() {
     auto timed_launch = [&](hipStream_t q, bool piece, InflateGate gate) {      // the call's whole-range launch, with its own pair of events on its own stream
         if (c->link) { c->chip_hold.take(&c->link->chip); mark("the chip's DEFLATE turn is ours"); }
         (void)hipEventRecord(c->ev_launch[0], q);
-        launch_inflate(d_bam, d_members + m_lo, n_range, b_arena.as<uint8_t>(), upos_lo, b_lens.as<uint32_t>(), d_sc, q, ignore_below, 0, piece, 0, d_bad,
-            pairs, false, gate);
+        launch_inflate(d_bam, d_members + m_lo, n_range, b_arena.as<uint8_t>(), upos_lo, b_lens.as<uint32_t>(), &d_sc->inflate.first_bad, q,
+            ignore_below, 0, piece, 0, d_bad, pairs, false, gate);
         (void)hipEventRecord(c->ev_launch[1], q);
         if (c->link && hipLaunchHostFunc(q, [](void *h) { ((TurnHold *)h)->give(); }, &c->chip_hold) != hipSuccess) { (void)hipGetLastError();
             c->chip_hold.give(); }
@@ -591,8 +586,8 @@ int EventsRun::stage_range_and_inflate() {
             hipStream_t q = own ? st : c->side[j];
             if (!own) used_side |= 1u << j;
             HIP_TRY(hipStreamWaitEvent(q, c->chunk_ev[j], 0));
-            launch_inflate(d_bam, d_members + g_lo, g_hi - g_lo, b_arena.as<uint8_t>(), upos_lo, (uint32_t *)(b_lens.as<uint8_t>() + scratch_off), d_sc, q,
-                ignore_below, g_lo - m_lo, /*piece=*/true, 0, d_bad, pairs);
+            launch_inflate(d_bam, d_members + g_lo, g_hi - g_lo, b_arena.as<uint8_t>(), upos_lo, (uint32_t *)(b_lens.as<uint8_t>() + scratch_off),
+                &d_sc->inflate.first_bad, q, ignore_below, g_lo - m_lo, /*piece=*/true, 0, d_bad, pairs);
             scratch_off += inflate_scratch_bytes(g_hi - g_lo);
             g_lo = g_hi;
         }

@@ -38,6 +38,7 @@
 #include "worker_pool.h"
 #include <sys/stat.h>
 #include "kernels.h"
+#include "scalars.h"
 
 using namespace rgx;
 
@@ -207,6 +208,51 @@ struct DevBuf {
         p = nullptr; cap = 0; mapped = 0; piece_len.clear();
     }
     template <class T> T *as() const { return (T *)p; }
+};
+
+// Hands out a buffer's bytes array by array and remembers whether it was asked for more than the buffer holds: CARVE_TRY, behind the last array and in
+// front of the first launch, fails the call instead of letting a kernel write past the end.
+struct Carve {
+    uint8_t *at; size_t left; bool over = false;
+    explicit Carve(const DevBuf &b) : at(b.as<uint8_t>()), left(b.cap) {}
+    template <class T> T *take(size_t n) {
+        if (n > left / sizeof(T)) { over = true; n = 0; }
+        T *r = (T *)at; at += n * sizeof(T); left -= n * sizeof(T);
+        return r;
+    }
+    uint8_t *u8(size_t n) { return take<uint8_t>(n); }
+    uint32_t *u32(size_t n) { return take<uint32_t>(n); }
+    uint64_t *u64(size_t n) { return take<uint64_t>(n); }
+};
+#define CARVE_TRY(w, what) \
+    do { if ((w).over) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the %s buffer is smaller than its arrays\n", what); } while (0)
+
+// Stable LSD radix sort of n positions by several 32-bit words, least significant first, 8 bits a pass: the permutation ping-pongs between perm[0] and
+// perm[1] (the first pass of a sort starts from the identity: perm_in == nullptr).  The keyed forms gather a word through the permutation once and let
+// its passes stream (key, permutation) pairs between key[0] and key[1] instead of gathering per pass.
+struct RadixSort {
+    uint32_t *perm[2], *tmp; uint32_t n; hipStream_t st; uint32_t *key[2] = {nullptr, nullptr};
+    int cur = -1;                                          // the buffer the permutation is in (-1 = identity)
+    const uint32_t *in() const { return cur < 0 ? nullptr : perm[cur]; }
+    void passes(const uint32_t *word, uint32_t nbits, int kc) {            // kc >= 0: keyed -- the keys go to key[kc] and ping-pong from there
+        for (uint32_t sh = 0; sh < nbits; sh += 8) {
+            const uint32_t bits = std::min<uint32_t>(8, nbits - sh); const int nxt = cur < 0 ? 0 : cur ^ 1;
+            if (kc < 0) launch_radix_pass(word, sh, bits, in(), perm[nxt], n, tmp, st);
+            else { launch_radix_pass_keyed(word, key[kc], sh, bits, in(), perm[nxt], n, tmp, st); word = key[kc]; kc ^= 1; }
+            cur = nxt;
+        }
+    }
+    void by(const uint32_t *word, uint32_t nbits) { passes(word, nbits, -1); }
+    void by_keyed(const uint32_t *word, uint32_t nbits) {                 // (under the identity the word is its own key column)
+        if (cur < 0) return passes(word, nbits, 0);
+        launch_gather_u32(n, word, perm[cur], key[0], st);
+        passes(key[0], nbits, 1);
+    }
+    // (the word comes from gather(perm_in or nullptr, key_out) -- under the identity too)
+    template <class G> void by_gathered(G gather, uint32_t nbits) { gather(in(), key[0]); passes(key[0], nbits, 1); }
+    const uint32_t *sorted() const { return perm[cur]; }
+    uint32_t *spare() const { return perm[cur ^ 1]; }      // the buffer the permutation is not in: free once the sort is over
+    void reset() { cur = -1; }
 };
 
 constexpr int kSideStreams = 2;
@@ -382,7 +428,8 @@ struct EventsRun {
     bool overlap = false, gated = false;
     size_t gate_chunk = 0;
     uint64_t hm_total = 0;
-    uint32_t *d_sc = nullptr, *h_sc = nullptr;               // the call's scalars in HBM and their pinned host mirror
+    Scalars *d_sc = nullptr, *h_sc = nullptr;                // the call's scalars in HBM and their pinned host mirror (scalars.h)
+    template <class T> hipError_t fetch(T &host_member) { return fetch_scalar(d_sc, h_sc, host_member, st); }
     // before anything looks at the file through the device (the fallbacks of damaged files): the bytes a shard did not send
     hipError_t complete_upload() {
         if (!h_bam || !(up.lo || (up.hi && up.hi < bam_len))) return hipSuccess;
@@ -405,10 +452,10 @@ struct EventsRun {
         int cur = 0;
         for (uint32_t span = 1; span < n_cand; span <<= 1) { launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st); cur ^= 1; }
         launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st);
-        launch_scan_u32(c_reach, c_rank, n_cand, d_sc + 17, c_tmp, st);
+        launch_scan_u32(c_reach, c_rank, n_cand, &d_sc->n_members, c_tmp, st);
         launch_member_compact(d_bam, bam_len, cand, c_isize, c_reach, c_rank, n_cand, d_members, c_isz2, st);
-        if (d_true_sizes) launch_member_fix(d_members, c_isz2, n_cand, d_sc + 17, d_true_sizes, st);     // second run: lengths from the probe, not the footers
-        launch_member_upos(d_members, c_isz2, d_sc + 17, (uint64_t *)(d_sc + 20), st);
+        if (d_true_sizes) launch_member_fix(d_members, c_isz2, n_cand, &d_sc->n_members, d_true_sizes, st);   // second run: lengths from the probe, not the footers
+        launch_member_upos(d_members, c_isz2, &d_sc->n_members, &d_sc->total_inflated, st);
     }
     bool whole = false, seek = false, chunked = false, geom_chunked_hint = false, empty_stream = false;
     uint64_t seek_voff = 0, cut_lo = 0, cut_hi = UINT64_MAX, total_all = 0, q_upos[3] = {0, 0, 0};
@@ -461,21 +508,20 @@ struct EventsRun {
     int frame(uint32_t n_s, uint32_t walk_from, bool &ended) {
         DevBuf &b_tmp = c->buf("tmp");
         launch_seg_walk(arena, geom, n_s, n_ref, seg_start[cur], seg_exit[cur], seg_cnt[cur], seg_cp, st, walk_from);
-        // d_sc[10]: leftmost disagreeing segment, d_sc[11]: leftmost chain end, d_sc[3]: record total
         for (int iter = 0;; ++iter) {
-            HIP_TRY(hipMemsetAsync(d_sc + 10, 0xff, 8, st));
+            HIP_TRY(hipMemsetAsync(&d_sc->framing, 0xff, sizeof d_sc->framing, st));
             launch_seg_verify(arena, geom, n_s, seg_start[cur], seg_exit[cur], seg_cnt[cur], seg_start[cur ^ 1], seg_exit[cur ^ 1],
-                              seg_cnt[cur ^ 1], d_sc + 10, seg_cp, st);
+                              seg_cnt[cur ^ 1], &d_sc->framing.disagree, seg_cp, st);
             cur ^= 1;
-            launch_scan_u32(seg_cnt[cur], seg_base, n_s, d_sc + 3, b_tmp.as<uint32_t>(), st);
-            HIP_TRY(hipMemcpyAsync(h_sc + 3, d_sc + 3, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(h_sc + 10, d_sc + 10, 8, hipMemcpyDeviceToHost, st));
+            launch_scan_u32(seg_cnt[cur], seg_base, n_s, &d_sc->n_rec, b_tmp.as<uint32_t>(), st);
+            HIP_TRY(fetch(h_sc->n_rec));
+            HIP_TRY(fetch(h_sc->framing));
             if (spec && iter == 0) {
-                HIP_TRY(hipMemcpyAsync(h_sc, d_sc, 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(h_sc + kStatusEarly, d_sc + kStatusEarly, 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(fetch(h_sc->inflate));
+                HIP_TRY(fetch(h_sc->inflate_early));
             }
             HIP_TRY(hipStreamSynchronize(st));
-            if (spec && iter == 0 && (h_sc[0] != 0xffffffffu || h_sc[kStatusEarly] != 0xffffffffu)) {
+            if (spec && iter == 0 && (h_sc->inflate.first_bad != 0xffffffffu || h_sc->inflate_early.first_bad != 0xffffffffu)) {
                 // some member did not inflate to its footer's length: nothing enqueued since is worth anything
                 mark("inflate verdict: not clean, starting over device-resident");
                 if (gated) { c->gate_distrust = true; if (trace) fprintf(stderr,
@@ -489,17 +535,18 @@ struct EventsRun {
                 return rc2;
             }
             ++P.framing_sweeps;
-            if (h_sc[11] != 0xffffffffu) ended = true;           // some segment's chain ends: an unreadable / cut-off record (sam.c:421-423)
+            const Scalars::Framing &fr = h_sc->framing;
+            if (fr.chain_end != 0xffffffffu) ended = true;           // some segment's chain ends: an unreadable / cut-off record (sam.c:421-423)
             // the chain ends inside the exact prefix (or everything is exact): nothing starts after that segment -- with one chain the
             // end already spread to the right by itself; the chains of later chunks would not know
-            if (h_sc[11] != 0xffffffffu && (h_sc[11] < h_sc[10] || (h_sc[10] == 0xffffffffu && geom.chunks))) {
-                launch_seg_truncate(geom, n_s, h_sc[11], seg_start[cur], seg_exit[cur], seg_cnt[cur], st);
-                launch_scan_u32(seg_cnt[cur], seg_base, n_s, d_sc + 3, b_tmp.as<uint32_t>(), st);
-                HIP_TRY(hipMemcpyAsync(h_sc + 3, d_sc + 3, 4, hipMemcpyDeviceToHost, st));
+            if (fr.chain_end != 0xffffffffu && (fr.chain_end < fr.disagree || (fr.disagree == 0xffffffffu && geom.chunks))) {
+                launch_seg_truncate(geom, n_s, fr.chain_end, seg_start[cur], seg_exit[cur], seg_cnt[cur], st);
+                launch_scan_u32(seg_cnt[cur], seg_base, n_s, &d_sc->n_rec, b_tmp.as<uint32_t>(), st);
+                HIP_TRY(fetch(h_sc->n_rec));
                 HIP_TRY(hipStreamSynchronize(st));
                 break;
             }
-            if (h_sc[10] == 0xffffffffu) break;
+            if (fr.disagree == 0xffffffffu) break;
             if (iter > 1 << 20) return fail(err, errlen, RGX_ERR_FORMAT, "regtools_amd: record framing did not converge\n");
         }
         return -1;

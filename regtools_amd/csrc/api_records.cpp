@@ -14,17 +14,17 @@ int EventsRun::stage_footers_and_header() {
     BamHeader hdr_host;
     mean_rec = 0;                                    // mean size of the file's first records (0 = unknown: 16 KiB segments)
     spec = overlap && !d_true_sizes && !geom_chunked_hint && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hdr_host, nullptr, &mean_rec);
-    if (spec) { h_sc[0] = h_sc[1] = 0xffffffffu; h_sc[kStatusEarly] = h_sc[kStatusEarly + 1] = 0xffffffffu; }
+    if (spec) h_sc->inflate = h_sc->inflate_early = InflateStatus{0xffffffffu, 0xffffffffu};
     else {
         HIP_TRY(join_B());
-        HIP_TRY(hipMemcpyAsync(h_sc, d_sc, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_sc + kStatusEarly, d_sc + kStatusEarly, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(fetch(h_sc->inflate));
+        HIP_TRY(fetch(h_sc->inflate_early));
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (!d_true_sizes) {
-        auto size_trouble = [&](uint32_t k) { return h_sc[k] != 0xffffffffu &&
-            (h_sc[k + 1] == 12u /* INF_SIZE_MISMATCH */ || h_sc[k + 1] == 10u /* INF_OUT_OVERFLOW */); };
-        bool lies = size_trouble(0) || size_trouble(kStatusEarly);
+        auto size_trouble = [](const InflateStatus &s) { return s.first_bad != 0xffffffffu &&
+            (s.code == 12u /* INF_SIZE_MISMATCH */ || s.code == 10u /* INF_OUT_OVERFLOW */); };
+        bool lies = size_trouble(h_sc->inflate) || size_trouble(h_sc->inflate_early);
         if (!lies && stop < n_members_all) {
             Member ms; uint8_t two[2] = {0, 0};
             HIP_TRY(member_at(stop, ms));
@@ -55,7 +55,7 @@ int EventsRun::stage_footers_and_header() {
     //    the file is inflated into its own small arena -----------------------------------------------------------------------
     if (spec) hdr = hdr_host;
     else {
-        const uint32_t h_early = h_sc[kStatusEarly];            // read back right after the launch finished (below the footer check)
+        const uint32_t h_early = h_sc->inflate_early.first_bad;           // read back right after the launch finished (below the footer check)
         uint32_t n_h = std::min<uint32_t>(n_members_all, 4);
         for (;;) {
             const uint8_t *src; uint64_t have;
@@ -70,15 +70,15 @@ int EventsRun::stage_footers_and_header() {
             if (m_lo == 0 && used <= n_range) src = b_arena.as<uint8_t>();
             else {
                 HIP_TRY(b_hdr.ensure(have + 256));
-                HIP_TRY(hipMemsetAsync(d_sc + 12, 0xff, 4, st));
-                launch_inflate(d_bam, d_members, used, b_hdr.as<uint8_t>(), 0, b_lens.as<uint32_t>(), d_sc + 12, st);
+                HIP_TRY(hipMemsetAsync(&d_sc->hdr_inflate.first_bad, 0xff, 4, st));
+                launch_inflate(d_bam, d_members, used, b_hdr.as<uint8_t>(), 0, b_lens.as<uint32_t>(), &d_sc->hdr_inflate.first_bad, st);
                 src = b_hdr.as<uint8_t>();
             }
             std::vector<uint8_t> hbuf(have);
             HIP_TRY(hipMemcpyAsync(hbuf.data(), src, have, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(h_sc, d_sc, 64, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_sc, d_sc, kScalarsHeaderPart, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            bad_h = (src == b_arena.as<uint8_t>()) ? std::min(h_sc[0], h_early) : h_sc[12];     // (members in front of a seek target report apart)
+            bad_h = (src == b_arena.as<uint8_t>()) ? std::min(h_sc->inflate.first_bad, h_early) : h_sc->hdr_inflate.first_bad;  // (a seek's front apart)
             if (bad_h != 0xffffffffu && bad_h < used) have = hmem[bad_h].upos;          // a corrupt member ends the header read
             uint64_t need = 0;
             int r = parse_bam_header(hbuf.data(), have, hdr, need);
@@ -108,42 +108,42 @@ int EventsRun::stage_footers_and_header() {
 int EventsRun::stage_bounds_and_chains() {
     // -- stream bounds inside the arena -------------------------------------------------------------------------------------
     lim = total;
-    if (h_sc[0] != 0xffffffffu) {       // a member of the range failed to inflate: the stream ends where it starts
+    if (h_sc->inflate.first_bad != 0xffffffffu) {       // a member of the range failed to inflate: the stream ends where it starts
         uint64_t u = 0;
-        HIP_TRY(upos_of(m_lo + h_sc[0], u));
+        HIP_TRY(upos_of(m_lo + h_sc->inflate.first_bad, u));
         lim = u - upos_lo;
     }
     auto arena_of = [&](uint64_t voff, uint32_t idx, uint64_t upos) -> uint64_t {   // virtual offset -> arena offset (idx/upos from the query)
         if (idx >= n_members_all || idx < m_lo || idx >= m_hi) return total;
         return std::min<uint64_t>(total, upos - upos_lo + (voff & 0xffff));
     };
-    if (cut_lo) pos0 = arena_of(cut_lo, h_sc[25], q_upos[1]);
+    if (cut_lo) pos0 = arena_of(cut_lo, h_sc->q_index[1], q_upos[1]);
     else pos0 = hdr.end;                 // no seek: records start right after the header (range starts at member 0)
     // Did the stream stop for a reason that ends iteration upstream, rather than at this shard's upper cut?  (A later shard is a seek past
     // that point; the merge drops the shards behind one that ended, so that a damaged file gives the same table whatever the shard count.)
     chain_ended = false;
     P.stream_ended = empty_stream;
     if (cut_hi != UINT64_MAX) {
-        const uint64_t cut_lim = arena_of(cut_hi, h_sc[26], q_upos[2]);
-        const uint32_t mh = h_sc[26];
+        const uint64_t cut_lim = arena_of(cut_hi, h_sc->q_index[2], q_upos[2]);
+        const uint32_t mh = h_sc->q_index[2];
         const uint32_t hi_wanted = (mh < n_members_all && (cut_hi & 0xffff)) ? mh + 1 : mh;
         // (a region's chunks are seeks of their own: what lies between two of them ends nothing, and a chunk whose reader does run into such a
         //  member reports it through its chain, below)
-        if (!chunked && h_sc[0] != 0xffffffffu && lim < cut_lim) P.stream_ended = true;        // a member in front of the cut does not inflate
+        if (!chunked && h_sc->inflate.first_bad != 0xffffffffu && lim < cut_lim) P.stream_ended = true;        // a member in front of the cut does not inflate
         // an empty / unusable member in front of the cut (bgzf.c:548-578)
         if (!chunked && stop < std::min(hi_wanted, n_members_all)) P.stream_ended = true;
         lim = std::min(lim, cut_lim);
-    } else if (h_sc[0] != 0xffffffffu) P.stream_ended = true;
+    } else if (h_sc->inflate.first_bad != 0xffffffffu) P.stream_ended = true;
     if (pos0 > lim) pos0 = lim;
     if (empty_stream) lim = pos0;            // the seek target does not exist: no record is read
 
     memset(&cfg, 0, sizeof cfg);
     cfg.n_ref = n_ref; cfg.strandness = p->strandness; cfg.tag0 = (uint8_t)p->strand_tag[0]; cfg.tag1 = (uint8_t)p->strand_tag[1];
     // (`junctions extract` only: identify's per-window extractions upstream meet such a read only inside a window -- DESIGN 8)
-    if ((p->strandness == 0 || p->barcodes) && !want_read_span) { cfg.abort_out = d_sc + 96; HIP_TRY(hipMemsetAsync(d_sc + 96, 0xff, 4, st)); }
+    if ((p->strandness == 0 || p->barcodes) && !want_read_span) { cfg.abort_out = &d_sc->abort_row; HIP_TRY(hipMemsetAsync(&d_sc->abort_row, 0xff, 4, st)); }
     if (p->barcodes && !want_read_span) { cfg.bc0 = (uint8_t)p->barcode_tag[0]; cfg.bc1 = (uint8_t)p->barcode_tag[1]; }
     // (identify: the same reads counted and marked; which of them a window reads is known when the windows are, cse_api.cpp)
-    if (p->strandness == 0 && want_read_span) { cfg.odd_count = d_sc + 97; HIP_TRY(hipMemsetAsync(d_sc + 97, 0, 4, st)); }
+    if (p->strandness == 0 && want_read_span) { cfg.odd_count = &d_sc->odd_aux; HIP_TRY(hipMemsetAsync(&d_sc->odd_aux, 0, 4, st)); }
     P.odd_aux.clear();
     cfg.min_anchor = p->min_anchor; cfg.min_intron = p->min_intron; cfg.max_intron = p->max_intron;
     cfg.region_tid = -2; cfg.long_threshold = 16;
@@ -184,7 +184,7 @@ int EventsRun::stage_bounds_and_chains() {
         DevBuf &bt = c->buf("fasta_tab");
         HIP_TRY(bt.ensure(tab.size() * sizeof(FaContig) + 64));
         HIP_TRY(hipMemcpy(bt.p, tab.data(), tab.size() * sizeof(FaContig), hipMemcpyHostToDevice));
-        cfg.fa_data = c->buf("fasta").as<uint8_t>(); cfg.fa_tab = bt.as<FaContig>(); cfg.fa_missing = d_sc + 64;
+        cfg.fa_data = c->buf("fasta").as<uint8_t>(); cfg.fa_tab = bt.as<FaContig>(); cfg.fa_missing = &d_sc->fa_missing;
     }
 
     // -- region queries: one record chain per chunk of the iterator -----------------------------------------------------------------
@@ -296,25 +296,25 @@ int EventsRun::stage_framing() {
             uint32_t sJ = (uint32_t)std::min<uint64_t>(n_seg, (ep.upos - kBgzfMaxBlock - pos0) / seg_bytes);
             if (small_ok ? (sJ < sA + 2 || n_seg - sJ < 1) : (sJ < sA + 1024 || n_seg - sJ < 64)) continue;
             // the stream waits until every wave of parts 0..j has finished (the counters of the parts are waited for in turn)
-            HIP_TRY(hipMemsetAsync(d_sc + 83, 0, 4, st));
+            HIP_TRY(hipMemsetAsync(&d_sc->wait_timed_out, 0, 4, st));
             for (size_t i = 0; i <= j; ++i) {
                 const uint32_t w_end = early_parts[i].waves, w_beg = i ? early_parts[i - 1].waves : 0u;
-                if (w_end > waves_done) { launch_wait_done(c->buf("gate_done").as<uint32_t>() + i, w_end - w_beg, d_sc + 83, st); waves_done = w_end; }
+                if (w_end > waves_done) { launch_wait_done(c->buf("gate_done").as<uint32_t>() + i, w_end - w_beg, &d_sc->wait_timed_out, st); waves_done = w_end; }
             }
-            HIP_TRY(hipMemcpyAsync(h_sc + 83, d_sc + 83, 4, hipMemcpyDeviceToHost, st));      // (read behind the framing's first wait for the stream)
+            HIP_TRY(fetch(h_sc->wait_timed_out));      // (read behind the framing's first wait for the stream)
             if (trace) fprintf(stderr, "[rgx trace] early tail: part %zu: members < %u, segments [%u, %u) of %u\n", j, ep.members, sA, sJ, n_seg);
             bool ended_J = false;
             const uint32_t sweeps0 = P.framing_sweeps;
             const int rcJ = frame(sJ, sA, ended_J);
             if (rcJ != -1) return rcJ;
-            const uint32_t n_rec_J = h_sc[3];
+            const uint32_t n_rec_J = h_sc->n_rec;
             // Where the last record that STARTS in the prefix ends = the verified chain's exit from its last segment.  The margin between the prefix
             // and the part of the arena still being inflated is one member; a record that reaches past it (a CIGAR of tens of thousands of
             // operations, a read of tens of kilobases) would be decoded from bytes that may not be there yet: such a file takes the one-pass order.
             uint64_t exit_J = 0;
-            HIP_TRY(hipMemcpyAsync(h_sc + 92, seg_exit[cur] + (sJ - 1), 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&h_sc->exit_staging, seg_exit[cur] + (sJ - 1), 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            memcpy(&exit_J, h_sc + 92, 8);
+            exit_J = h_sc->exit_staging;
             const bool reaches_J = exit_J > ep.upos;
             if (reaches_J && trace) fprintf(stderr,
                 "[rgx trace] early tail: a record of the prefix ends at %llu, behind the inflated part (%llu): one pass\n", (unsigned long long)exit_J,
@@ -322,16 +322,16 @@ int EventsRun::stage_framing() {
             const bool slow_J = P.framing_sweeps - sweeps0 > 2;
             P.framing_sweeps = sweeps0;                               // (the sweeps over everything, below, are the call's count)
             const uint64_t span_J = (uint64_t)sJ * seg_bytes;
-            if (h_sc[83]) { c->early_distrust = true; if (trace) fprintf(stderr,
+            if (h_sc->wait_timed_out) { c->early_distrust = true; if (trace) fprintf(stderr,
                 "[rgx trace] early tail: a wait for a part's waves timed out, this context no longer uses it\n"); }
-            if (h_sc[83] || ended_J || slow_J || reaches_J || !n_rec_J || span_J / n_rec_J > kSparseRecordBytes ||
+            if (h_sc->wait_timed_out || ended_J || slow_J || reaches_J || !n_rec_J || span_J / n_rec_J > kSparseRecordBytes ||
                 // not the plain case: one pass over everything below
                 (sA && n_rec_J > soa_cap)) { early = false; sA = 0; emit_parts_ok = false; emit_parts = 0; emit_rows = 0; break; }
             if (!sA) {
                 // rows for the whole file, estimated from the first part (+ 1/8); when the estimate turns out short the decode is simply made again below
                 HIP_TRY(soa_layout((size_t)((double)n_rec_J * ((double)n_seg / sJ) * 1.125) + 65536));
                 cfg.insane_out = nullptr;
-                if (lite_walk) { cfg.insane_out = d_sc + 82; HIP_TRY(hipMemsetAsync(d_sc + 82, 0, 4, st)); h_sc[82] = 0; }
+                if (lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
             }
             launch_decode_seg(arena, geom, sJ, seg_start[cur], seg_base, seg_cnt[cur], cfg, soa, seg_iter_e, seg_long_e, seg_cp, /*staged=*/true, st, sA);
             // ... and its junction events emitted, into the events block the context's last call left (no count is known yet, so nothing can be
@@ -345,8 +345,8 @@ int EventsRun::stage_framing() {
                     ev_e = ev_layout(b_ev0.as<uint8_t>(), ev_lay); }
             }
             if (emit_parts_ok && emit_parts < kGateParts - 1) {
-                launch_scan_u32(soa.n_ev + emit_rows, ev_base + emit_rows, n_rec_J - emit_rows, d_sc + 84 + emit_parts, b_tmp.as<uint32_t>(), st);
-                launch_emit_short(arena, n_rec_J, cfg, soa, ev_base, ev_e, st, emit_rows, d_sc + 84, emit_parts, (uint32_t)std::min<size_t>(ev_lay,
+                launch_scan_u32(soa.n_ev + emit_rows, ev_base + emit_rows, n_rec_J - emit_rows, d_sc->part_events + emit_parts, b_tmp.as<uint32_t>(), st);
+                launch_emit_short(arena, n_rec_J, cfg, soa, ev_base, ev_e, st, emit_rows, d_sc->part_events, emit_parts, (uint32_t)std::min<size_t>(ev_lay,
                     0xffffffffu));
                 emit_rows = n_rec_J; ++emit_parts;
             }
@@ -356,13 +356,13 @@ int EventsRun::stage_framing() {
         HIP_TRY(join_B());
         const int rcF = frame(n_seg, sA, chain_ended);
         if (rcF != -1) return rcF;
-        n_rec = h_sc[3];
+        n_rec = h_sc->n_rec;
     } else HIP_TRY(join_B());
     if (spec && !n_seg) {                                     // (no framing, no sync yet: the inflate's verdict is still due)
-        HIP_TRY(hipMemcpyAsync(h_sc, d_sc, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_sc + kStatusEarly, d_sc + kStatusEarly, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(fetch(h_sc->inflate));
+        HIP_TRY(fetch(h_sc->inflate_early));
         HIP_TRY(hipStreamSynchronize(st));
-        if (h_sc[0] != 0xffffffffu || h_sc[kStatusEarly] != 0xffffffffu) {
+        if (h_sc->inflate.first_bad != 0xffffffffu || h_sc->inflate_early.first_bad != 0xffffffffu) {
             HIP_TRY(complete_upload());
             HIP_TRY(hipStreamSynchronize(copy_q));
             const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, nullptr, false, region_to_file_end);
@@ -406,32 +406,33 @@ int EventsRun::stage_decode() {
         // first record that ends the iteration and the last one that passed the overlap test; when one of those lies behind the other
         // (records out of order -- no indexer writes such a file) the pass is repeated with the stop in place
         if (geom.chunks) {
-            cfg.stop_out = d_sc + 80; cfg.stop_index = 0xffffffffu;
-            HIP_TRY(hipMemsetAsync(d_sc + 80, 0xff, 4, st));
-            HIP_TRY(hipMemsetAsync(d_sc + 81, 0, 4, st));
+            cfg.stop_out = &d_sc->stop_rule.index; cfg.stop_index = 0xffffffffu;
+            HIP_TRY(hipMemsetAsync(&d_sc->stop_rule.index, 0xff, 4, st));
+            HIP_TRY(hipMemsetAsync(&d_sc->stop_rule.last_pass, 0, 4, st));
         }
         if (!s_from) {
             cfg.insane_out = nullptr;
-            if (lite_walk) { cfg.insane_out = d_sc + 82; HIP_TRY(hipMemsetAsync(d_sc + 82, 0, 4, st)); h_sc[82] = 0; }
+            if (lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
         }
         for (int pass = 0; pass < 2; ++pass) {
             launch_decode_seg(arena, geom, n_seg, seg_start[cur], seg_base, seg_cnt[cur], cfg, soa, seg_iter, seg_long, seg_cp,
                               /*staged=*/span / n_rec <= kSparseRecordBytes, st, s_from);
             if (emit_parts_ok && s_from) {
                 // the last part's events, emitted like the others'; the event total = the parts' totals
-                launch_scan_u32(soa.n_ev + emit_rows, ev_base + emit_rows, n_rec - emit_rows, d_sc + 84 + emit_parts, b_tmp.as<uint32_t>(), st);
-                launch_emit_short(arena, n_rec, cfg, soa, ev_base, ev_e, st, emit_rows, d_sc + 84, emit_parts, (uint32_t)std::min<size_t>(ev_lay, 0xffffffffu));
-                HIP_TRY(hipMemcpyAsync(h_sc + 84, d_sc + 84, 4 * kGateParts, hipMemcpyDeviceToHost, st));
-            } else launch_scan_u32(soa.n_ev, ev_base, n_rec, d_sc + 4, b_tmp.as<uint32_t>(), st);
-            launch_scan_u32(seg_iter, seg_iter, n_seg, d_sc + 8, b_tmp.as<uint32_t>(), st);
-            launch_scan_u32(seg_long, seg_long_base, n_seg, d_sc + 5, b_tmp.as<uint32_t>(), st);
-            HIP_TRY(hipMemcpyAsync(h_sc + 4, d_sc + 4, 24, hipMemcpyDeviceToHost, st));
-            if (cfg.stop_out) HIP_TRY(hipMemcpyAsync(h_sc + 80, d_sc + 80, 8, hipMemcpyDeviceToHost, st));
-            if (cfg.insane_out) HIP_TRY(hipMemcpyAsync(h_sc + 82, d_sc + 82, 4, hipMemcpyDeviceToHost, st));
-            if (cfg.abort_out) HIP_TRY(hipMemcpyAsync(h_sc + 96, d_sc + 96, 4, hipMemcpyDeviceToHost, st));
-            if (cfg.odd_count) HIP_TRY(hipMemcpyAsync(h_sc + 97, d_sc + 97, 4, hipMemcpyDeviceToHost, st));
+                launch_scan_u32(soa.n_ev + emit_rows, ev_base + emit_rows, n_rec - emit_rows, d_sc->part_events + emit_parts, b_tmp.as<uint32_t>(), st);
+                launch_emit_short(arena, n_rec, cfg, soa, ev_base, ev_e, st, emit_rows, d_sc->part_events, emit_parts,
+                    (uint32_t)std::min<size_t>(ev_lay, 0xffffffffu));
+                HIP_TRY(fetch(h_sc->part_events));
+            } else launch_scan_u32(soa.n_ev, ev_base, n_rec, &d_sc->counts.n_events, b_tmp.as<uint32_t>(), st);
+            launch_scan_u32(seg_iter, seg_iter, n_seg, &d_sc->counts.n_iterated, b_tmp.as<uint32_t>(), st);
+            launch_scan_u32(seg_long, seg_long_base, n_seg, &d_sc->counts.n_long, b_tmp.as<uint32_t>(), st);
+            HIP_TRY(fetch(h_sc->counts));
+            if (cfg.stop_out) HIP_TRY(fetch(h_sc->stop_rule));
+            if (cfg.insane_out) HIP_TRY(fetch(h_sc->insane));
+            if (cfg.abort_out) HIP_TRY(fetch(h_sc->abort_row));
+            if (cfg.odd_count) HIP_TRY(fetch(h_sc->odd_aux));
             HIP_TRY(hipStreamSynchronize(st));
-            if (cfg.insane_out && h_sc[82]) {
+            if (cfg.insane_out && h_sc->insane) {
                 // a record the reference's reader would not have accepted (sam.c:421-423) lies on the chain the block_size walk followed:
                 // the whole call again with the framing making the full test (damaged files only)
                 mark("decode: a record fails bam_read1's test, starting over with the full walk");
@@ -443,44 +444,44 @@ int EventsRun::stage_decode() {
                 P.t_begin = t_begin;
                 return rc2;
             }
-            if (pass || !cfg.stop_out || h_sc[80] == 0xffffffffu || h_sc[81] <= h_sc[80] + 1) break;
-            cfg.stop_index = h_sc[80];
+            if (pass || !cfg.stop_out || h_sc->stop_rule.index == 0xffffffffu || h_sc->stop_rule.last_pass <= h_sc->stop_rule.index + 1) break;
+            cfg.stop_index = h_sc->stop_rule.index;
         }
         // an iterated read (in front of the record that ends the iteration) whose strand tag upstream cannot get at
-        if (cfg.abort_out && h_sc[96] != 0xffffffffu && h_sc[96] < (cfg.stop_out ? cfg.stop_index : 0xffffffffu))
+        if (cfg.abort_out && h_sc->abort_row != 0xffffffffu && h_sc->abort_row < (cfg.stop_out ? cfg.stop_index : 0xffffffffu))
             return fail(err, errlen, RGX_ERR_ABORT,
                 "regtools_amd: record %u has an auxiliary field of unknown type in front of its strand or barcode tag: the reference abort()s here\n",
-                h_sc[96]);
-        n_events = h_sc[4]; n_long = h_sc[5];
+                h_sc->abort_row);
+        n_events = h_sc->counts.n_events; n_long = h_sc->counts.n_long;
         if (emit_parts_ok && s_from) {
             uint64_t tot = 0;
-            for (uint32_t k = 0; k <= emit_parts && k < kGateParts; ++k) tot += h_sc[84 + k];
+            for (uint32_t k = 0; k <= emit_parts && k < kGateParts; ++k) tot += h_sc->part_events[k];
             if (tot > ev_lay || tot > 0xffffffffull || n_long) {
                 // the recycled block was too small after all (or wave-per-read rows want their global slots): everything once more, the plain way
                 emit_parts_ok = false;
-                launch_scan_u32(soa.n_ev, ev_base, n_rec, d_sc + 4, b_tmp.as<uint32_t>(), st);
-                HIP_TRY(hipMemcpyAsync(h_sc + 4, d_sc + 4, 4, hipMemcpyDeviceToHost, st));
+                launch_scan_u32(soa.n_ev, ev_base, n_rec, &d_sc->counts.n_events, b_tmp.as<uint32_t>(), st);
+                HIP_TRY(fetch(h_sc->counts.n_events));
                 HIP_TRY(hipStreamSynchronize(st));
-                n_events = h_sc[4];
+                n_events = h_sc->counts.n_events;
             } else n_events = (uint32_t)tot;
         }
-        n_iterated = h_sc[8];
-        if (cfg.odd_count && h_sc[97]) {
+        n_iterated = h_sc->counts.n_iterated;
+        if (cfg.odd_count && h_sc->odd_aux) {
             // damaged files only: the marked rows' (tid, pos, end) come to the host; what was counted (a second decode pass counts again) bounds the list
-            const uint32_t cap = h_sc[97];
+            const uint32_t cap = h_sc->odd_aux;
             DevBuf &b_odd = c->buf("odd_aux");
             HIP_TRY(b_odd.ensure((size_t)cap * 12 + 16));
-            HIP_TRY(hipMemsetAsync(d_sc + 97, 0, 4, st));
-            launch_collect_odd_aux(arena, soa, n_rec, cap, d_sc + 97, b_odd.as<int32_t>(), st);
-            HIP_TRY(hipMemcpyAsync(h_sc + 97, d_sc + 97, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemsetAsync(&d_sc->odd_aux, 0, 4, st));
+            launch_collect_odd_aux(arena, soa, n_rec, cap, &d_sc->odd_aux, b_odd.as<int32_t>(), st);
+            HIP_TRY(fetch(h_sc->odd_aux));
             HIP_TRY(hipStreamSynchronize(st));
-            const uint32_t n_odd = std::min(h_sc[97], cap);
+            const uint32_t n_odd = std::min(h_sc->odd_aux, cap);
             std::vector<int32_t> rows((size_t)n_odd * 3);
             if (n_odd) { HIP_TRY(hipMemcpyAsync(rows.data(), b_odd.p, (size_t)n_odd * 12, hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); }
             for (uint32_t k = 0; k < n_odd; ++k) P.odd_aux.push_back(Prep::OddAux{rows[3 * (size_t)k], rows[3 * (size_t)k + 1], rows[3 * (size_t)k + 2]});
         }
         // this shard read the record that ends the iteration (hts.c:1946-1950)
-        if (geom.chunks && p->n_shards > 1 && h_sc[80] != 0xffffffffu) P.stream_ended = true;
+        if (geom.chunks && p->n_shards > 1 && h_sc->stop_rule.index != 0xffffffffu) P.stream_ended = true;
         if (n_long) launch_long_fill(n_seg, seg_base, seg_cnt[cur], seg_long_base, cfg, soa, long_list, st);
     }
     HIP_TRY(hipEventRecord(c->ev[4], st));
@@ -503,11 +504,11 @@ int EventsRun::stage_emit() {
             launch_emit_long(arena, long_list, n_long, cfg, soa, ev_base, ev, st);
         }
         if (cfg.fa_data) {
-            HIP_TRY(hipMemcpyAsync(h_sc + 64, d_sc + 64, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(fetch(h_sc->fa_missing));
             HIP_TRY(hipStreamSynchronize(st));
             // cc:553
-            if (h_sc[64]) return fail(err, errlen, RGX_ERR_FASTA, "Unable to extract FASTA sequence for position %s\n\n",
-                hdr.names[(size_t)(h_sc[64] - 1)].c_str());
+            if (h_sc->fa_missing) return fail(err, errlen, RGX_ERR_FASTA, "Unable to extract FASTA sequence for position %s\n\n",
+                hdr.names[(size_t)(h_sc->fa_missing - 1)].c_str());
         }
     }
     HIP_TRY(hipEventRecord(c->ev[5], st));

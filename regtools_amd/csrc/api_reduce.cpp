@@ -5,14 +5,12 @@
 int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bits, uint32_t ilen_bits, const uint32_t *rank_of_group_host,
                          uint32_t n_groups, HostRows &R, char *err, size_t errlen, bool view_only, RowMap *row_map, TableSink *sink, bool allow_preagg) {
     hipStream_t st = c->stream;
-    uint32_t *d_sc = c->buf("scalars").as<uint32_t>();
-    uint32_t *h_sc = (uint32_t *)c->pinned;
+    Scalars *d_sc = c->buf("scalars").as<Scalars>(), *h_sc = (Scalars *)c->pinned;
     DevBuf &b_sort = c->buf("sort"), &b_uni = c->buf("unique");
     c->last_rows_valid = false;            // the "rows_out" block is about to be overwritten
     uint32_t n_unique = 0;
     UniqueSoA u; memset(&u, 0, sizeof u);
-    uint32_t *perm[2] = {nullptr, nullptr};
-    uint32_t *final_perm = nullptr;
+    const uint32_t *final_perm = nullptr;
     uint32_t *chrom_rank_rows = nullptr;
     R = HostRows();
     if (n_events) {
@@ -27,60 +25,44 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
             DevBuf &b_par = c->buf("partials");
             const size_t Ev = n_events;
             HIP_TRY(b_par.ensure(Ev * 4 * 9 + scan_tmp_words(n_events) * 4 + 512));
-            uint32_t *q = b_par.as<uint32_t>();
-            pr.tid = q; q += Ev; pr.start = q; q += Ev; pr.ilen_cls = q; q += Ev; pr.ts = q; q += Ev; pr.te = q; q += Ev;
-            pr.count = q; q += Ev; pr.first = q; q += Ev; pr.last = q; q += Ev; ev_flag = q;
-            HIP_TRY(hipMemsetAsync(d_sc + 7, 0, 4, st));
-            launch_preagg(ev, n_events, pr, d_sc + 7, st);
-            HIP_TRY(hipMemcpyAsync(h_sc + 7, d_sc + 7, 4, hipMemcpyDeviceToHost, st));
+            Carve q(b_par);
+            pr.tid = q.u32(Ev); pr.start = q.u32(Ev); pr.ilen_cls = q.u32(Ev); pr.ts = q.u32(Ev); pr.te = q.u32(Ev);
+            pr.count = q.u32(Ev); pr.first = q.u32(Ev); pr.last = q.u32(Ev); ev_flag = q.u32(Ev + scan_tmp_words(n_events)); CARVE_TRY(q, "partials");
+            HIP_TRY(hipMemsetAsync(&d_sc->counts.n_partial, 0, 4, st));
+            launch_preagg(ev, n_events, pr, &d_sc->counts.n_partial, st);
+            HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->counts.n_partial, st));
             HIP_TRY(hipStreamSynchronize(st));
-            n_s = h_sc[7];
+            n_s = h_sc->counts.n_partial;
             memset(&sev, 0, sizeof sev);
             sev.tid = pr.tid; sev.start = pr.start; sev.ilen_cls = pr.ilen_cls; sev.ts = pr.ts; sev.te = pr.te;
         }
         const size_t E = n_s;
         const size_t rtmp = radix_tmp_words(n_s) + scan_tmp_words(n_s) + 64;
         HIP_TRY(b_sort.ensure(E * 4 * 6 + rtmp * 4 + 256));
-        uint32_t *q = b_sort.as<uint32_t>();
-        perm[0] = q; q += E; perm[1] = q; q += E;
-        uint32_t *key[2]; key[0] = q; q += E; key[1] = q; q += E;    // the word being sorted on, carried along with the permutation
-        uint32_t *head = q; q += E; uint32_t *seg_excl = q; q += E;
-        uint32_t *tmp = q;
-        int pc = -1;  // current permutation buffer (-1 = identity)
-        // each word is gathered through the current permutation ONCE, then its 8-bit passes stream (key, permutation) pairs: with
-        // 10^8 events the per-pass gathers of the plain form miss every cache (29 -> 12 ms on the long-read workload)
-        auto sort_word = [&](const uint32_t *word, uint32_t nbits) {
-            const uint32_t *kin = word;
-            int kc = 0;
-            if (pc >= 0) { launch_gather_u32(n_s, word, perm[pc], key[0], st); kin = key[0]; kc = 1; }
-            for (uint32_t sh = 0; sh < nbits; sh += 8) {
-                const uint32_t bits = std::min<uint32_t>(8, nbits - sh);
-                const int nxt = pc < 0 ? 0 : pc ^ 1;
-                launch_radix_pass_keyed(kin, key[kc], sh, bits, pc < 0 ? nullptr : perm[pc], perm[nxt], n_s, tmp, st);
-                kin = key[kc]; kc ^= 1;
-                pc = nxt;
-            }
-        };
-        sort_word(sev.ilen_cls, ilen_bits);
-        sort_word(sev.start, 32);
-        sort_word(sev.tid, group_bits);
-        const uint32_t *sorted = perm[pc];
+        Carve q(b_sort);
+        uint32_t *perm0 = q.u32(E), *perm1 = q.u32(E), *key0 = q.u32(E), *key1 = q.u32(E);     // key: the word being sorted on, carried along
+        uint32_t *head = q.u32(E), *seg_excl = q.u32(E), *tmp = q.u32(rtmp); CARVE_TRY(q, "sort");
+        // the keyed form: with 10^8 events the per-pass gathers of the plain form miss every cache (29 -> 12 ms on the long-read workload)
+        RadixSort by_key{{perm0, perm1}, tmp, n_s, st, {key0, key1}};
+        by_key.by_keyed(sev.ilen_cls, ilen_bits);
+        by_key.by_keyed(sev.start, 32);
+        by_key.by_keyed(sev.tid, group_bits);
+        const uint32_t *sorted = by_key.sorted();
         launch_heads(sev, sorted, n_s, head, st);
-        launch_scan_u32(head, seg_excl, n_s, d_sc + 6, tmp, st);
-        HIP_TRY(hipMemcpyAsync(h_sc + 6, d_sc + 6, 4, hipMemcpyDeviceToHost, st));
+        launch_scan_u32(head, seg_excl, n_s, &d_sc->counts.n_unique, tmp, st);
+        HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->counts.n_unique, st));
         HIP_TRY(hipStreamSynchronize(st));
-        n_unique = h_sc[6];
+        n_unique = h_sc->counts.n_unique;
 
         const size_t U = n_unique;
         const size_t utmp = radix_tmp_words(n_unique) + 64;
         HIP_TRY(b_uni.ensure(U * 4 * 13 + U + utmp * 4 + 256));
-        uint32_t *w = b_uni.as<uint32_t>();
-        u.tid = w; w += U; u.start = w; w += U; u.end = w; w += U; u.ts_min = w; w += U; u.te_max = w; w += U; u.count = w; w += U;
-        u.first_seen = w; w += U; u.last_seen = w; w += U; u.name_rank = w; w += U;
-        uint32_t *head_pos = w; w += U; chrom_rank_rows = w; w += U;
-        uint32_t *uperm[2]; uperm[0] = w; w += U; uperm[1] = w; w += U;
-        uint32_t *utmp_p = w; w += utmp;
-        u.strand = (uint8_t *)w;
+        Carve w(b_uni);
+        u.tid = w.u32(U); u.start = w.u32(U); u.end = w.u32(U); u.ts_min = w.u32(U); u.te_max = w.u32(U); u.count = w.u32(U);
+        u.first_seen = w.u32(U); u.last_seen = w.u32(U); u.name_rank = w.u32(U);
+        uint32_t *head_pos = w.u32(U); chrom_rank_rows = w.u32(U);
+        uint32_t *uperm0 = w.u32(U), *uperm1 = w.u32(U), *utmp_p = w.u32(utmp);
+        u.strand = w.u8(U); CARVE_TRY(w, "unique");
         launch_fill_u32(u.ts_min, 0xffffffffu, U, st);
         launch_fill_u32(u.te_max, 0u, U, st);
         if (preagg) {
@@ -98,7 +80,8 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
             if (row_map) {
                 DevBuf &b_map = c->buf("row_map");
                 HIP_TRY(b_map.ensure((E + U) * 4 + 256));
-                row_map->ev_urow = b_map.as<uint32_t>(); row_map->urow_pos = row_map->ev_urow + E;
+                Carve wm(b_map);
+                row_map->ev_urow = wm.u32(E); row_map->urow_pos = wm.u32(U); CARVE_TRY(wm, "row_map");
                 launch_event_urow(sorted, head, seg_excl, n_events, row_map->ev_urow, st);
             }
             // first-seen naming (junctions_extractor.cc:152-157): rank of the key's first event among all keys
@@ -118,20 +101,12 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
         c->rank_stage.assign(rank_of_group_host, rank_of_group_host + n_groups);
         HIP_TRY(hipMemcpyAsync(b_rank.p, c->rank_stage.data(), (size_t)n_groups * 4, hipMemcpyHostToDevice, st));
         launch_gather_u32(n_unique, b_rank.as<uint32_t>(), u.tid, chrom_rank_rows, st);
-        int upc = -1;
-        auto usort = [&](const uint32_t *word, uint32_t nbits) {
-            for (uint32_t sh = 0; sh < nbits; sh += 8) {
-                const uint32_t bits = std::min<uint32_t>(8, nbits - sh);
-                const int nxt = upc < 0 ? 0 : upc ^ 1;
-                launch_radix_pass(word, sh, bits, upc < 0 ? nullptr : uperm[upc], uperm[nxt], n_unique, utmp_p, st);
-                upc = nxt;
-            }
-        };
-        usort(u.name_rank, std::max<uint32_t>(1, bitlen(n_unique)));
-        usort(u.te_max, 32);
-        usort(u.ts_min, 32);
-        usort(chrom_rank_rows, std::max<uint32_t>(1, bitlen(rk)));
-        final_perm = uperm[upc];
+        RadixSort order{{uperm0, uperm1}, utmp_p, n_unique, st};
+        order.by(u.name_rank, std::max<uint32_t>(1, bitlen(n_unique)));
+        order.by(u.te_max, 32);
+        order.by(u.ts_min, 32);
+        order.by(chrom_rank_rows, std::max<uint32_t>(1, bitlen(rk)));
+        final_perm = order.sorted();
         if (row_map) launch_inverse_perm(final_perm, n_unique, row_map->urow_pos, st);
         if (!n_unique) HIP_TRY(hipStreamSynchronize(st));
     }
@@ -193,51 +168,41 @@ int barcode_rows(rgx_ctx *c, const Prep &P, const RowMap &rm, const rgx_extract_
     t->bc_row_begin = (uint64_t *)calloc(U + 1, 8);
     if (!E) { t->bc_count = (uint32_t *)calloc(1, 4); t->bc_str_begin = (uint64_t *)calloc(1, 8); t->bc_text = (char *)calloc(1, 1);
         t->bc_insert_rank = (uint32_t *)calloc(1, 4); return RGX_OK; }
-    uint32_t *d_sc = c->buf("scalars").as<uint32_t>();
-    uint32_t *h_sc = (uint32_t *)c->pinned;
+    Scalars *d_sc = c->buf("scalars").as<Scalars>(), *h_sc = (Scalars *)c->pinned;
     DevBuf &b_bc = c->buf("barcodes");
     const size_t rtmp = radix_tmp_words((uint32_t)E) + scan_tmp_words((uint32_t)E) + 64;
     HIP_TRY(b_bc.ensure(E * (8 + 4 * 4 + 4 * 4 + 8 + 4 * 5) + rtmp * 4 + 512));
-    uint8_t *q = b_bc.as<uint8_t>();
+    Carve q(b_bc);
     BarcodeEv b;
-    b.off = (uint64_t *)q; q += E * 8;
-    uint64_t *pair_off = (uint64_t *)q; q += E * 8;
-    b.len = (uint32_t *)q; q += E * 4; b.h_lo = (uint32_t *)q; q += E * 4; b.h_hi = (uint32_t *)q; q += E * 4; b.row = (uint32_t *)q; q += E * 4;
-    uint32_t *perm[2]; perm[0] = (uint32_t *)q; q += E * 4; perm[1] = (uint32_t *)q; q += E * 4;
-    uint32_t *head = (uint32_t *)q; q += E * 4; uint32_t *seg_excl = (uint32_t *)q; q += E * 4;
-    uint32_t *pair_row = (uint32_t *)q; q += E * 4; uint32_t *pair_first = (uint32_t *)q; q += E * 4; uint32_t *pair_pos = (uint32_t *)q; q += E * 4;
-    uint32_t *pair_len = (uint32_t *)q; q += E * 4; uint32_t *pair_count = (uint32_t *)q; q += E * 4;
-    uint32_t *tmp = (uint32_t *)q;
-    uint32_t *flags = d_sc + 72;
+    b.off = q.u64(E);
+    uint64_t *pair_off = q.u64(E);
+    b.len = q.u32(E); b.h_lo = q.u32(E); b.h_hi = q.u32(E); b.row = q.u32(E);
+    uint32_t *perm0 = q.u32(E), *perm1 = q.u32(E), *head = q.u32(E), *seg_excl = q.u32(E);
+    uint32_t *pair_row = q.u32(E), *pair_first = q.u32(E), *pair_pos = q.u32(E), *pair_len = q.u32(E), *pair_count = q.u32(E);
+    uint32_t *tmp = q.u32(rtmp); CARVE_TRY(q, "barcodes");
+    uint32_t *flags = &d_sc->barcodes.not_string;            // (k_bc_*: flags[0] = not_string, flags[1] = hash_clash)
     HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
     launch_bc_event_keys(P.arena, (uint32_t)E, P.ev.read, P.soa.rec_off, rm.ev_urow, rm.urow_pos, (uint8_t)p->barcode_tag[0], (uint8_t)p->barcode_tag[1], b,
         flags, st);
-    int pc = -1;
-    auto sort_word = [&](const uint32_t *word, uint32_t nbits) {
-        for (uint32_t sh = 0; sh < nbits; sh += 8) {
-            const int nxt = pc < 0 ? 0 : pc ^ 1;
-            launch_radix_pass(word, sh, std::min<uint32_t>(8, nbits - sh), pc < 0 ? nullptr : perm[pc], perm[nxt], (uint32_t)E, tmp, st);
-            pc = nxt;
-        }
-    };
-    sort_word(b.h_lo, 32); sort_word(b.h_hi, 32);
-    sort_word(b.row, std::max<uint32_t>(1, bitlen((uint32_t)std::max<size_t>(U, 1) - 1)));
-    const uint32_t *sorted = perm[pc];
+    RadixSort by_key{{perm0, perm1}, tmp, (uint32_t)E, st};
+    by_key.by(b.h_lo, 32); by_key.by(b.h_hi, 32);
+    by_key.by(b.row, std::max<uint32_t>(1, bitlen((uint32_t)std::max<size_t>(U, 1) - 1)));
+    const uint32_t *sorted = by_key.sorted();
     launch_bc_heads(P.arena, b, sorted, (uint32_t)E, head, flags, st);
-    launch_scan_u32(head, seg_excl, (uint32_t)E, d_sc + 74, tmp, st);
-    HIP_TRY(hipMemcpyAsync(h_sc + 72, d_sc + 72, 12, hipMemcpyDeviceToHost, st));
+    launch_scan_u32(head, seg_excl, (uint32_t)E, &d_sc->barcodes.n_pairs, tmp, st);
+    HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->barcodes, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_sc[72]) return fail(err, errlen, RGX_ERR_FORMAT,
+    if (h_sc->barcodes.not_string) return fail(err, errlen, RGX_ERR_FORMAT,
         "regtools_amd: the %c%c tag of an alignment is not a string (the reference dies on such input)\n\n", p->barcode_tag[0], p->barcode_tag[1]);
-    if (h_sc[73]) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: two different barcodes of one junction share a 64-bit hash; not handled\n\n");
-    const uint32_t n_pairs = h_sc[74];
+    if (h_sc->barcodes.hash_clash) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: two different barcodes of one junction share a 64-bit hash; not handled\n\n");
+    const uint32_t n_pairs = h_sc->barcodes.n_pairs;
     launch_bc_pairs(b, sorted, head, seg_excl, (uint32_t)E, pair_row, pair_first, pair_pos, pair_off, pair_len, st);
     launch_bc_counts(n_pairs, (uint32_t)E, pair_pos, pair_count, st);
     uint32_t *str_begin = head;                       // head / seg_excl are dead after launch_bc_pairs
-    launch_scan_u32(pair_len, str_begin, n_pairs, d_sc + 75, tmp, st);
-    HIP_TRY(hipMemcpyAsync(h_sc + 75, d_sc + 75, 4, hipMemcpyDeviceToHost, st));
+    launch_scan_u32(pair_len, str_begin, n_pairs, &d_sc->barcode_text_len, tmp, st);
+    HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->barcode_text_len, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const size_t text_len = h_sc[75];
+    const size_t text_len = h_sc->barcode_text_len;
     DevBuf &b_txt = c->buf("barcode_text");
     HIP_TRY(b_txt.ensure(text_len + 256));
     launch_bc_gather(P.arena, n_pairs, pair_off, pair_len, str_begin, b_txt.as<uint8_t>(), st);

@@ -109,6 +109,10 @@ struct rgx_cohort {
     DevBuf up, sort, rows, image;
 };
 
+// what rgx_cohort_finish's scans leave 16 words behind the append counter d_fill[0] (a block of 256 bytes): the distinct keys, and the rows and counts
+// the filters keep (read back by one copy)
+struct FinishTotals { uint32_t rows; struct Kept { uint32_t rows, nnz; } kept; };
+
 extern "C" void rgx_cohort_params_default(rgx_cohort_params *p) { if (p) { p->only_anchored = 1; p->min_samples = 1; p->min_total = 1; } }
 
 extern "C" int rgx_cohort_create(rgx_ctx *ctx, const rgx_cohort_params *p, rgx_cohort **out, char *err, size_t errlen) {
@@ -275,49 +279,42 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         const size_t tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;
         if (co->sort.ensure((Nn * (2 + 2 + 7) + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory to sort %u triples\n", N); }
-        uint32_t *w = co->sort.as<uint32_t>();
-        uint32_t *key[2] = {w, w + Nn}; w += 2 * Nn;
-        uint32_t *perm[2] = {w, w + Nn}; w += 2 * Nn;
-        CohortSorted s; s.tid = w; w += Nn; s.start = w; w += Nn; s.end = w; w += Nn; s.ts = w; w += Nn; s.te = w; w += Nn; s.count = w; w += Nn; s.ss = w; w += Nn;
-        uint32_t *tmp = w;
-        uint32_t *d_scal = co->d_fill + 16;
+        Carve w(co->sort);
+        uint32_t *key0 = w.u32(Nn), *key1 = w.u32(Nn), *perm0 = w.u32(Nn), *perm1 = w.u32(Nn);
+        CohortSorted s; s.tid = w.u32(Nn); s.start = w.u32(Nn); s.end = w.u32(Nn); s.ts = w.u32(Nn); s.te = w.u32(Nn); s.count = w.u32(Nn); s.ss = w.u32(Nn);
+        uint32_t *tmp = w.u32(tmp_words); CARVE_TRY(w, "cohort sort");
+        FinishTotals *d_tot = (FinishTotals *)(co->d_fill + 16);
         // stable LSD radix sort by (tid, start, end, class): the triples of one key keep the order they were appended in, which is sample order.
         // Each key word is gathered through the permutation once; its 8-bit passes then stream (key, permutation) pairs.
-        int pc = -1;
+        RadixSort by_key{{perm0, perm1}, tmp, N, st, {key0, key1}};
         auto sort_word = [&](uint32_t which, uint32_t nbits) {
-            launch_cohort_key(co->d_blocks, pc < 0 ? nullptr : perm[pc], N, which, key[0], st);
-            int kc = 0;
-            for (uint32_t sh = 0; sh < nbits; sh += 8) {
-                const int nxt = pc < 0 ? 0 : pc ^ 1;
-                launch_radix_pass_keyed(key[kc], key[kc ^ 1], sh, std::min<uint32_t>(8, nbits - sh), pc < 0 ? nullptr : perm[pc], perm[nxt], N, tmp, st);
-                kc ^= 1; pc = nxt;
-            }
+            by_key.by_gathered([&](const uint32_t *perm_in, uint32_t *out) { launch_cohort_key(co->d_blocks, perm_in, N, which, out, st); }, nbits);
         };
         sort_word(3, 2);
         sort_word(2, std::max<uint32_t>(1, bitlen(co->max_end)));
         sort_word(1, std::max<uint32_t>(1, bitlen(co->max_start)));
         sort_word(0, std::max<uint32_t>(1, bitlen((uint32_t)std::max<size_t>(co->contigs.names.size(), 1) - 1)));
         mark("key sort");
-        uint32_t *head = key[0], *seg = key[1], *row_start = perm[pc ^ 1];
-        launch_cohort_gather(co->d_blocks, perm[pc], N, s, head, st);
-        launch_scan_u32(head, seg, N, d_scal, tmp, st);
+        uint32_t *head = key0, *seg = key1, *row_start = by_key.spare();
+        launch_cohort_gather(co->d_blocks, by_key.sorted(), N, s, head, st);
+        launch_scan_u32(head, seg, N, &d_tot->rows, tmp, st);
         launch_cohort_row_start(head, seg, N, row_start, st);
-        HIP_TRY(hipMemcpyAsync(&U, d_scal, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&U, &d_tot->rows, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         mark("gather + heads");
         const size_t Un = (size_t)U + 64;
         if (co->rows.ensure(Un * (2 + 6) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory for %u cohort rows\n", U); }
-        uint32_t *q = co->rows.as<uint32_t>();
-        CohortRows r; r.total = (unsigned long long *)q; q += 2 * Un; r.ts = q; q += Un; r.te = q; q += Un; r.keep = q; q += Un; r.kept_nnz = q; q += Un;
-        uint32_t *out_row = q; q += Un; uint32_t *nnz_excl = q;
+        Carve q(co->rows);
+        CohortRows r; r.total = (unsigned long long *)q.u64(Un); r.ts = q.u32(Un); r.te = q.u32(Un); r.keep = q.u32(Un); r.kept_nnz = q.u32(Un);
+        uint32_t *out_row = q.u32(Un), *nnz_excl = q.u32(Un); CARVE_TRY(q, "cohort rows");
         launch_cohort_reduce(s, row_start, N, U, co->p.min_samples, co->p.min_total, r, st);
-        launch_scan_u32(r.keep, out_row, U, d_scal + 1, tmp, st);
-        launch_scan_u32(r.kept_nnz, nnz_excl, U, d_scal + 2, tmp, st);
-        uint32_t two[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(two, d_scal + 1, 8, hipMemcpyDeviceToHost, st));
+        launch_scan_u32(r.keep, out_row, U, &d_tot->kept.rows, tmp, st);
+        launch_scan_u32(r.kept_nnz, nnz_excl, U, &d_tot->kept.nnz, tmp, st);
+        FinishTotals::Kept kept = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&kept, &d_tot->kept, sizeof kept, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        Uk = two[0]; NNZ = two[1];
+        Uk = kept.rows; NNZ = kept.nnz;
         mark("reduce + filters");
         const MatrixLayout L = matrix_layout(Uk, NNZ);
         if (co->image.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,

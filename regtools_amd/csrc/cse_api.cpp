@@ -126,16 +126,16 @@ static int variant_windows(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32
     hipStream_t st = c->stream;
     HIP_ENTER(c->device);
     DevBuf &b = c->buf("cse_variants"), &sc = c->buf("scalars");
-    HIP_TRY(sc.ensure(512));
+    HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t N = n;
     HIP_TRY(b.ensure(N * 4 * 7 + scan_tmp_words(n) * 4 + 256));
     uint32_t *w = b.as<uint32_t>();
     int32_t *d_chrom = (int32_t *)w; w += N; uint32_t *d_pos = w; w += N; uint32_t *d_cnt = w; w += N; uint32_t *d_base = w; w += N;
     uint32_t *d_ces = w; w += N; uint32_t *d_cee = w; w += N; uint32_t *d_last = w; w += N; uint32_t *d_tmp = w;
-    uint32_t *d_total = sc.as<uint32_t>() + 60;
+    uint32_t *d_total = &sc.as<Scalars>()->variant_hits;
     HIP_TRY(hipMemcpyAsync(d_chrom, chrom.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_pos, pos0.data(), N * 4, hipMemcpyHostToDevice, st));
-    unsigned long long *d_visits = (unsigned long long *)(sc.as<uint32_t>() + 64), h_visits = 0;
+    unsigned long long *d_visits = &sc.as<Scalars>()->variant_visits, h_visits = 0;
     HIP_TRY(hipMemsetAsync(d_visits, 0, 8, st));
     ktime_begin(c, 0);
     launch_variant_scan(false, g->view, n, d_chrom, d_pos, o, d_cnt, nullptr, d_ces, d_cee, nullptr, nullptr, d_visits, st, d_last);
@@ -206,18 +206,18 @@ static int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<in
     hipStream_t st = c->stream;
     HIP_ENTER(c->device);
     DevBuf &b = c->buf("cse_junctions"), &sc = c->buf("scalars");
-    HIP_TRY(sc.ensure(512));
+    HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t N = n;
     HIP_TRY(b.ensure(N * 4 * 7 + N + scan_tmp_words(n) * 4 + 512));
     uint32_t *w = b.as<uint32_t>();
     int32_t *d_chrom = (int32_t *)w; w += N; uint32_t *d_js = w; w += N; uint32_t *d_je = w; w += N; uint32_t *d_cnt = w; w += N; uint32_t *d_base = w; w += N;
     uint32_t *d_flags = w; w += N; uint32_t *d_visit_each = w; w += N; uint32_t *d_tmp = w; w += scan_tmp_words(n) + 8; uint8_t *d_strand = (uint8_t *)w;
-    uint32_t *d_total = sc.as<uint32_t>() + 61;
+    uint32_t *d_total = &sc.as<Scalars>()->junction_items;
     HIP_TRY(hipMemcpyAsync(d_chrom, chrom.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_js, js.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_je, je.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_strand, strand.data(), N, hipMemcpyHostToDevice, st));
-    unsigned long long *d_visits = (unsigned long long *)(sc.as<uint32_t>() + 66), h_visits = 0;
+    unsigned long long *d_visits = &sc.as<Scalars>()->junction_visits, h_visits = 0;
     HIP_TRY(hipMemsetAsync(d_visits, 0, 8, st));
     ktime_begin(c, 1);
     launch_junction_scan(false, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, nullptr, d_flags, nullptr, nullptr, nullptr, d_visits, d_visit_each, st);
@@ -315,7 +315,7 @@ static int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_
     uint32_t *w = b.as<uint32_t>();
     int32_t *d_tid = (int32_t *)w; w += Wn; int32_t *d_beg = (int32_t *)w; w += Wn; int32_t *d_end = (int32_t *)w; w += Wn;
     uint32_t *d_lo = w; w += Wn; uint32_t *d_hi = w; w += Wn; uint32_t *d_cnt = w; w += Sn; uint32_t *d_base = w; w += Sn; uint32_t *d_tmp = w;
-    uint32_t *d_span = sc.as<uint32_t>() + 62, *d_total = sc.as<uint32_t>() + 63;
+    uint32_t *d_span = &sc.as<Scalars>()->max_span, *d_total = &sc.as<Scalars>()->window_pairs;
     HIP_TRY(hipMemcpyAsync(d_tid, w_tid.data(), Wn * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_beg, w_beg.data(), Wn * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_end, w_end.data(), Wn * 4, hipMemcpyHostToDevice, st));
@@ -1089,14 +1089,14 @@ static int identify_run(rgx_ctx *c, const std::vector<rgx_ctx *> *shards, const 
             hipStream_t st = c->stream;
             HIP_ENTER(c->device);
             DevBuf &b = c->buf("cse_assoc"), &sc = c->buf("scalars");
-            HIP_TRY(sc.ensure(512));
+            HIP_TRY(sc.ensure(sizeof(Scalars)));
             const size_t Wn = W, Jn = J, Cn = chrom_off.size();
             HIP_TRY(b.ensure((Wn * 5 + Jn * 2 + Cn + scan_tmp_words(W)) * 4 + 512));
             uint32_t *w = b.as<uint32_t>();
             int32_t *d_wch = (int32_t *)w; w += Wn; uint32_t *d_ces = w; w += Wn; uint32_t *d_cee = w; w += Wn; uint32_t *d_cnt = w; w += Wn;
                 uint32_t *d_base = w; w += Wn;
             uint32_t *d_js = w; w += Jn; uint32_t *d_je = w; w += Jn; uint32_t *d_off = w; w += Cn; uint32_t *d_tmp = w;
-            uint32_t *d_total = sc.as<uint32_t>() + 68;
+            uint32_t *d_total = &sc.as<Scalars>()->assoc_pairs;
             HIP_TRY(hipMemcpyAsync(d_wch, wch.data(), Wn * 4, hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(d_ces, wces.data(), Wn * 4,
                 hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_cee, wcee.data(), Wn * 4, hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(d_js, js.data(), Jn * 4,
