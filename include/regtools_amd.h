@@ -302,6 +302,33 @@ int  rgx_k_inflate(const void *d_comp, const rgx_member *d_members, uint32_t n_m
 int  rgx_k_inflate_form(int form, const void *d_comp, const rgx_member *d_members, uint32_t n_members,
                         void *d_arena, uint32_t *d_status, void *stream);
 
+/* The tail behind the DEFLATE launch, stage by stage (tests): the exclusive scan, the radix sort and the group-by every table goes through, on the
+ * caller's DEVICE arrays.  They run the pipeline's own code on the context's stream with scratch carved from the context's buffers as the
+ * pipeline carves it, and return behind a synchronisation of that stream; the caller's arrays must be complete before the call (the
+ * context's stream does not wait for the caller's).  RGX_ERR_DEVICE also when a stage wrote behind the scratch its own sizing function
+ * (scan_tmp_words / radix_tmp_words) gives it. */
+/* d_out[i] = d_in[0] + ... + d_in[i - 1] (mod 2^32); d_out may be d_in; *d_total = the sum of all n, written only when d_total is not NULL
+ * (0 for n = 0). */
+int  rgx_k_scan_u32(rgx_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint32_t n, uint32_t *d_total, char *err, size_t errlen);
+/* d_perm_out = the positions 0 .. n-1 in stable order of the key whose word k (k = 0 the LEAST significant) is the low nbits[k] (1 .. 32) bits of
+ * d_words[k][position]; d_words and nbits are host arrays of n_words entries.  mode = how the sort is driven, word by word: 0 = plain passes that
+ * gather the word through the permutation, 1 = the word gathered once and its passes keyed, 2 = keyed passes on a word the caller's gather
+ * produces (here: the column through the permutation, or a copy of it in front of the first pass).  n_scratch (0 = n): the key count the scratch
+ * is sized and carved for, n_scratch >= n -- a merge sorts its unique rows in the scratch of all its rows.  n = 0 writes nothing. */
+int  rgx_k_radix_sort(rgx_ctx *ctx, uint32_t n, uint32_t n_scratch, uint32_t n_words, const uint32_t *const *d_words, const uint32_t *nbits,
+                      int mode, uint32_t *d_perm_out, char *err, size_t errlen);
+/* Junction events (file order) -> the unique rows in output order.  Key = (tid, start, ilen_cls), ilen_cls = intron length << 2 | strand class;
+ * every tid is below n_groups and 2^group_bits, every ilen_cls below 2^ilen_bits; rank_of_group_host[tid] (host, n_groups entries) leads the
+ * output order.  form: 0 = equal keys grouped per tile of events first (junctions extract), 1 = the events sorted as they are (identify),
+ * 2 = 1 + the row map of -b: d_ev_urow[event] = its unique row, d_urow_pos[unique row] = that row's place in the output (n_events entries
+ * each).  d_rows_out: room for 10 x n_events words; receives ten columns of *n_rows_out entries each -- tid, start, end, thick_start,
+ * thick_end, count, name rank (1-based, by first event), first event, last event, strand byte of the last event.  The context's last
+ * table is no longer valid for rgx_last_table_pack_device afterwards. */
+int  rgx_k_group_by(rgx_ctx *ctx, const uint32_t *d_tid, const uint32_t *d_start, const uint32_t *d_ilen_cls, const uint32_t *d_ts,
+                    const uint32_t *d_te, const uint8_t *d_strand, uint32_t n_events, uint32_t group_bits, uint32_t ilen_bits,
+                    const uint32_t *rank_of_group_host, uint32_t n_groups, int form, uint32_t *d_rows_out, uint64_t *n_rows_out,
+                    uint32_t *d_ev_urow, uint32_t *d_urow_pos, char *err, size_t errlen);
+
 /* =====================================================================================================
  * `cis-splice-effects identify`.
  * Replaces CisSpliceEffectsIdentifier::identify() + annotate_junctions()

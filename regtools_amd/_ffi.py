@@ -51,7 +51,8 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_table_pack_barcodes", "rgx_table_unpack_barcodes", "rgx_identify_multi", "rgx_ctx_arena_trials",
            "rgx_pipeline_create", "rgx_pipeline_depth", "rgx_pipeline_ctx", "rgx_extract_submit", "rgx_extract_wait", "rgx_pipeline_destroy",
            "rgx_cohort_params_default", "rgx_cohort_create", "rgx_cohort_add", "rgx_cohort_add_path", "rgx_cohort_finish", "rgx_cohort_destroy",
-           "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts"]
+           "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts",
+           "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by"]
 
 
 class CohortParams(C.Structure):
@@ -167,6 +168,10 @@ def lib():
         L.rgx_table_format_barcodes.restype = C.c_size_t
         L.rgx_k_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rgx_k_inflate_form.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rgx_k_scan_u32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+        L.rgx_k_radix_sort.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p), P(C.c_uint32), C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
+        L.rgx_k_group_by.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p,
+                                     P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
         L.rgx_identify_params_default.argtypes = [P(IdentifyParams)]
         L.rgx_identify.argtypes = [C.c_void_p, P(IdentifyParams), P(IdentifyStats), C.c_char_p, C.c_size_t]
         L.rgx_associate.argtypes = L.rgx_identify.argtypes
