@@ -284,6 +284,59 @@ size_t rgx_cohort_format_bed12(const rgx_cohort_matrix *m, char *buf, size_t cap
  * S dense counts (0 where a sample lacks the key).  Same buffer protocol. */
 size_t rgx_cohort_format_counts(const rgx_cohort_matrix *m, char *buf, size_t cap);
 
+/* =====================================================================================================
+ * Intron clusters of a cohort matrix: the junctions that hang together through shared splice sites, and per cluster and sample the reads
+ * on it -- the denominators of the ratio "reads on this junction / reads on its cluster" that differential-splicing tools work with.
+ * The reference has no counterpart; this is the cohort's own rule.  It is the FIRST step of LeafCutter-style clustering only: it makes no
+ * claim to equal LeafCutter's iterative refinement (which removes weak introns and clusters again), and there is NO re-clustering behind
+ * the filters here -- a component is kept or dropped whole.
+ *   input                 any rgx_cohort_matrix m: from rgx_cohort_finish or rgx_cohort_merge_host, filtered or not
+ *   graph                 rows i and j are linked when they have the same tid, the same strand class (m->strand[i]: '+' 0, '-' 1, anything
+ *                         else 2) and the same start or the same end; a cluster is a connected component (transitive: A and B sharing a
+ *                         start and B and C sharing an end puts all three in one)
+ *   filters               a component is kept when it has at least min_rows rows and the sum of m->total over them is at least min_total;
+ *                         the rows of a dropped one get cluster[i] = RGX_NO_CLUSTER
+ *   numbering             kept clusters are 0 .. C-1, ascending by the index of their first (lowest) row in m
+ *   denominators          per cluster, the samples whose counts over its rows sum to more than zero, ascending, and that sum (64 bit)
+ *   limits                m->n and m->row_begin[m->n] each at most 2^32 - 2^16 (RGX_ERR_ARG beyond); RGX_ERR_DEVICE when workspace cannot be
+ *                         had; an empty matrix gives n_clusters = 0 and cl_begin = cs_begin = [0]
+ * ===================================================================================================== */
+#define RGX_NO_CLUSTER 0xffffffffu
+typedef struct { uint32_t min_rows; uint64_t min_total; } rgx_cluster_params;
+/* Structure-of-arrays, owned by the library (rgx_cohort_clusters_free), one page-locked block like the matrix. */
+typedef struct {
+    uint64_t   n_rows;          /* = m->n */
+    uint64_t   n_clusters;      /* C */
+    uint32_t  *cluster;         /* n_rows: the row's cluster, or RGX_NO_CLUSTER */
+    uint64_t  *cl_begin;        /* C + 1: cluster k owns cl_row [cl_begin[k], cl_begin[k + 1]) */
+    uint32_t  *cl_row;          /* the member rows, ascending within a cluster */
+    uint64_t  *cl_total;        /* C: sum of m->total over the members */
+    uint64_t  *cs_begin;        /* C + 1: cluster k owns cs_sample / cs_total [cs_begin[k], cs_begin[k + 1]) */
+    uint32_t  *cs_sample;       /* ascending within a cluster */
+    uint64_t  *cs_total;        /* the cluster's reads in that sample (never 0) */
+    /* statistics */
+    uint32_t   n_rounds;        /* hook + jump rounds the component search ran, the one that changed nothing included (the twin: 0) */
+    double     ms_cluster;      /* this call, wall, up to the result being in host memory */
+    uint64_t   n_components;    /* before the filters */
+} rgx_cohort_clusters;
+void rgx_cluster_params_default(rgx_cluster_params *p);                     /* 1, 0: everything is kept */
+/* On the cohort's device and stream.  When m is the matrix of co's most recent finish its image is still in HBM and is read in place;
+ * otherwise the columns needed (tid, start, end, strand, total, row_begin, col_sample, val_count) are uploaded.  Same result.  co may be a
+ * cohort with no samples.  Two stable radix sorts of the rows give the edges (neighbours in a site group), hooking towards the smaller
+ * label and pointer jumping give the components, and one key-carrying radix sort of the count entries gives the denominators. */
+int  rgx_cohort_cluster(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_cluster_params *p, rgx_cohort_clusters **out,
+                        char *err, size_t errlen);
+int  rgx_cohort_cluster_path(rgx_cohort *co);   /* statistics: 1 = the last cluster call read the matrix in HBM, 0 = it uploaded it */
+/* Host twin: sort-based site groups plus union-find in plain C++, its own code path, no device.  NOT a fallback: it is what the device result
+ * is checked against. */
+int  rgx_cohort_cluster_host(const rgx_cohort_matrix *m, const rgx_cluster_params *p, rgx_cohort_clusters **out, char *err, size_t errlen);
+void rgx_cohort_clusters_free(rgx_cohort_clusters *cl);
+/* The cluster counts in the layout of LeafCutter's perind.counts: "chrom" and one " <sample name>" per sample, then one line per clustered
+ * row in matrix order: "<contig>:<start>:<end>:clu_<k>_<s>" (k = cluster + 1; s = +, - or NA by strand class) and one " <num>/<den>" per
+ * sample -- the row's count in the sample over the cluster's, "0/0" where the sample has no reads in the cluster.  Rows with
+ * RGX_NO_CLUSTER are left out.  Buffer protocol of rgx_cohort_format_counts. */
+size_t rgx_cohort_format_cluster_counts(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, char *buf, size_t cap);
+
 /* Library/build identification: "regtools_amd <version> gfx950". */
 const char *rgx_version(void);
 
@@ -328,6 +381,11 @@ int  rgx_k_group_by(rgx_ctx *ctx, const uint32_t *d_tid, const uint32_t *d_start
                     const uint32_t *d_te, const uint8_t *d_strand, uint32_t n_events, uint32_t group_bits, uint32_t ilen_bits,
                     const uint32_t *rank_of_group_host, uint32_t n_groups, int form, uint32_t *d_rows_out, uint64_t *n_rows_out,
                     uint32_t *d_ev_urow, uint32_t *d_urow_pos, char *err, size_t errlen);
+/* The component search of the cohort's intron clusters on the caller's edge list: edge e joins vertices d_a[e] and d_b[e], all below
+ * n_vertices (self loops and duplicates allowed).  d_label_out[v] = the smallest vertex id of v's component; *n_rounds = the hook + jump
+ * rounds run, the one that changed nothing included. */
+int  rgx_k_components(rgx_ctx *ctx, uint32_t n_vertices, uint32_t n_edges, const uint32_t *d_a, const uint32_t *d_b, uint32_t *d_label_out,
+                      uint32_t *n_rounds, char *err, size_t errlen);
 
 /* =====================================================================================================
  * `cis-splice-effects identify`.

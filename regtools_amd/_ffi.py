@@ -52,7 +52,9 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_pipeline_create", "rgx_pipeline_depth", "rgx_pipeline_ctx", "rgx_extract_submit", "rgx_extract_wait", "rgx_pipeline_destroy",
            "rgx_cohort_params_default", "rgx_cohort_create", "rgx_cohort_add", "rgx_cohort_add_path", "rgx_cohort_finish", "rgx_cohort_destroy",
            "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts",
-           "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by"]
+           "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by",
+           "rgx_cluster_params_default", "rgx_cohort_cluster", "rgx_cohort_cluster_path", "rgx_cohort_cluster_host", "rgx_cohort_clusters_free",
+           "rgx_cohort_format_cluster_counts", "rgx_k_components"]
 
 
 class CohortParams(C.Structure):
@@ -67,6 +69,17 @@ class CohortMatrix(C.Structure):
                 ("n_with", C.POINTER(C.c_uint32)), ("total", C.POINTER(C.c_uint64)), ("row_begin", C.POINTER(C.c_uint64)),
                 ("col_sample", C.POINTER(C.c_uint32)), ("val_count", C.POINTER(C.c_uint32)),
                 ("ms_add_total", C.c_double), ("ms_finish", C.c_double), ("n_triples", C.c_uint64)]
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("min_rows", C.c_uint32), ("min_total", C.c_uint64)]
+
+
+class CohortClusters(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_clusters", C.c_uint64), ("cluster", C.POINTER(C.c_uint32)), ("cl_begin", C.POINTER(C.c_uint64)),
+                ("cl_row", C.POINTER(C.c_uint32)), ("cl_total", C.POINTER(C.c_uint64)), ("cs_begin", C.POINTER(C.c_uint64)),
+                ("cs_sample", C.POINTER(C.c_uint32)), ("cs_total", C.POINTER(C.c_uint64)),
+                ("n_rounds", C.c_uint32), ("ms_cluster", C.c_double), ("n_components", C.c_uint64)]
 
 
 class IdentifyParams(C.Structure):
@@ -206,6 +219,14 @@ def lib():
         L.rgx_cohort_format_bed12.restype = C.c_size_t
         L.rgx_cohort_format_counts.argtypes = [P(CohortMatrix), C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_counts.restype = C.c_size_t
+        L.rgx_cluster_params_default.argtypes = [P(ClusterParams)]
+        L.rgx_cohort_cluster.argtypes = [C.c_void_p, P(CohortMatrix), P(ClusterParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_cluster_path.argtypes = [C.c_void_p]
+        L.rgx_cohort_cluster_host.argtypes = [P(CohortMatrix), P(ClusterParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_clusters_free.argtypes = [P(CohortClusters)]
+        L.rgx_cohort_format_cluster_counts.argtypes = [P(CohortMatrix), P(CohortClusters), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_cluster_counts.restype = C.c_size_t
+        L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 

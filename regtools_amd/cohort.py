@@ -76,6 +76,64 @@ class CohortMatrix(object):
             pass
 
 
+class CohortClusters(object):
+    """rgx_cohort_clusters: the intron clusters of a matrix (rows linked through a shared start or end) and, per cluster and sample, the reads on
+    it.  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        c = handle.contents
+        self.n_rows, self.n_clusters, self.n_components = int(c.n_rows), int(c.n_clusters), int(c.n_components)
+        self.n_rounds, self.ms_cluster = int(c.n_rounds), c.ms_cluster
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        self.cluster = view(c.cluster, self.n_rows, np.uint32)
+        self.cl_begin = np.ctypeslib.as_array(c.cl_begin, shape=(self.n_clusters + 1,))
+        self.cs_begin = np.ctypeslib.as_array(c.cs_begin, shape=(self.n_clusters + 1,))
+        self.cl_row, self.cl_total = view(c.cl_row, int(self.cl_begin[-1]), np.uint32), view(c.cl_total, self.n_clusters, np.uint64)
+        self.cs_sample, self.cs_total = view(c.cs_sample, int(self.cs_begin[-1]), np.uint32), view(c.cs_total, int(self.cs_begin[-1]), np.uint64)
+
+    def counts_text(self, matrix):
+        """The cluster counts of `matrix` (the CohortMatrix these clusters were made from) in the layout of LeafCutter's perind.counts."""
+        fn = self._lib.rgx_cohort_format_cluster_counts
+        n = fn(matrix._h, self._h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, self._h, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_clusters_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _cluster_params(min_rows, min_total):
+    p = _ffi.ClusterParams()
+    _ffi.lib().rgx_cluster_params_default(C.byref(p))
+    p.min_rows, p.min_total = min_rows, min_total
+    return p
+
+
+def cluster_host(matrix, min_rows=1, min_total=0):
+    """rgx_cohort_cluster_host: the clusters of a CohortMatrix by the library's plain C++ twin, no device involved."""
+    p = _cluster_params(min_rows, min_total)
+    out = C.POINTER(_ffi.CohortClusters)()
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_cluster_host(matrix._h, C.byref(p), C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortClusters(out)
+
+
 def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1):
     """rgx_cohort_merge_host over the tables the extractors hold (each with its own min_anchor_length_): no device involved."""
     lib = _ffi.lib()
@@ -111,6 +169,7 @@ class Cohort(object):
         self._device = device
         self._h = C.c_void_p()
         self.add_paths = []                      # per add: 1 = device to device, 0 = uploaded (rgx_cohort_add_path)
+        self.cluster_paths = []                  # per cluster: 1 = the matrix was still in HBM, 0 = uploaded (rgx_cohort_cluster_path)
         p = _params(only_anchored, min_samples, min_total)
         err = C.create_string_buffer(512)
         rc = self._lib.rgx_cohort_create(self._ctx._h, C.byref(p), C.byref(self._h), err, len(err))
@@ -136,6 +195,18 @@ class Cohort(object):
         if rc != 0:
             raise RegtoolsError(rc, err.value.decode())
         return CohortMatrix(out)
+
+    def cluster(self, matrix, min_rows=1, min_total=0):
+        """The intron clusters of `matrix` (any CohortMatrix) on this cohort's device.  The matrix of the most recent finish is read where it lies
+        in HBM; any other one is uploaded."""
+        p = _cluster_params(min_rows, min_total)
+        out = C.POINTER(_ffi.CohortClusters)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_cluster(self._h, matrix._h, C.byref(p), C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
+        return CohortClusters(out)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

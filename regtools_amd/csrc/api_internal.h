@@ -255,6 +255,15 @@ struct RadixSort {
     void reset() { cur = -1; }
 };
 
+// The component search of the cohort's intron clusters (cohort_cluster.cpp; also behind rgx_k_components): every vertex of parent[0 .. n_vertices) gets the
+// smallest vertex id of its component under the edges of `lists`.  Rounds of one hook launch per list and one jump launch are enqueued kCcBatch at a
+// time, each with its own flag word in d_flags (kCcBatch words, zeroed per batch); the host reads the flags behind a batch and stops at the first round
+// that changed nothing.  *n_rounds counts the rounds up to and including that one.
+constexpr uint32_t kCcBatch = 4;
+struct EdgeList { const uint32_t *a, *b; uint32_t n; };
+int components_run(uint32_t n_vertices, const EdgeList *lists, int n_lists, uint32_t *parent, uint32_t *d_flags, hipStream_t st, uint32_t *n_rounds,
+                   char *err, size_t errlen);
+
 constexpr int kSideStreams = 2;
 // REGTOOLS_AMD_OVERLAP="min_bytes[,chunks[,early_min_members]]" (tests): the thresholds of the overlapped upload, so that files of test size take the path
 // the 533 MB bench file takes -- from how many bytes a host buffer goes up in chunks behind ONE arrival-gated inflate launch (default 8 MiB), in how many

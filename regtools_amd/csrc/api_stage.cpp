@@ -106,3 +106,24 @@ extern "C" int rgx_k_group_by(rgx_ctx *c, const uint32_t *d_tid, const uint32_t 
     *n_rows_out = R.n;
     return RGX_OK;
 }
+
+extern "C" int rgx_k_components(rgx_ctx *c, uint32_t n_vertices, uint32_t n_edges, const uint32_t *d_a, const uint32_t *d_b, uint32_t *d_label_out,
+                                uint32_t *n_rounds, char *err, size_t errlen) {
+    if (!c || (n_edges && (!d_a || !d_b)) || (n_vertices && !d_label_out)) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
+    if (n_rounds) *n_rounds = 0;
+    HIP_ENTER(c->device);
+    hipStream_t st = c->stream;
+    // (rgx_cohort_cluster's loop: the labels live in the caller's array, the scratch is the rounds' flag words)
+    DevBuf &b = c->buf("stage");
+    HIP_TRY(b.ensure((kCcBatch + kGuardWords) * 4 + 256));
+    Carve q(b);
+    uint32_t *flags = q.u32(kCcBatch), *guard_at = q.u32(kGuardWords); CARVE_TRY(q, "stage");
+    Guard g; g.arm(guard_at, st);
+    const EdgeList list = {d_a, d_b, n_edges};
+    const int rc = components_run(n_vertices, &list, 1, d_label_out, flags, st, n_rounds, err, errlen);
+    if (rc != RGX_OK) return rc;
+    bool touched = false;
+    HIP_TRY(g.check(st, &touched));
+    if (touched) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the component search wrote behind its %u flag words\n", kCcBatch);
+    return RGX_OK;
+}

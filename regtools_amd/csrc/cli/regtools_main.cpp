@@ -251,6 +251,10 @@ void cohort_usage(std::ostream &out) {
         << "\t\t-t STR\tTag used in bam to label strand. [XS]\n"
         << "\t\t-o FILE\tThe cohort's junctions as BED12; the score is the summed read count. [STDOUT]\n"
         << "\t\t-c FILE\tThe counts table: chrom, start, end, strand and one column per sample.\n"
+        << "\t\t-k FILE\tThe cluster counts: junctions linked through a shared start or end, <reads on the junction>/<reads on its cluster>\n"
+        << "\t\t\t per sample, laid out as LeafCutter's perind.counts.\n"
+        << "\t\t-K INT\tKeep clusters of at least INT junctions. [1]\n"
+        << "\t\t-T INT\tKeep clusters with at least INT reads over all samples. [0]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -300,13 +304,15 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA";
+        std::string counts = "NA", clusters = "NA";
         rgx_cohort_params cp;
         rgx_cohort_params_default(&cp);
+        rgx_cluster_params kp;
+        rgx_cluster_params_default(&kp);
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -319,6 +325,9 @@ int junctions_cohort(int argc, char **argv) {
                 case 'A': cp.only_anchored = 0; break;
                 case 'n': cp.min_samples = (uint32_t)atoi(optarg); break;
                 case 'N': cp.min_total = (uint64_t)atoll(optarg); break;
+                case 'k': clusters = optarg; break;
+                case 'K': kp.min_rows = (uint32_t)atoi(optarg); break;
+                case 'T': kp.min_total = (uint64_t)atoll(optarg); break;
                 case 's': {
                     std::string s = optarg;
                     if (s == "XS") o.strandness = 0; else if (s == "RF") o.strandness = 1; else if (s == "FR") o.strandness = 2;
@@ -391,7 +400,10 @@ int junctions_cohort(int argc, char **argv) {
         }
         rgx_cohort_matrix *m = nullptr;
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
+        if (ok && clusters != "NA" && rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         if (!ok) {
+            if (m) rgx_cohort_matrix_free(m);
             rgx_pipeline_destroy(pl);                       // (runs what is still queued to its end: the buffers below were promised to it)
             for (Flight &f : fl) if (f.bam) rgx_host_free(f.bam);
             rgx_cohort_destroy(co);
@@ -404,6 +416,8 @@ int junctions_cohort(int argc, char **argv) {
         rgx_cohort_format_bed12(m, bed.get(), nb);
         size_t nc = 0; std::unique_ptr<char[]> tsv;
         if (counts != "NA") { nc = rgx_cohort_format_counts(m, nullptr, 0); tsv.reset(new char[nc + 1]); rgx_cohort_format_counts(m, tsv.get(), nc); }
+        size_t nk = 0; std::unique_ptr<char[]> ktx;
+        if (cl) { nk = rgx_cohort_format_cluster_counts(m, cl, nullptr, 0); ktx.reset(new char[nk + 1]); rgx_cohort_format_cluster_counts(m, cl, ktx.get(), nk); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -413,10 +427,19 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + counts + "\n\n");
             short_write |= fwrite(tsv.get(), 1, nc, g) != nc; short_write |= fclose(g) != 0;
         }
+        if (cl) {
+            FILE *g = fopen(clusters.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + clusters + "\n\n");
+            short_write |= fwrite(ktx.get(), 1, nk, g) != nk; short_write |= fclose(g) != 0;
+        }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
             fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
                     (unsigned long long)m->n_triples, (unsigned long long)m->n, m->ms_add_total, m->ms_finish);
+        if (cl && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] clusters: %llu of %llu components kept, %u rounds, %.3f ms\n", (unsigned long long)cl->n_clusters,
+                    (unsigned long long)cl->n_components, cl->n_rounds, cl->ms_cluster);
+        rgx_cohort_clusters_free(cl);
         rgx_cohort_matrix_free(m);
         rgx_cohort_destroy(co);
         rgx_pipeline_destroy(pl);

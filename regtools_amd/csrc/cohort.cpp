@@ -5,66 +5,21 @@
 // joined by a script; the reference has no counterpart.  The semantics (rows that take part, contigs by name, key, reductions, order, filters) are
 // stated once, in the header.  Device side: cohort_kernels.hip.  add is an enqueue: a sample's rows go from the block its extraction left in the source
 // context's HBM (or from an uploaded copy of the host table) into the accumulator on the cohort's own stream; finish sorts, reduces and copies back.
-#include "api_internal.h"
+#include "cohort_internal.h"
 
 namespace {
-
-// The cohort's contig table: the samples' header names in order of first appearance.
-struct CohortContigs {
-    std::vector<std::string> names; std::vector<uint32_t> lens, first_sample;
-    std::unordered_map<std::string, uint32_t> index;
-    // map[tid of t] = cohort tid.  A name that is already there with another length changes nothing and is an error.
-    int map_sample(const rgx_junction_table *t, uint32_t sample, const char *sample_name, const std::vector<std::string> &sample_names,
-                   std::vector<uint32_t> &map, char *err, size_t errlen) {
-        std::unordered_map<std::string, uint32_t> own;                       // (a header may list a name twice)
-        for (int32_t i = 0; i < t->n_ref; ++i) {
-            const std::string nm = t->ref_name[i];
-            auto it = index.find(nm);
-            if (it != index.end() && lens[it->second] != t->ref_len[i]) return fail(err, errlen, RGX_ERR_ARG,
-                "regtools_amd: contig %s is %u long in sample %s and %u in sample %s\n", nm.c_str(), lens[it->second],
-                sample_names[first_sample[it->second]].c_str(), t->ref_len[i], sample_name);
-            auto o = own.find(nm);
-            if (o != own.end() && o->second != t->ref_len[i]) return fail(err, errlen, RGX_ERR_ARG,
-                "regtools_amd: contig %s is %u long in sample %s and %u in sample %s\n", nm.c_str(), o->second, sample_name, t->ref_len[i], sample_name);
-            own[nm] = t->ref_len[i];
-        }
-        map.resize((size_t)std::max<int32_t>(t->n_ref, 0));
-        for (int32_t i = 0; i < t->n_ref; ++i) {
-            const std::string nm = t->ref_name[i];
-            auto it = index.find(nm);
-            if (it == index.end()) {
-                it = index.emplace(nm, (uint32_t)names.size()).first;
-                names.push_back(nm); lens.push_back(t->ref_len[i]); first_sample.push_back(sample);
-            }
-            map[(size_t)i] = it->second;
-        }
-        return RGX_OK;
-    }
-};
 
 inline bool anchored(const rgx_junction_table *t, uint64_t i, uint32_t min_anchor) {
     return (uint32_t)(t->start[i] - t->thick_start[i]) >= min_anchor && (uint32_t)(t->thick_end[i] - t->end[i]) >= min_anchor;
 }
 
-// The matrix's row and CSR arrays live in ONE block in this order, every array 16-byte aligned: finish writes the same image on the device and
-// copies it once.
-struct MatrixLayout { size_t total, row_begin, tid, start, end, ts, te, n_with, col, val, strand, bytes; };
-MatrixLayout matrix_layout(uint64_t n, uint64_t nnz) {
-    MatrixLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    L.total = take((size_t)n * 8); L.row_begin = take((size_t)(n + 1) * 8);
-    L.tid = take((size_t)n * 4); L.start = take((size_t)n * 4); L.end = take((size_t)n * 4); L.ts = take((size_t)n * 4); L.te = take((size_t)n * 4);
-    L.n_with = take((size_t)n * 4); L.col = take((size_t)nnz * 4); L.val = take((size_t)nnz * 4); L.strand = take((size_t)n + 1);
-    L.bytes = o;
-    return L;
-}
-struct MatrixBox { rgx_cohort_matrix m; void *block; size_t block_cap; bool pinned; };
+std::atomic<uint64_t> g_matrix_serial{0};
 
 rgx_cohort_matrix *matrix_alloc(const CohortContigs &c, const std::vector<std::string> &samples, uint64_t n, uint64_t nnz, bool pinned) {
     MatrixBox *box = (MatrixBox *)calloc(1, sizeof *box);
     if (!box) return nullptr;
     const MatrixLayout L = matrix_layout(n, nnz);
-    box->pinned = pinned;
+    box->pinned = pinned; box->serial = ++g_matrix_serial;
     box->block = block_take(L.bytes, box->block_cap, pinned);
     if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
     if (!box->block) { free(box); return nullptr; }
@@ -84,30 +39,7 @@ rgx_cohort_matrix *matrix_alloc(const CohortContigs &c, const std::vector<std::s
     return m;
 }
 
-constexpr uint64_t kMaxTriples = (1ull << 32) - (1ull << 16);        // (the sort's tiles round the count up inside 32 bits)
-constexpr uint32_t kMaxSamples = 1u << 24;                           // (a triple keeps its sample in 24 bits, beside the strand character)
-constexpr size_t kMaxBlocks = (size_t)1 << (32 - kCohortBlockLog2);
-
 }  // namespace
-
-struct rgx_cohort {
-    int device = 0;
-    rgx_cohort_params p{};
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_src = nullptr, ev_done = nullptr, ev_up = nullptr; bool up_pending = false;
-    CohortContigs contigs; std::vector<std::string> sample_names;
-    std::vector<uint32_t *> blocks = std::vector<uint32_t *>(kMaxBlocks, nullptr);   // (fixed size: copies to the device table read its elements in place)
-    size_t n_blocks = 0;
-    uint32_t **d_blocks = nullptr; uint32_t *d_fill = nullptr;
-    // a sample's tid map must outlive its append, which is only enqueued: maps stay until the cohort goes (most samples share the one before)
-    struct TidMap { std::vector<uint32_t> host; uint32_t *dev = nullptr; };
-    std::vector<std::unique_ptr<TidMap>> maps;
-    uint64_t n_triples = 0; uint32_t max_start = 0, max_end = 0;
-    int last_path = 0; double ms_add_total = 0;
-    void *pinned_up = nullptr; size_t pinned_up_cap = 0; bool pinned_up_locked = false;
-    DevBuf up, sort, rows, image;
-};
 
 // what rgx_cohort_finish's scans leave 16 words behind the append counter d_fill[0] (a block of 256 bytes): the distinct keys, and the rows and counts
 // the filters keep (read back by one copy)
@@ -145,6 +77,7 @@ extern "C" void rgx_cohort_destroy(rgx_cohort *co) {
     if (co->d_blocks) (void)hipFree(co->d_blocks);
     if (co->d_fill) (void)hipFree(co->d_fill);
     co->up.release(); co->sort.release(); co->rows.release(); co->image.release();
+    co->cl_in.release(); co->cl_rows.release(); co->cl_entries.release();
     if (co->pinned_up) { if (co->pinned_up_locked) (void)hipHostFree(co->pinned_up); else free(co->pinned_up); }
     if (co->ev_src) (void)hipEventDestroy(co->ev_src);
     if (co->ev_done) (void)hipEventDestroy(co->ev_done);
@@ -317,12 +250,11 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         Uk = kept.rows; NNZ = kept.nnz;
         mark("reduce + filters");
         const MatrixLayout L = matrix_layout(Uk, NNZ);
+        co->image_serial = 0;                                            // (the image is about to be rewritten)
         if (co->image.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory for the cohort matrix (%u rows, %u counts)\n", Uk, NNZ); }
         uint8_t *b = co->image.as<uint8_t>();
-        CohortImage o; o.total = (unsigned long long *)(b + L.total); o.row_begin = (unsigned long long *)(b + L.row_begin); o.tid = (uint32_t *)(b + L.tid);
-        o.start = (uint32_t *)(b + L.start); o.end = (uint32_t *)(b + L.end); o.ts = (uint32_t *)(b + L.ts); o.te = (uint32_t *)(b + L.te);
-        o.n_with = (uint32_t *)(b + L.n_with); o.col_sample = (uint32_t *)(b + L.col); o.val_count = (uint32_t *)(b + L.val); o.strand = b + L.strand;
+        const CohortImage o = image_at(b, L);
         launch_cohort_out(s, head, seg, row_start, r, out_row, nnz_excl, N, U, NNZ, o, st);
         m = matrix_alloc(co->contigs, co->sample_names, Uk, NNZ, /*pinned=*/true);
         if (!m) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the cohort matrix\n"); }
@@ -330,10 +262,12 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
         if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
         if (e_ != hipSuccess) { rgx_cohort_matrix_free(m); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s finishing the cohort\n", hipGetErrorString(e_)); }
+        co->image_serial = ((MatrixBox *)m)->serial;
         mark("rows out + copy");
     } else {
         m = matrix_alloc(co->contigs, co->sample_names, 0, 0, false);
         if (!m) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the cohort matrix\n");
+        co->image_serial = ((MatrixBox *)m)->serial;                     // (no rows: nothing of it needs to be in HBM)
     }
     m->n_triples = N; m->ms_add_total = co->ms_add_total; m->ms_finish = now_ms() - t0;
     *out = m;

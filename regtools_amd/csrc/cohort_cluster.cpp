@@ -1,0 +1,345 @@
+// cohort_cluster.cpp -- the intron clusters of a cohort matrix: rgx_cohort_cluster (device), its host twin rgx_cohort_cluster_host and the
+// perind.counts-style text (contract in include/regtools_amd.h; the reference has no counterpart).  Device side: cluster_kernels.hip.
+//   rows -> two stable sorts by (tid, class, start) / (tid, class, end) -> edges between neighbours on a site -> components (hook + jump rounds,
+//   components_run) -> rows and reads per root (integer atomics), filters, scan = cluster numbers -> stable sort by cluster = cl_row
+//   -> the clustered rows' count entries as (cluster, sample, count) -> stable sort by sample, then cluster -> heads, scan, one sum per run = cs_*
+#include "cohort_internal.h"
+
+namespace {
+
+struct ClustersLayout { size_t cluster, cl_begin, cl_row, cl_total, cs_begin, cs_sample, cs_total, bytes; };
+ClustersLayout clusters_layout(uint64_t n, uint64_t n_clusters, uint64_t n_kept, uint64_t n_cs) {
+    ClustersLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    L.cl_begin = take((size_t)(n_clusters + 1) * 8); L.cl_total = take((size_t)n_clusters * 8); L.cs_begin = take((size_t)(n_clusters + 1) * 8);
+    L.cs_total = take((size_t)n_cs * 8); L.cluster = take((size_t)n * 4); L.cl_row = take((size_t)n_kept * 4); L.cs_sample = take((size_t)n_cs * 4);
+    L.bytes = o + 16;
+    return L;
+}
+struct ClustersBox { rgx_cohort_clusters c; void *block; size_t block_cap; bool pinned; };
+
+rgx_cohort_clusters *clusters_alloc(uint64_t n, uint64_t n_clusters, uint64_t n_kept, uint64_t n_cs, bool pinned) {
+    ClustersBox *box = (ClustersBox *)calloc(1, sizeof *box);
+    if (!box) return nullptr;
+    const ClustersLayout L = clusters_layout(n, n_clusters, n_kept, n_cs);
+    box->pinned = pinned;
+    box->block = block_take(L.bytes, box->block_cap, pinned);
+    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
+    if (!box->block) { free(box); return nullptr; }
+    uint8_t *q = (uint8_t *)box->block;
+    rgx_cohort_clusters *c = &box->c;
+    c->n_rows = n; c->n_clusters = n_clusters;
+    c->cluster = (uint32_t *)(q + L.cluster); c->cl_begin = (uint64_t *)(q + L.cl_begin); c->cl_row = (uint32_t *)(q + L.cl_row);
+    c->cl_total = (uint64_t *)(q + L.cl_total); c->cs_begin = (uint64_t *)(q + L.cs_begin); c->cs_sample = (uint32_t *)(q + L.cs_sample);
+    c->cs_total = (uint64_t *)(q + L.cs_total);
+    c->cl_begin[0] = 0; c->cs_begin[0] = 0;
+    return c;
+}
+
+constexpr uint64_t kMaxClusterItems = (1ull << 32) - (1ull << 16);   // (rows, and count entries: the sort's tiles round the count up inside 32 bits)
+
+int check_limits(const rgx_cohort_matrix *m, char *err, size_t errlen) {
+    if (m->n > kMaxClusterItems || m->row_begin[m->n] > kMaxClusterItems) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: clustering takes at most %llu rows and %llu counts; the matrix has %llu and %llu\n", (unsigned long long)kMaxClusterItems,
+        (unsigned long long)kMaxClusterItems, (unsigned long long)m->n, (unsigned long long)m->row_begin[m->n]);
+    return RGX_OK;
+}
+
+inline uint32_t class_of(char c) { return c == '+' ? 0u : c == '-' ? 1u : 2u; }
+
+// what the scans leave at the front of the row workspace (read back by one copy each time the host needs a size)
+struct ClusterScalars { uint32_t flags[kCcBatch]; uint32_t n_components, n_clusters, n_kept, n_entries, n_cs; };
+
+}  // namespace
+
+int components_run(uint32_t n_vertices, const EdgeList *lists, int n_lists, uint32_t *parent, uint32_t *d_flags, hipStream_t st, uint32_t *n_rounds,
+                   char *err, size_t errlen) {
+    uint32_t rounds = 0;
+    launch_cc_init(parent, n_vertices, st);
+    for (bool done = n_vertices == 0; !done;) {
+        HIP_TRY(hipMemsetAsync(d_flags, 0, kCcBatch * 4, st));
+        for (uint32_t k = 0; k < kCcBatch; ++k) {
+            for (int l = 0; l < n_lists; ++l) launch_cc_hook(parent, lists[l].a, lists[l].b, lists[l].n, n_vertices, d_flags + k, st);
+            launch_cc_jump(parent, n_vertices, d_flags + k, st);
+        }
+        uint32_t h[kCcBatch];
+        HIP_TRY(hipMemcpyAsync(h, d_flags, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < kCcBatch && !done; ++k) { ++rounds; done = h[k] == 0; }
+        // (every round that changes something lowers a label: far fewer than one round per vertex, whatever the graph)
+        if (!done && rounds > n_vertices + kCcBatch) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the component search did not settle in %u rounds\n", rounds);
+    }
+    if (n_rounds) *n_rounds = rounds;
+    return RGX_OK;
+}
+
+extern "C" void rgx_cluster_params_default(rgx_cluster_params *p) { if (p) { p->min_rows = 1; p->min_total = 0; } }
+
+extern "C" int rgx_cohort_cluster_path(rgx_cohort *co) { return co ? co->cluster_path : 0; }
+
+extern "C" void rgx_cohort_clusters_free(rgx_cohort_clusters *cl) {
+    if (!cl) return;
+    ClustersBox *box = (ClustersBox *)cl;                             // cl is the first member
+    block_give(box->block, box->block_cap, box->pinned);
+    free(box);
+}
+
+extern "C" int rgx_cohort_cluster(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_cluster_params *p, rgx_cohort_clusters **out, char *err,
+                                  size_t errlen) {
+    if (!co || !m || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_cluster needs a cohort and a matrix\n");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(co->mu);
+    const double t0 = now_ms();
+    rgx_cluster_params prm; if (p) prm = *p; else rgx_cluster_params_default(&prm);
+    const int rc_lim = check_limits(m, err, errlen);
+    if (rc_lim != RGX_OK) return rc_lim;
+    const bool in_hbm = ((const MatrixBox *)m)->serial == co->image_serial;          // m is the first member of its box
+    co->cluster_path = in_hbm ? 1 : 0;
+    const uint32_t n = (uint32_t)m->n, nnz = (uint32_t)m->row_begin[m->n];
+    if (!n) {
+        rgx_cohort_clusters *c = clusters_alloc(0, 0, 0, 0, false);
+        if (!c) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the clusters\n");
+        c->n_rounds = 0; c->n_components = 0; c->ms_cluster = now_ms() - t0;
+        *out = c;
+        return RGX_OK;
+    }
+    HIP_ENTER(co->device);
+    hipStream_t st = co->stream;
+    const bool trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+    double t_last = t0;
+    auto mark = [&](const char *what) { if (trace) { (void)hipStreamSynchronize(st); const double t = now_ms(); fprintf(stderr,
+        "[rgx trace] cluster: %-28s +%8.3f ms\n", what, t - t_last); t_last = t; } };
+    // the pass counts come from the data
+    uint32_t max_start = 0, max_end = 0, max_tid = 0;
+    for (uint32_t i = 0; i < n; ++i) { max_start = std::max(max_start, m->start[i]); max_end = std::max(max_end, m->end[i]); max_tid = std::max(max_tid, m->tid[i]); }
+    const MatrixLayout L = matrix_layout(n, nnz);
+    uint8_t *base = co->image.as<uint8_t>();
+    if (!in_hbm) {
+        // the columns needed, where the image has them: total, row_begin, tid, start, end in front of the thick bounds; col_sample, val_count, strand behind n_with
+        if (co->cl_in.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
+            "regtools_amd: no device memory to upload the matrix (%u rows, %u counts)\n", n, nnz); }
+        base = co->cl_in.as<uint8_t>();
+        const uint8_t *h = (const uint8_t *)m->total - L.total;
+        HIP_TRY(hipMemcpyAsync(base, h, L.ts, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + L.col, h + L.col, L.strand + n - L.col, hipMemcpyHostToDevice, st));
+    }
+    const CohortImage in = image_at(base, L);
+    mark("matrix in HBM");
+
+    const size_t Nn = (size_t)n + 64;
+    const size_t tmp_words = radix_tmp_words(n) + scan_tmp_words(n) + 64;
+    if (co->cl_rows.ensure((Nn * (8 + 13) + 8 + 64 + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
+        "regtools_amd: no device memory to cluster %u rows\n", n); }
+    Carve w(co->cl_rows);
+    unsigned long long *tot = (unsigned long long *)w.u64(Nn), *cl_total = (unsigned long long *)w.u64(Nn), *o_cl_begin = (unsigned long long *)w.u64(Nn + 1),
+                       *o_cs_begin = (unsigned long long *)w.u64(Nn + 1);
+    ClusterScalars *d_sc = (ClusterScalars *)w.u32(64);
+    uint32_t *parent = w.u32(Nn), *ea0 = w.u32(Nn), *eb0 = w.u32(Nn), *ea1 = w.u32(Nn), *eb1 = w.u32(Nn), *perm0 = w.u32(Nn), *perm1 = w.u32(Nn),
+             *key0 = w.u32(Nn), *key1 = w.u32(Nn), *cls = w.u32(Nn), *cluster = w.u32(Nn), *cl_count = w.u32(Nn), *tmp = w.u32(tmp_words);
+    CARVE_TRY(w, "cluster rows");
+
+    // 1. edges: neighbours in the stable order of (tid, class, start), then of (tid, class, end)
+    launch_cluster_class(in.strand, n, cls, st);
+    const uint32_t tid_bits = std::max<uint32_t>(1, bitlen(max_tid));
+    RadixSort by_site{{perm0, perm1}, tmp, n, st, {key0, key1}};
+    by_site.by_keyed(in.start, std::max<uint32_t>(1, bitlen(max_start))); by_site.by_keyed(cls, 2); by_site.by_keyed(in.tid, tid_bits);
+    launch_cluster_edges(by_site.sorted(), in.tid, cls, in.start, n, ea0, eb0, st);
+    by_site.reset();
+    by_site.by_keyed(in.end, std::max<uint32_t>(1, bitlen(max_end))); by_site.by_keyed(cls, 2); by_site.by_keyed(in.tid, tid_bits);
+    launch_cluster_edges(by_site.sorted(), in.tid, cls, in.end, n, ea1, eb1, st);
+    mark("site sorts + edges");
+
+    // 2. components: parent[i] = the smallest row of i's component
+    const EdgeList lists[2] = {{ea0, eb0, n}, {ea1, eb1, n}};
+    uint32_t n_rounds = 0;
+    const int rc_cc = components_run(n, lists, 2, parent, d_sc->flags, st, &n_rounds, err, errlen);
+    if (rc_cc != RGX_OK) return rc_cc;
+    mark("components");
+
+    // 3. clusters (the edge arrays are free from here on)
+    uint32_t *cnt = ea0, *keep = eb0, *cid_excl = ea1, *sort_key = eb1, *is_root = cls;
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)n * 4, st));
+    HIP_TRY(hipMemsetAsync(tot, 0, (size_t)n * 8, st));
+    launch_cluster_tally(parent, in.total, n, cnt, tot, st);
+    launch_cluster_roots(parent, cnt, tot, n, prm.min_rows, prm.min_total, is_root, keep, st);
+    launch_scan_u32(keep, cid_excl, n, &d_sc->n_clusters, tmp, st);
+    launch_scan_u32(is_root, key0, n, &d_sc->n_components, tmp, st);
+    ClusterScalars sc;
+    HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t C = sc.n_clusters, n_components = sc.n_components;
+    launch_cluster_assign(parent, keep, cid_excl, cnt, tot, n, C, cluster, sort_key, cl_count, cl_total, st);
+    uint32_t *cl_begin32 = cnt;                                          // (assign was the last reader of cnt, keep and cid_excl)
+    launch_scan_u32(cl_count, cl_begin32, C, &d_sc->n_kept, tmp, st);
+    launch_cluster_widen(cl_begin32, C, &d_sc->n_kept, o_cl_begin, st);
+    RadixSort by_cluster{{perm0, perm1}, tmp, n, st, {key0, key1}};
+    by_cluster.by_keyed(sort_key, std::max<uint32_t>(1, bitlen(C)));    // (dropped rows carry C: behind every cluster)
+    const uint32_t *cl_row = by_cluster.sorted();
+    // 4. denominators: the entries of clustered rows that are not zero, as (cluster, sample, count)
+    const bool wave_per_row = (uint64_t)n * 32 <= nnz;
+    uint32_t *len = keep, *ent_off = cid_excl;
+    launch_cluster_row_len(cluster, in.row_begin, in.val_count, n, wave_per_row, len, st);
+    launch_scan_u32(len, ent_off, n, &d_sc->n_entries, tmp, st);
+    HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t n_kept = sc.n_kept, M = sc.n_entries;
+    mark("clusters + cl_row");
+
+    uint32_t n_cs = 0;
+    const uint32_t *cs_sample = nullptr; const unsigned long long *cs_total = nullptr;
+    if (M) {
+        const size_t Mn = (size_t)M + 64;
+        const size_t etmp_words = radix_tmp_words(M) + scan_tmp_words(M) + 64;
+        if (co->cl_entries.ensure((Mn * (2 + 7) + etmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
+            "regtools_amd: no device memory for the clusters' %u counts\n", M); }
+        Carve q(co->cl_entries);
+        unsigned long long *sums = (unsigned long long *)q.u64(Mn);
+        uint32_t *e_cluster = q.u32(Mn), *e_sample = q.u32(Mn), *e_count = q.u32(Mn), *eperm0 = q.u32(Mn), *eperm1 = q.u32(Mn), *ekey0 = q.u32(Mn),
+                 *ekey1 = q.u32(Mn), *etmp = q.u32(etmp_words);
+        CARVE_TRY(q, "cluster entries");
+        launch_cluster_expand(cluster, in.row_begin, in.col_sample, in.val_count, ent_off, n, wave_per_row, e_cluster, e_sample, e_count, st);
+        // stable LSD sort by (cluster, sample): the entries of one pair end up side by side
+        RadixSort by_pair{{eperm0, eperm1}, etmp, M, st, {ekey0, ekey1}};
+        by_pair.by_keyed(e_sample, std::max<uint32_t>(1, bitlen(std::max<uint32_t>(m->n_samples, 1) - 1)));
+        by_pair.by_keyed(e_cluster, std::max<uint32_t>(1, bitlen(C - 1)));
+        mark("entries + pair sort");
+        uint32_t *head = ekey0, *seg = ekey1, *seg_start = by_pair.spare();
+        launch_cluster_cs_heads(by_pair.sorted(), e_cluster, e_sample, M, head, st);
+        launch_scan_u32(head, seg, M, &d_sc->n_cs, etmp, st);
+        launch_cohort_row_start(head, seg, M, seg_start, st);
+        HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_cs = sc.n_cs;
+        uint32_t *seg_cluster = head, *samples = seg;                   // (the heads and their scan are used up)
+        launch_cluster_cs_sum(by_pair.sorted(), e_cluster, e_sample, e_count, seg_start, M, n_cs, seg_cluster, samples, sums, st);
+        launch_cluster_cs_begin(seg_cluster, n_cs, C, o_cs_begin, st);
+        cs_sample = samples; cs_total = sums;
+    } else launch_cluster_cs_begin(nullptr, 0, C, o_cs_begin, st);
+    mark("heads + sums");
+
+    rgx_cohort_clusters *c = clusters_alloc(n, C, n_kept, n_cs, /*pinned=*/true);
+    if (!c) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the clusters\n"); }
+    hipError_t e_ = hipMemcpyAsync(c->cluster, cluster, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess) e_ = hipMemcpyAsync(c->cl_begin, o_cl_begin, ((size_t)C + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess) e_ = hipMemcpyAsync(c->cs_begin, o_cs_begin, ((size_t)C + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess && C) e_ = hipMemcpyAsync(c->cl_total, cl_total, (size_t)C * 8, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess && n_kept) e_ = hipMemcpyAsync(c->cl_row, cl_row, (size_t)n_kept * 4, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess && n_cs) e_ = hipMemcpyAsync(c->cs_sample, cs_sample, (size_t)n_cs * 4, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess && n_cs) e_ = hipMemcpyAsync(c->cs_total, cs_total, (size_t)n_cs * 8, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
+    if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+    if (e_ != hipSuccess) { rgx_cohort_clusters_free(c); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s clustering the cohort\n", hipGetErrorString(e_)); }
+    mark("copy");
+    c->n_rounds = n_rounds; c->n_components = n_components; c->ms_cluster = now_ms() - t0;
+    *out = c;
+    return RGX_OK;
+}
+
+// ---- the host twin: the same contract in plain C++ (std::sort for the site groups, union-find, one pass per cluster) --------------------------
+extern "C" int rgx_cohort_cluster_host(const rgx_cohort_matrix *m, const rgx_cluster_params *p, rgx_cohort_clusters **out, char *err, size_t errlen) {
+    if (!m || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_cluster_host needs a matrix\n");
+    *out = nullptr;
+    const double t0 = now_ms();
+    rgx_cluster_params prm; if (p) prm = *p; else rgx_cluster_params_default(&prm);
+    const int rc_lim = check_limits(m, err, errlen);
+    if (rc_lim != RGX_OK) return rc_lim;
+    const uint32_t n = (uint32_t)m->n;
+    std::vector<uint32_t> parent(n), order(n);
+    for (uint32_t i = 0; i < n; ++i) parent[i] = order[i] = i;
+    auto find = [&](uint32_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
+    auto unite = [&](uint32_t a, uint32_t b) { a = find(a); b = find(b); if (a != b) parent[std::max(a, b)] = std::min(a, b); };   // (the root is the lowest row)
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t *site = side ? m->end : m->start;
+        auto same = [&](uint32_t a, uint32_t b) { return m->tid[a] == m->tid[b] && class_of(m->strand[a]) == class_of(m->strand[b]) && site[a] == site[b]; };
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            if (m->tid[a] != m->tid[b]) return m->tid[a] < m->tid[b];
+            const uint32_t ca = class_of(m->strand[a]), cb = class_of(m->strand[b]);
+            if (ca != cb) return ca < cb;
+            if (site[a] != site[b]) return site[a] < site[b];
+            return a < b;
+        });
+        for (uint32_t i = 1; i < n; ++i) if (same(order[i - 1], order[i])) unite(order[i - 1], order[i]);
+    }
+    std::vector<uint32_t> rows_of(n, 0), cid(n, RGX_NO_CLUSTER);
+    std::vector<uint64_t> total_of(n, 0);
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t r = find(i); ++rows_of[r]; total_of[r] += m->total[i]; }
+    uint64_t n_components = 0, C = 0, n_kept = 0;
+    for (uint32_t i = 0; i < n; ++i) if (parent[i] == i) {
+        ++n_components;
+        if (rows_of[i] >= prm.min_rows && total_of[i] >= prm.min_total) { cid[i] = (uint32_t)C++; n_kept += rows_of[i]; }
+    }
+    // the member rows, ascending within a cluster
+    std::vector<uint64_t> begin(C + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) if (parent[i] == i && cid[i] != RGX_NO_CLUSTER) begin[cid[i] + 1] = rows_of[i];
+    for (uint64_t k = 0; k < C; ++k) begin[k + 1] += begin[k];
+    std::vector<uint32_t> members(n_kept);
+    { std::vector<uint64_t> at(begin.begin(), begin.end() - 1);
+      for (uint32_t i = 0; i < n; ++i) { const uint32_t k = cid[find(i)]; if (k != RGX_NO_CLUSTER) members[at[k]++] = i; } }
+    // per cluster and sample: a dense accumulator and the list of the samples touched
+    std::vector<uint64_t> acc(std::max<uint32_t>(m->n_samples, 1), 0), cs_begin(C + 1, 0), cs_total;
+    std::vector<uint32_t> touched, cs_sample;
+    for (uint64_t k = 0; k < C; ++k) {
+        touched.clear();
+        for (uint64_t q = begin[k]; q < begin[k + 1]; ++q) {
+            const uint32_t r = members[q];
+            for (uint64_t e = m->row_begin[r]; e < m->row_begin[r + 1]; ++e) {
+                const uint32_t s = m->col_sample[e];
+                if (!m->val_count[e] || s >= acc.size()) continue;
+                if (!acc[s]) touched.push_back(s);
+                acc[s] += m->val_count[e];
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        for (uint32_t s : touched) { cs_sample.push_back(s); cs_total.push_back(acc[s]); acc[s] = 0; }
+        cs_begin[k + 1] = cs_sample.size();
+    }
+    rgx_cohort_clusters *c = clusters_alloc(n, C, n_kept, cs_sample.size(), false);
+    if (!c) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the clusters\n");
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t r = find(i);
+        c->cluster[i] = cid[r];
+        if (r == i && cid[i] != RGX_NO_CLUSTER) c->cl_total[cid[i]] = total_of[i];
+    }
+    memcpy(c->cl_begin, begin.data(), (C + 1) * 8); memcpy(c->cs_begin, cs_begin.data(), (C + 1) * 8);
+    if (n_kept) memcpy(c->cl_row, members.data(), n_kept * 4);
+    if (!cs_sample.empty()) { memcpy(c->cs_sample, cs_sample.data(), cs_sample.size() * 4); memcpy(c->cs_total, cs_total.data(), cs_total.size() * 8); }
+    c->n_rounds = 0; c->n_components = n_components; c->ms_cluster = now_ms() - t0;
+    *out = c;
+    return RGX_OK;
+}
+
+// ---- text ------------------------------------------------------------------------------------------------------------------------------
+extern "C" size_t rgx_cohort_format_cluster_counts(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, char *buf, size_t cap) {
+    if (!m || !cl || cl->n_rows != m->n) return 0;
+    // one pass to size the text, a second one to write it when it fits (rgx_cohort_format_counts)
+    auto run = [&](char *dst) {
+        size_t need = 0;
+        auto put = [&](const char *s, size_t k) { if (dst) memcpy(dst + need, s, k); need += k; };
+        put("chrom", 5);
+        for (uint32_t g = 0; g < m->n_samples; ++g) { put(" ", 1); put(m->sample_name[g], strlen(m->sample_name[g])); }
+        put("\n", 1);
+        char num[96];
+        for (uint64_t i = 0; i < m->n; ++i) {
+            const uint32_t c = cl->cluster[i];
+            if (c == RGX_NO_CLUSTER) continue;
+            put(m->ref_name[m->tid[i]], strlen(m->ref_name[m->tid[i]]));
+            const uint32_t k = class_of(m->strand[i]);
+            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s", m->start[i], m->end[i], (unsigned long long)c + 1, k == 0 ? "+" : k == 1 ? "-" : "NA"));
+            uint64_t e = m->row_begin[i], d = cl->cs_begin[c];
+            const uint64_t e_end = m->row_begin[i + 1], d_end = cl->cs_begin[c + 1];
+            for (uint32_t g = 0; g < m->n_samples; ++g) {
+                uint32_t a = 0; uint64_t b = 0;
+                if (e < e_end && m->col_sample[e] == g) a = m->val_count[e++];
+                if (d < d_end && cl->cs_sample[d] == g) b = cl->cs_total[d++];
+                char *t = num; *t++ = ' ';
+                t = std::to_chars(t, num + sizeof num, a).ptr; *t++ = '/'; t = std::to_chars(t, num + sizeof num, b).ptr;
+                put(num, (size_t)(t - num));
+            }
+            put("\n", 1);
+        }
+        return need;
+    };
+    const size_t need = run(nullptr);
+    if (buf && need <= cap) run(buf);
+    return need;
+}

@@ -1,0 +1,85 @@
+// cohort_internal.h -- what cohort.cpp (the matrix) and cohort_cluster.cpp (the intron clusters of a matrix) share: the cohort itself, the layout of
+// a matrix's block and the box a matrix lives in.
+#pragma once
+#include "api_internal.h"
+
+// The cohort's contig table: the samples' header names in order of first appearance.
+struct CohortContigs {
+    std::vector<std::string> names; std::vector<uint32_t> lens, first_sample;
+    std::unordered_map<std::string, uint32_t> index;
+    // map[tid of t] = cohort tid.  A name that is already there with another length changes nothing and is an error.
+    int map_sample(const rgx_junction_table *t, uint32_t sample, const char *sample_name, const std::vector<std::string> &sample_names,
+                   std::vector<uint32_t> &map, char *err, size_t errlen) {
+        std::unordered_map<std::string, uint32_t> own;                       // (a header may list a name twice)
+        for (int32_t i = 0; i < t->n_ref; ++i) {
+            const std::string nm = t->ref_name[i];
+            auto it = index.find(nm);
+            if (it != index.end() && lens[it->second] != t->ref_len[i]) return fail(err, errlen, RGX_ERR_ARG,
+                "regtools_amd: contig %s is %u long in sample %s and %u in sample %s\n", nm.c_str(), lens[it->second],
+                sample_names[first_sample[it->second]].c_str(), t->ref_len[i], sample_name);
+            auto o = own.find(nm);
+            if (o != own.end() && o->second != t->ref_len[i]) return fail(err, errlen, RGX_ERR_ARG,
+                "regtools_amd: contig %s is %u long in sample %s and %u in sample %s\n", nm.c_str(), o->second, sample_name, t->ref_len[i], sample_name);
+            own[nm] = t->ref_len[i];
+        }
+        map.resize((size_t)std::max<int32_t>(t->n_ref, 0));
+        for (int32_t i = 0; i < t->n_ref; ++i) {
+            const std::string nm = t->ref_name[i];
+            auto it = index.find(nm);
+            if (it == index.end()) {
+                it = index.emplace(nm, (uint32_t)names.size()).first;
+                names.push_back(nm); lens.push_back(t->ref_len[i]); first_sample.push_back(sample);
+            }
+            map[(size_t)i] = it->second;
+        }
+        return RGX_OK;
+    }
+};
+
+// The matrix's row and CSR arrays live in ONE block in this order, every array 16-byte aligned: finish writes the same image on the device and
+// copies it once.
+struct MatrixLayout { size_t total, row_begin, tid, start, end, ts, te, n_with, col, val, strand, bytes; };
+inline MatrixLayout matrix_layout(uint64_t n, uint64_t nnz) {
+    MatrixLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    L.total = take((size_t)n * 8); L.row_begin = take((size_t)(n + 1) * 8);
+    L.tid = take((size_t)n * 4); L.start = take((size_t)n * 4); L.end = take((size_t)n * 4); L.ts = take((size_t)n * 4); L.te = take((size_t)n * 4);
+    L.n_with = take((size_t)n * 4); L.col = take((size_t)nnz * 4); L.val = take((size_t)nnz * 4); L.strand = take((size_t)n + 1);
+    L.bytes = o;
+    return L;
+}
+inline CohortImage image_at(uint8_t *b, const MatrixLayout &L) {
+    CohortImage o; o.total = (unsigned long long *)(b + L.total); o.row_begin = (unsigned long long *)(b + L.row_begin); o.tid = (uint32_t *)(b + L.tid);
+    o.start = (uint32_t *)(b + L.start); o.end = (uint32_t *)(b + L.end); o.ts = (uint32_t *)(b + L.ts); o.te = (uint32_t *)(b + L.te);
+    o.n_with = (uint32_t *)(b + L.n_with); o.col_sample = (uint32_t *)(b + L.col); o.val_count = (uint32_t *)(b + L.val); o.strand = b + L.strand;
+    return o;
+}
+// serial: every matrix the library hands out has its own (never 0); a cohort remembers that of the matrix whose image its last finish left in HBM
+struct MatrixBox { rgx_cohort_matrix m; void *block; size_t block_cap; bool pinned; uint64_t serial; };
+
+constexpr uint64_t kMaxTriples = (1ull << 32) - (1ull << 16);        // (the sort's tiles round the count up inside 32 bits)
+constexpr uint32_t kMaxSamples = 1u << 24;                           // (a triple keeps its sample in 24 bits, beside the strand character)
+constexpr size_t kMaxBlocks = (size_t)1 << (32 - kCohortBlockLog2);
+
+struct rgx_cohort {
+    int device = 0;
+    rgx_cohort_params p{};
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_src = nullptr, ev_done = nullptr, ev_up = nullptr; bool up_pending = false;
+    CohortContigs contigs; std::vector<std::string> sample_names;
+    std::vector<uint32_t *> blocks = std::vector<uint32_t *>(kMaxBlocks, nullptr);   // (fixed size: copies to the device table read its elements in place)
+    size_t n_blocks = 0;
+    uint32_t **d_blocks = nullptr; uint32_t *d_fill = nullptr;
+    // a sample's tid map must outlive its append, which is only enqueued: maps stay until the cohort goes (most samples share the one before)
+    struct TidMap { std::vector<uint32_t> host; uint32_t *dev = nullptr; };
+    std::vector<std::unique_ptr<TidMap>> maps;
+    uint64_t n_triples = 0; uint32_t max_start = 0, max_end = 0;
+    int last_path = 0; double ms_add_total = 0;
+    void *pinned_up = nullptr; size_t pinned_up_cap = 0; bool pinned_up_locked = false;
+    DevBuf up, sort, rows, image;
+    // rgx_cohort_cluster (cohort_cluster.cpp): the matrix whose image `image` holds (0: none), an uploaded matrix, the row and the entry workspace
+    uint64_t image_serial = 0;
+    int cluster_path = 0;
+    DevBuf cl_in, cl_rows, cl_entries;
+};

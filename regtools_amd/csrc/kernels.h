@@ -322,4 +322,35 @@ void launch_cohort_reduce(CohortSorted s, const uint32_t *row_start, uint32_t n,
 void launch_cohort_out(CohortSorted s, const uint32_t *head, const uint32_t *seg_excl, const uint32_t *row_start, CohortRows r, const uint32_t *out_row,
                        const uint32_t *nnz_excl, uint32_t n, uint32_t n_rows, uint32_t n_nnz_kept, CohortImage o, hipStream_t st);
 
+// ---- intron clusters of a cohort matrix (cluster_kernels.hip; host side in cohort_cluster.cpp) -------------------------------------------------
+void launch_cluster_class(const uint8_t *strand, uint32_t n, uint32_t *cls /* '+' 0, '-' 1, else 2 */, hipStream_t st);
+// perm = the rows in stable order of (tid, cls, site): (ea[i], eb[i]) = (perm[i - 1], perm[i]) where both lie on one site, a self loop otherwise
+void launch_cluster_edges(const uint32_t *perm, const uint32_t *tid, const uint32_t *cls, const uint32_t *site, uint32_t n, uint32_t *ea, uint32_t *eb,
+                          hipStream_t st);
+// The component search, a launch per step (components_run, cohort_cluster.cpp): parent[v] = v; hook the larger label of an edge's ends under
+// the smaller (atomicMin; ends at or above n_vertices are skipped); parent[v] = parent[parent[parent[v]]].  *flag |= 1 when a step changed a label.
+void launch_cc_init(uint32_t *parent, uint32_t n, hipStream_t st);
+void launch_cc_hook(uint32_t *parent, const uint32_t *a, const uint32_t *b, uint32_t n_edges, uint32_t n_vertices, uint32_t *flag, hipStream_t st);
+void launch_cc_jump(uint32_t *parent, uint32_t n, uint32_t *flag, hipStream_t st);
+// cnt[root] / tot[root] += 1 / total[i] (both zeroed by the caller); is_root, keep = root that passes the filters
+void launch_cluster_tally(const uint32_t *label, const unsigned long long *total, uint32_t n, uint32_t *cnt, unsigned long long *tot, hipStream_t st);
+void launch_cluster_roots(const uint32_t *label, const uint32_t *cnt, const unsigned long long *tot, uint32_t n, uint32_t min_rows, uint64_t min_total,
+                          uint32_t *is_root, uint32_t *keep, hipStream_t st);
+// cid_excl = exclusive scan of keep: cluster[i] (0xffffffff = dropped), sort_key[i] (dropped rows: n_clusters), and per kept cluster its rows and total
+void launch_cluster_assign(const uint32_t *label, const uint32_t *keep, const uint32_t *cid_excl, const uint32_t *cnt, const unsigned long long *tot,
+                           uint32_t n, uint32_t n_clusters, uint32_t *cluster, uint32_t *sort_key, uint32_t *cl_count, unsigned long long *cl_total,
+                           hipStream_t st);
+// out[k] = in[k] for k < n, out[n] = *last (device)
+void launch_cluster_widen(const uint32_t *in, uint32_t n, const uint32_t *last, unsigned long long *out /* n + 1 */, hipStream_t st);
+// the count entries of clustered rows that are not zero: len[row], then (cluster, sample, count) from ent_off[row] = exclusive scan of len on
+void launch_cluster_row_len(const uint32_t *cluster, const unsigned long long *row_begin, const uint32_t *val, uint32_t n, bool wave_per_row, uint32_t *len,
+                            hipStream_t st);
+void launch_cluster_expand(const uint32_t *cluster, const unsigned long long *row_begin, const uint32_t *col, const uint32_t *val, const uint32_t *ent_off,
+                           uint32_t n, bool wave_per_row, uint32_t *e_cluster, uint32_t *e_sample, uint32_t *e_count, hipStream_t st);
+// perm = the n entries in stable order of (cluster, sample): head flags, then one sum per run (seg_start as launch_cohort_row_start leaves it)
+void launch_cluster_cs_heads(const uint32_t *perm, const uint32_t *e_cluster, const uint32_t *e_sample, uint32_t n, uint32_t *head, hipStream_t st);
+void launch_cluster_cs_sum(const uint32_t *perm, const uint32_t *e_cluster, const uint32_t *e_sample, const uint32_t *e_count, const uint32_t *seg_start,
+                           uint32_t n, uint32_t n_seg, uint32_t *seg_cluster, uint32_t *cs_sample, unsigned long long *cs_total, hipStream_t st);
+void launch_cluster_cs_begin(const uint32_t *seg_cluster, uint32_t n_seg, uint32_t n_clusters, unsigned long long *cs_begin /* n_clusters + 1 */, hipStream_t st);
+
 }  // namespace rgx

@@ -7,6 +7,11 @@
   --part finish     rgx_cohort_finish (ms_finish) beside rgx_cohort_merge_host on the same rows, for every SAMPLESxROWS of --sizes; the matrices
                     are compared; bytes moved per triple (counted from the passes, see finish_bytes_per_triple) over ms_finish against 8 TB/s
 
+  --cluster         rgx_cohort_cluster (ms_cluster) on the matrix of the same SAMPLESxROWS cohorts: first and warm
+                    calls on both paths (the matrix still in HBM behind its finish; uploaded through a cohort that never saw it), beside
+                    rgx_cohort_cluster_host on the same matrix and the ms_finish of the same run; the results are compared word for word; bytes
+                    moved per count entry by step 4 (counted from the passes, see cluster_bytes_per_entry) over ms_cluster against 8 TB/s
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -117,6 +122,69 @@ def part_finish(a):
         print(json.dumps(line), flush=True)
 
 
+def cluster_bytes_per_entry(sample_bits, cluster_bits):
+    """HBM bytes per count entry that step 4 of rgx_cohort_cluster reads and writes: the row lengths (val_count, 4 in), the
+    expansion (col_sample + val_count in, three words out: 20), per key word of the pair sort its 8-bit passes (histogram read of the key 4 +
+    scatter of key and permutation in and out 16) and, for the second word, one gather (permutation 4 + word 4 in, 4 out), the head flags (two
+    permutation entries and their two words each: 24 in, 4 out), their scan (4 in twice, 4 out), the run starts (8 in) and the sums (permutation
+    and count: 8 in).  Per-row, per-run and per-cluster words and the copy to the host are not counted."""
+    passes = (sample_bits + 7) // 8 + (cluster_bits + 7) // 8
+    return 4 + 20 + passes * 20 + 12 + 28 + 12 + 8 + 8
+
+
+CLUSTER_ARRAYS = ("cluster", "cl_begin", "cl_row", "cl_total", "cs_begin", "cs_sample", "cs_total")
+
+
+def part_cluster(a):
+    import regtools_amd
+    from regtools_amd import _ffi, cohort
+    ctx = regtools_amd.Context(0)
+    for size in a.sizes.split(","):
+        shape, _, mix = size.partition(":")
+        mix = mix or "sparse"
+        n_samples, rows = [int(x) for x in shape.lower().split("x")]
+        rng = np.random.default_rng(3)
+        tables = [make_sample(g, rows, rng, mix) for g in range(n_samples)]
+        co = regtools_amd.Cohort(ctx=ctx)
+        for g, t in enumerate(tables):
+            co.add(Sample(t), "s%04d" % g)
+        for _ in range(2):                           # (the second finish is a warm one)
+            m = co.finish()
+        in_hbm, uploaded = [], []
+        for _ in range(a.reps):                      # (the first call grows the cohort's workspace and the page-locked result block)
+            cl = co.cluster(m)
+            in_hbm.append(round(cl.ms_cluster, 3))
+        other = regtools_amd.Cohort(ctx=ctx)
+        for _ in range(a.reps):
+            up = other.cluster(m)
+            uploaded.append(round(up.ms_cluster, 3))
+        assert co.cluster_paths == [1] * a.reps and other.cluster_paths == [0] * a.reps
+        entries = int(m.row_begin[-1])
+        sizes = np.diff(cl.cl_begin)
+        bpe = cluster_bytes_per_entry(max(1, (n_samples - 1).bit_length()), max(1, (cl.n_clusters - 1).bit_length()))
+        best = min(in_hbm[1:] or in_hbm)
+        line = {"part": "cluster", "mix": mix, "samples": n_samples, "rows_per_sample": rows, "rows": m.n, "count_entries": entries,
+                "components": cl.n_components, "clusters": cl.n_clusters, "largest_cluster_rows": int(sizes.max()), "singletons": int((sizes == 1).sum()),
+                "cluster_sample_pairs": int(cl.cs_begin[-1]), "n_rounds": cl.n_rounds, "ms_finish_same_run": round(m.ms_finish, 3),
+                "ms_cluster_in_hbm": in_hbm, "ms_cluster_uploaded": uploaded, "ms_cluster_best_warm": best,
+                "paths_equal": bool(all(np.array_equal(getattr(cl, k), getattr(up, k)) for k in CLUSTER_ARRAYS)),
+                "step4_bytes_per_entry_counted": bpe, "step4_TBps_over_ms_cluster": round(bpe * entries / best / 1e9, 3),
+                "share_of_8TBps": round(bpe * entries / best / 1e9 / 8.0, 4)}
+        assert line["paths_equal"], "the two paths differ"
+        if not a.no_host:
+            h = cohort.cluster_host(m)
+            line["ms_cluster_host"] = round(h.ms_cluster, 1)
+            line["device_over_host"] = round(h.ms_cluster / best, 1)
+            same = (cl.n_clusters, cl.n_components) == (h.n_clusters, h.n_components) and all(np.array_equal(getattr(cl, k), getattr(h, k)) for k in CLUSTER_ARRAYS)
+            line["identical_to_host"] = bool(same)
+            assert same, "the device clusters differ from the host twin's"
+            h.close()
+        cl.close(); up.close(); m.close(); co.close(); other.close()
+        for t in tables:
+            _ffi.lib().rgx_table_free(t)
+        print(json.dumps(line), flush=True)
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -170,12 +238,15 @@ def part_pipeline(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", default="all", choices=["all", "pipeline", "finish"])
+    ap.add_argument("--cluster", action="store_true", help="the cluster part, alone")
     ap.add_argument("--reads", type=int, default=50_000_000)
     ap.add_argument("--files", type=int, default=24)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="64x100000:sparse,512x300000:shared", help="SAMPLESxROWS[:sparse|shared], comma separated")
-    ap.add_argument("--no-host", action="store_true", help="skip rgx_cohort_merge_host (profiling runs)")
+    ap.add_argument("--no-host", action="store_true", help="skip rgx_cohort_merge_host / rgx_cohort_cluster_host (profiling runs)")
     a = ap.parse_args()
+    if a.cluster:
+        return part_cluster(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
