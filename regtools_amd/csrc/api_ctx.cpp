@@ -60,7 +60,7 @@ extern "C" int rgx_ctx_create(int device, rgx_ctx **out, char *err, size_t errle
     c->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     { const char *e = getenv("REGTOOLS_AMD_ONE_SHOT"); c->one_shot = e && strcmp(e, "0") != 0; }
-    c->buf("arena").piece = arena_knobs().piece;                     // (DevBuf::map_pieces: what the DEFLATE launch writes into)
+    c->buf(Buf::arena).piece = arena_knobs().piece;                     // (DevBuf::map_pieces: what the DEFLATE launch writes into)
     for (auto &e : c->ev) HIP_TRY(hipEventCreate(&e));
     for (auto &e : c->ev_launch) HIP_TRY(hipEventCreate(&e));
     for (auto &e : c->ev_trial) HIP_TRY(hipEventCreate(&e));
@@ -117,7 +117,7 @@ extern "C" void rgx_ctx_destroy(rgx_ctx *c) {
     if (!c) return;
     Reaper::get().drain();                                  // (deferred teardown of finished calls may still hold memory of this device)
     (void)hipSetDevice(c->device);
-    for (auto &kv : c->bufs) kv.second.release();
+    for (DevBuf &b : c->bufs) b.release();                  // (in enum order; the order carries no meaning: a kept address range is never freed)
     if (c->arena_retired) { c->arena_retired->release(); delete c->arena_retired; }
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_launch) if (e) (void)hipEventDestroy(e);

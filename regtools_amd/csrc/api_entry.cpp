@@ -327,10 +327,10 @@ int rgx_last_table_pack_async(rgx_ctx *c, const rgx_junction_table *t, void **d_
     if (!c->last_rows_valid || t->n != c->last_rows || t->n_records != c->last_records || t->n_events != c->last_events || t->inflated_bytes != c->last_bytes)
         return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the table is not the result of the last extraction on this context\n");
     HIP_ENTER(c->device);
-    DevBuf &b = c->buf("rows_packed");
+    DevBuf &b = c->buf(Buf::rows_packed);
     HIP_TRY(b.ensure((size_t)std::max<uint64_t>(1, t->n) * RGX_PACKED_ROW_BYTES));
     if (!c->ev_packed) HIP_TRY(hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming));
-    if (t->n) launch_cols_to_packed(c->buf("rows_out").as<uint32_t>(), (uint32_t)t->n, b.as<uint32_t>(), c->stream);
+    if (t->n) launch_cols_to_packed(c->buf(Buf::rows_out).as<uint32_t>(), (uint32_t)t->n, b.as<uint32_t>(), c->stream);
     HIP_TRY(hipEventRecord(c->ev_packed, c->stream));
     *d_packed = b.p; *done = c->ev_packed;
     return RGX_OK;
@@ -345,7 +345,7 @@ extern "C" int rgx_last_table_pack_device(rgx_ctx *c, const rgx_junction_table *
     if (!d_dst || cap_rows < t->n) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: destination holds %llu rows, %llu needed\n",
         (unsigned long long)cap_rows, (unsigned long long)t->n);
     HIP_ENTER(c->device);
-    launch_cols_to_packed(c->buf("rows_out").as<uint32_t>(), (uint32_t)t->n, (uint32_t *)d_dst, c->stream);
+    launch_cols_to_packed(c->buf(Buf::rows_out).as<uint32_t>(), (uint32_t)t->n, (uint32_t *)d_dst, c->stream);
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RGX_OK;
 }
@@ -379,7 +379,7 @@ extern "C" int rgx_table_merge_device(rgx_ctx *c, const void *d_rows, uint64_t s
     chrom_string_ranks(h, rank_of_tid);
     uint32_t rk = 0; for (uint32_t r : rank_of_tid) rk = std::max(rk, r);
 
-    DevBuf &b = c->buf("merge"), &sc = c->buf("scalars");
+    DevBuf &b = c->buf(Buf::merge), &sc = c->buf(Buf::scalars);
     HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t Nn = N, P = (size_t)n_parts, R = rank_of_tid.size();
     const size_t tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;

@@ -43,7 +43,7 @@ int EventsRun::calibrate_arena() {
     static std::mutex trial_mu[16];
     std::lock_guard<std::mutex> trial_lock(trial_mu[(unsigned)c->device % 16u]);
     if (!inflate_takes_coop(n_range) || h_sc->inflate.first_bad != 0xffffffffu) return RGX_OK;
-    DevBuf &b_arena = c->buf("arena"), &b_lens = c->buf("inflate_scratch");
+    DevBuf &b_arena = c->buf(Buf::arena), &b_lens = c->buf(Buf::inflate_scratch);
     if (!b_arena.p || b_arena.cap < total + 256) return RGX_OK;
     auto room_for_one = [&] {                                  // (a challenger AND what the call -- or a co-tenant of the device -- may still allocate)
         size_t free_b = 0, total_b = 0;
@@ -84,20 +84,21 @@ int EventsRun::calibrate_arena() {
         float ms = 0;
         if (time_into(cand.as<uint8_t>(), ms) != hipSuccess) { (void)hipGetLastError(); cand.release(); break; }
         if (c->arena_trials < 8) c->arena_trial_ms[c->arena_trials++] = ms;
-        if (ms < best_ms * 0.985f) { best = cand; best_ms = ms; } else cand.release();
+        if (ms < best_ms * 0.985f) { best = std::move(cand); best_ms = ms; } else cand.release();
     }
-    if (best.p) {
+    const bool challenger_kept = best.p != nullptr;
+    if (challenger_kept) {
         // the call's data lies in the old arena and the caller may still read it (P.arena): it is retired, not released
         if (c->arena_retired) { c->arena_retired->release(); delete c->arena_retired; }
-        c->arena_retired = new DevBuf(b_arena);
-        b_arena = best;
+        c->arena_retired = new DevBuf(std::move(b_arena));
+        b_arena = std::move(best);
         b_arena.piece = arena_knobs().piece;                   // (a later regrow is made of the configured pieces, not of the winner's ladder size)
     }
     c->arena_calibrated_bytes = b_arena.cap;
     if (trace) {
         fprintf(stderr, "[rgx trace] arena placement: call's arena %.3f ms", c->arena_trial_ms[0]);
         for (int k = 1; k < c->arena_trials; ++k) fprintf(stderr, ", %.3f", c->arena_trial_ms[k]);
-        fprintf(stderr, " -> %s\n", best.p ? "a challenger kept" : "kept");
+        fprintf(stderr, " -> %s\n", challenger_kept ? "a challenger kept" : "kept");
     }
     mark("arena placement trial");
     return RGX_OK;
@@ -118,7 +119,7 @@ int EventsRun::stage_upload() {
     std::vector<Member> &hm = c->hm_scratch;
     hm.clear();
     if (!d_bam) {
-        DevBuf &b = c->buf("bam");
+        DevBuf &b = c->buf(Buf::bam);
         HIP_TRY(b.ensure(bam_len + 64));
         d_bam = b.as<uint8_t>();
         mark("file buffer in HBM");
@@ -184,7 +185,7 @@ int EventsRun::stage_upload() {
             if (gated) {
                 gate_chunk = (((up_hi - up_lo) + gate_chunks - 1) / gate_chunks + 4095) & ~(size_t)4095;
                 for (size_t e = up_lo + gate_chunk; e < up_hi; e += gate_chunk) up.end.push_back(e);
-                DevBuf &bg = c->buf("gate_flags");
+                DevBuf &bg = c->buf(Buf::gate_flags);
                 if (!bg.p) { HIP_TRY(bg.ensure(4 * 64)); HIP_TRY(hipMemset(bg.p, 0, 4 * 64)); c->gate_epoch = 0; }
                 ++c->gate_epoch;
             } else
@@ -197,7 +198,7 @@ int EventsRun::stage_upload() {
             while (c->chunk_ev.size() < up.end.size()) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->chunk_ev.push_back(e); }
             uint8_t *dst = b.as<uint8_t>();
             up.copy_stream = copy_q;
-            uint32_t *gate_flags = gated ? c->buf("gate_flags").as<uint32_t>() : nullptr;
+            uint32_t *gate_flags = gated ? c->buf(Buf::gate_flags).as<uint32_t>() : nullptr;
             const uint32_t gate_epoch = c->gate_epoch;
             hipStream_t gate_q = c->side[0] ? c->side[0] : copy_q;
             up.th = std::thread([this, dst, hdr_hi, up_lo, gate_q, gate_flags, gate_epoch] {
@@ -240,7 +241,7 @@ int EventsRun::stage_upload() {
             }
         } else HIP_TRY(hipMemcpyAsync(b.p, h_bam, bam_len, hipMemcpyHostToDevice, st));
     }
-    DevBuf &b_scalars = c->buf("scalars");
+    DevBuf &b_scalars = c->buf(Buf::scalars);
     HIP_TRY(b_scalars.ensure(sizeof(Scalars)));
     d_sc = b_scalars.as<Scalars>();
     h_sc = (Scalars *)c->pinned;
@@ -256,7 +257,7 @@ int EventsRun::stage_upload() {
 int EventsRun::stage_members() {
     // -- BGZF member discovery on the device (replaces the serial BSIZE walk, bgzf.c:421-546) -------------------------------
     std::vector<Member> &hm = c->hm_scratch;
-    DevBuf &b_members = c->buf("members"), &b_disc = c->buf("discover");
+    DevBuf &b_members = c->buf(Buf::members), &b_disc = c->buf(Buf::discover);
     if (overlap) {
         // the member list came from the host scan: what the discovery kernels would have left in HBM
         // (in page-locked host memory, read in place by the kernels -- 24 bytes per member, once: an upload would queue behind the file's
@@ -276,22 +277,25 @@ int EventsRun::stage_members() {
     } else {
     const uint32_t n_tiles = (uint32_t)((bam_len + kMagicTile - 1) / kMagicTile);
     HIP_TRY(b_disc.ensure((size_t)n_tiles * 4 + scan_tmp_words(n_tiles) * 4 + 256));
-    uint32_t *tile_cnt = b_disc.as<uint32_t>(), *tile_tmp = tile_cnt + n_tiles;
+    Carve wd(b_disc);
+    uint32_t *tile_cnt = wd.u32(n_tiles), *tile_tmp = wd.u32(scan_tmp_words(n_tiles)); CARVE_TRY(wd, "discover");
     launch_magic_count(d_bam, bam_len, n_tiles, tile_cnt, st);
     launch_scan_u32(tile_cnt, tile_cnt, n_tiles, &d_sc->n_cand, tile_tmp, st);
     HIP_TRY(fetch(h_sc->n_cand));
     HIP_TRY(hipStreamSynchronize(st));
     n_cand = h_sc->n_cand;
     if (n_cand == 0) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);
-    DevBuf &b_cand = c->buf("cand");
+    DevBuf &b_cand = c->buf(Buf::cand);
     {
         const size_t N = n_cand;
         HIP_TRY(b_cand.ensure(N * 8 + N * 4 * 6 + scan_tmp_words(n_cand) * 4 + 256));
         HIP_TRY(b_members.ensure((N + 1) * sizeof(Member)));
     }
-    cand = b_cand.as<uint64_t>();
-    nx[0] = (uint32_t *)(cand + n_cand); nx[1] = (uint32_t *)(cand + n_cand) + n_cand;
-    c_isize = nx[1] + n_cand; c_reach = c_isize + n_cand; c_rank = c_reach + n_cand; c_isz2 = c_rank + n_cand; c_tmp = c_isz2 + n_cand;
+    Carve wc(b_cand);
+    cand = wc.u64(n_cand);
+    nx[0] = wc.u32(n_cand); nx[1] = wc.u32(n_cand);
+    c_isize = wc.u32(n_cand); c_reach = wc.u32(n_cand); c_rank = wc.u32(n_cand); c_isz2 = wc.u32(n_cand); c_tmp = wc.u32(scan_tmp_words(n_cand));
+    CARVE_TRY(wc, "cand");
     launch_magic_fill(d_bam, bam_len, n_tiles, tile_cnt, cand, st);
     }
     d_members = overlap ? (Member *)c->pinned_members : b_members.as<Member>();
@@ -443,7 +447,7 @@ int EventsRun::stage_members() {
 int EventsRun::stage_range_and_inflate() {
     // -- member range of this call ---------------------------------------------------------------------------------------------
     std::vector<Member> &hm = c->hm_scratch;
-    DevBuf &b_arena = c->buf("arena");
+    DevBuf &b_arena = c->buf(Buf::arena);
     m_lo = cut_lo ? h_sc->q_index[1] : 0;
     if (m_lo <= 4) m_lo = 0;        // keep the file head (BAM header) in the same launch: a lone lane needs milliseconds per member
     m_hi = stop;                                                  // exclusive
@@ -479,13 +483,13 @@ int EventsRun::stage_range_and_inflate() {
     n_range = m_hi - m_lo;
     HIP_TRY(b_arena.ensure(total + 256));
     HIP_TRY(hipEventRecord(c->ev[0], st));
-    DevBuf &b_lens = c->buf("inflate_scratch");
+    DevBuf &b_lens = c->buf(Buf::inflate_scratch);
     HIP_TRY(b_lens.ensure(inflate_scratch_bytes(std::max<uint32_t>(n_range, 64))));
     // with a seek, the members in front of its target are only inflated for the header's sake (same launch): their failures end nothing
     const uint32_t ignore_below = (seek && first_member < n_members_all && first_member > m_lo) ? first_member - m_lo : 0;
     d_bad = nullptr;                                 // region queries: which members of the range did not inflate (every chunk has its own end of stream)
     if (chunked && !chunks.empty() && n_range) {
-        DevBuf &b_bad = c->buf("bad_members");
+        DevBuf &b_bad = c->buf(Buf::bad_members);
         HIP_TRY(b_bad.ensure((size_t)n_range + 64));
         d_bad = b_bad.as<uint8_t>();
         HIP_TRY(hipMemsetAsync(d_bad, 0, n_range, st));
@@ -511,13 +515,14 @@ int EventsRun::stage_range_and_inflate() {
         HIP_TRY(b_lens.ensure(inflate_scratch_bytes(std::max<uint32_t>(n_range, 64)) + up.end.size() * inflate_scratch_bytes(64)));
         HIP_TRY(hipEventRecord(c->ev_ready, st));
         for (auto &q : c->side) if (q) HIP_TRY(hipStreamWaitEvent(q, c->ev_ready, 0));
-        uint32_t g_lo = m_lo; size_t scratch_off = 0; unsigned used_side = 0;
+        uint32_t g_lo = m_lo; unsigned used_side = 0;
+        Carve w_lens(b_lens);                                   // (every per-chunk launch below takes its own scratch)
         if (gated) {
             // one launch on the pipeline's stream, now: its waves wait for their chunk's flag themselves (k_inflate_coop; a range the wave form
             // takes -- a few thousand members -- is one launch behind the last chunk)
             if (inflate_takes_coop(n_range)) {
                 InflateGate gate;
-                gate.flags = c->buf("gate_flags").as<uint32_t>(); gate.epoch = c->gate_epoch; gate.n_chunks = (uint32_t)up.end.size(); gate.lo = up.lo;
+                gate.flags = c->buf(Buf::gate_flags).as<uint32_t>(); gate.epoch = c->gate_epoch; gate.n_chunks = (uint32_t)up.end.size(); gate.lo = up.lo;
                     gate.chunk_bytes = gate_chunk;
                 // Round 4, second half ("early tail"): the launch goes to a side stream and counts its finished waves per PART of the member list
                 // (parts cut where upload chunks end, at multiples of the lane-sorting group); the pipeline's stream waits for part after part
@@ -549,7 +554,7 @@ int EventsRun::stage_range_and_inflate() {
                     }
                 }
                 if (!early_parts.empty()) {
-                    DevBuf &bd = c->buf("gate_done");
+                    DevBuf &bd = c->buf(Buf::gate_done);
                     HIP_TRY(bd.ensure(64));
                     uint32_t *d_done = bd.as<uint32_t>();
                     hipStream_t q = c->side[1];
@@ -585,10 +590,10 @@ int EventsRun::stage_range_and_inflate() {
             const bool own = j + 1 == up.end.size() || j >= (size_t)kSideStreams || !c->side[j];
             hipStream_t q = own ? st : c->side[j];
             if (!own) used_side |= 1u << j;
+            uint32_t *lens = (uint32_t *)w_lens.u8(inflate_scratch_bytes(g_hi - g_lo)); CARVE_TRY(w_lens, "inflate_scratch");
             HIP_TRY(hipStreamWaitEvent(q, c->chunk_ev[j], 0));
-            launch_inflate(d_bam, d_members + g_lo, g_hi - g_lo, b_arena.as<uint8_t>(), upos_lo, (uint32_t *)(b_lens.as<uint8_t>() + scratch_off),
+            launch_inflate(d_bam, d_members + g_lo, g_hi - g_lo, b_arena.as<uint8_t>(), upos_lo, lens,
                 &d_sc->inflate.first_bad, q, ignore_below, g_lo - m_lo, /*piece=*/true, 0, d_bad, pairs);
-            scratch_off += inflate_scratch_bytes(g_hi - g_lo);
             g_lo = g_hi;
         }
         up.th.join();

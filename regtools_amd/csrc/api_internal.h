@@ -1,5 +1,6 @@
-// api_internal.h -- what the translation units behind the C ABI (include/regtools_amd.h) share: the context, its device buffers, one call's state (EventsRun)
-// and the functions one unit calls in another.  Round 6: api.cpp (2,600 lines, with cse_api.inc included into it) split along its stages --
+// api_internal.h -- what the translation units behind the C ABI (include/regtools_amd.h) share: the context, its device buffers (DevBuf, move-only; the
+// context's are named by enum Buf and cut into arrays with carve.h's Carve), the radix-sort helper, one call's state (EventsRun) and the functions one unit
+// calls in another.  Round 6: api.cpp (2,600 lines, with cse_api.inc included into it) split along its stages --
 //   api_ctx.cpp      contexts, streams, result tables and their text
 //   api_front.cpp    EventsRun: upload, member list, the DEFLATE launch (+ the opt-in arena placement trials)
 //   api_records.cpp  EventsRun: footers and header, record framing, decode, emit
@@ -37,6 +38,7 @@
 #include "host_io.h"
 #include "worker_pool.h"
 #include <sys/stat.h>
+#include "carve.h"
 #include "kernels.h"
 #include "scalars.h"
 
@@ -105,6 +107,19 @@ struct DevBuf {
     size_t mapped = 0;              // bytes of the reserved address range the pieces are mapped into, which may be longer than they are (0: a hipMalloc block)
     std::vector<size_t> piece_len;  // the mappings inside that range, in address order (each is unmapped on its own)
     int range_dev = -1;             // the device the range's pieces were created on
+    // One owner per allocation: a buffer moves, it is never copied.  The source is left empty (p == nullptr, cap == 0, mapped == 0, no pieces); what the
+    // target of an assignment owned is released first.
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this == &o) return *this;
+        release();
+        p = o.p; cap = o.cap; piece = o.piece; mapped = o.mapped; piece_len = std::move(o.piece_len); range_dev = o.range_dev;
+        o.p = nullptr; o.cap = 0; o.mapped = 0; o.piece_len.clear();
+        return *this;
+    }
     // The arena's form (round 5).  The DEFLATE launch writes 169,000 streams 64 KB apart at once, and what it costs depends on the memory under
     // them: 13.9-15.9 ms
     // into one hipMalloc block of 11 GB, 12.3-12.6 ms into the same bytes created as pieces of 1 GiB (hipMemCreate) and mapped side by side into one reserved
@@ -208,24 +223,16 @@ struct DevBuf {
         p = nullptr; cap = 0; mapped = 0; piece_len.clear();
     }
     template <class T> T *as() const { return (T *)p; }
+    explicit operator Carve() const { return Carve(p, cap); }      // Carve w(buffer): the whole buffer, to be cut into its arrays (carve.h)
 };
 
-// Hands out a buffer's bytes array by array and remembers whether it was asked for more than the buffer holds: CARVE_TRY, behind the last array and in
-// front of the first launch, fails the call instead of letting a kernel write past the end.
-struct Carve {
-    uint8_t *at; size_t left; bool over = false;
-    explicit Carve(const DevBuf &b) : at(b.as<uint8_t>()), left(b.cap) {}
-    template <class T> T *take(size_t n) {
-        if (n > left / sizeof(T)) { over = true; n = 0; }
-        T *r = (T *)at; at += n * sizeof(T); left -= n * sizeof(T);
-        return r;
-    }
-    uint8_t *u8(size_t n) { return take<uint8_t>(n); }
-    uint32_t *u32(size_t n) { return take<uint32_t>(n); }
-    uint64_t *u64(size_t n) { return take<uint64_t>(n); }
+// The context's device buffers: one enumerator per workspace, spelt like the name CARVE_TRY and the traces call it by.
+enum class Buf {
+    arena, bad_members, bam, barcode_text, barcodes, cand, cse_assoc, cse_events_all, cse_junction_items, cse_junctions, cse_pairs, cse_variant_hits,
+    cse_variants, cse_windows, discover, events, fasta, fasta_tab, gate_done, gate_flags, gtf_tables, hdr_arena, inflate_scratch, members, merge, odd_aux,
+    partials, probe_sizes, probe_slots, rank, row_map, rows_out, rows_packed, scalars, seg, seg_chunks, seg_cp, soa, sort, stage, table_dev, tmp, unique,
+    count
 };
-#define CARVE_TRY(w, what) \
-    do { if ((w).over) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the %s buffer is smaller than its arrays\n", what); } while (0)
 
 // Stable LSD radix sort of n positions by several 32-bit words, least significant first, 8 bits a pass: the permutation ping-pongs between perm[0] and
 // perm[1] (the first pass of a sort starts from the identity: perm_in == nullptr).  The keyed forms gather a word through the permutation once and let
@@ -338,7 +345,7 @@ struct rgx_ctx {
     float arena_trial_ms[8] = {}; int arena_trials = 0;  // (statistics: the candidates' times of the last calibration, [0] = the arena the call ran on)
     // around the call's whole-range DEFLATE launch, on the stream it runs on (host input: the arrival-gated launch, which spans the upload)
     hipEvent_t ev_launch[2] = {}; bool launch_timed = false;
-    std::map<std::string, DevBuf> bufs;
+    DevBuf bufs[(size_t)Buf::count];
     void *pinned = nullptr; size_t pinned_cap = 0;     // small pinned staging for scalar readbacks
     std::vector<Member> hm_scratch;
     void *pinned_members = nullptr; size_t pinned_members_cap = 0;      // the host scan's member list: kernels read it in place (grow-only)
@@ -355,7 +362,7 @@ struct rgx_ctx {
     rgx::Fasta *fasta = nullptr;
     // The genome the output stages look splice sites up in (host_fasta below): its mapping stays with the context from call to call
     rgx::Fasta *host_fasta = nullptr; std::string host_fasta_path; uint64_t host_fasta_key[4] = {0, 0, 0, 0};
-    DevBuf &buf(const char *name) { return bufs[name]; }
+    DevBuf &buf(Buf b) { return bufs[(size_t)b]; }
 };
 
 
@@ -444,7 +451,7 @@ struct EventsRun {
         if (!h_bam || !(up.lo || (up.hi && up.hi < bam_len))) return hipSuccess;
         if (up.th.joinable()) up.th.join();
         hipError_t e = hipStreamSynchronize(copy_q);
-        uint8_t *dst = c->buf("bam").as<uint8_t>();
+        uint8_t *dst = c->buf(Buf::bam).as<uint8_t>();
         if (e == hipSuccess && up.lo > up.hdr_hi) e = hipMemcpy(dst + up.hdr_hi, h_bam + up.hdr_hi, up.lo - up.hdr_hi, hipMemcpyHostToDevice);
         if (e == hipSuccess && up.hi < bam_len) e = hipMemcpy(dst + up.hi, h_bam + up.hi, bam_len - up.hi, hipMemcpyHostToDevice);
         up.lo = 0; up.hi = bam_len; up.hdr_hi = 0;
@@ -515,7 +522,7 @@ struct EventsRun {
     // One framing: the walk of segments [walk_from, n_s), then verification sweeps over [0, n_s) until the chain agrees.  Returns -1 to go on,
     // anything else is the call's result (a restart on another path has run, or an error).  `ended` = the chain ends inside [0, n_s).
     int frame(uint32_t n_s, uint32_t walk_from, bool &ended) {
-        DevBuf &b_tmp = c->buf("tmp");
+        DevBuf &b_tmp = c->buf(Buf::tmp);
         launch_seg_walk(arena, geom, n_s, n_ref, seg_start[cur], seg_exit[cur], seg_cnt[cur], seg_cp, st, walk_from);
         for (int iter = 0;; ++iter) {
             HIP_TRY(hipMemsetAsync(&d_sc->framing, 0xff, sizeof d_sc->framing, st));
@@ -564,30 +571,35 @@ struct EventsRun {
     // early tail: rows [0, emit_rows) have their events out, in emit_parts parts
     bool emit_parts_ok = false; uint32_t emit_parts = 0, emit_rows = 0; size_t ev_lay = 0;
     EventSoA ev_e;
-    EventSoA ev_layout(uint8_t *q, size_t E) {
+    // bytes of one event row in the "events" block: eight u32 columns (tid, start, ilen_cls, ts, te; rpos, rend; read) and the strand byte -- sized for all
+    // of them, whichever of the optional ones a call lays out
+    static constexpr size_t kEventRowBytes = 8 * sizeof(uint32_t) + 1;
+    // E rows' columns out of the "events" block (a fresh one, or the one the last call left: early tail); the caller's CARVE_TRY(w, "events") follows
+    EventSoA ev_layout(Carve &w, size_t E) {
         EventSoA v; memset(&v, 0, sizeof v);
-        v.tid = (uint32_t *)q; q += E * 4; v.start = (uint32_t *)q; q += E * 4; v.ilen_cls = (uint32_t *)q; q += E * 4;
-        v.ts = (uint32_t *)q; q += E * 4; v.te = (uint32_t *)q; q += E * 4;
-        if (want_read_span) { v.rpos = (uint32_t *)q; q += E * 4; v.rend = (uint32_t *)q; q += E * 4; }
-        if (p->barcodes) { v.read = (uint32_t *)q; q += E * 4; }
-        v.strand = q;
+        v.tid = w.u32(E); v.start = w.u32(E); v.ilen_cls = w.u32(E); v.ts = w.u32(E); v.te = w.u32(E);
+        if (want_read_span) { v.rpos = w.u32(E); v.rend = w.u32(E); }
+        if (p->barcodes) v.read = w.u32(E);
+        v.strand = w.u8(E);
         return v;
     }
     size_t soa_cap = 0;                                       // rows the SoA columns are laid out for (early tail: an estimate made from the prefix)
     ReadSoA soa;
     uint32_t *ev_base = nullptr, *long_list = nullptr;
-    hipError_t soa_layout(size_t R) {
-        DevBuf &b_soa = c->buf("soa");
-        hipError_t e_ = b_soa.ensure(R * (4 + 4 + 4 + 8 + 1 + 4 + 4 + 4 + (p->barcodes ? 8 : 0)) + 256);
-        if (e_ != hipSuccess) return e_;
-        uint8_t *q = b_soa.as<uint8_t>();
-        soa.cig_off = (uint64_t *)q; q += R * 8;
-        if (p->barcodes) { soa.rec_off = (uint64_t *)q; q += R * 8; }
-        soa.tid = (int32_t *)q; q += R * 4; soa.pos = (int32_t *)q; q += R * 4; soa.flag_nc = (uint32_t *)q; q += R * 4;
-        soa.n_ev = (uint32_t *)q; q += R * 4; ev_base = (uint32_t *)q; q += R * 4; long_list = (uint32_t *)q; q += R * 4;
-        soa.strand = q;
+    // bytes of one decoded row in the "soa" block: cig_off (u64), six u32 columns (tid, pos, flag_nc, n_ev, ev_base, long_list) and the strand byte; with
+    // barcodes, rec_off (u64) as well
+    static constexpr size_t kSoaRowBytes = sizeof(uint64_t) + 6 * sizeof(uint32_t) + 1, kSoaRecOffBytes = sizeof(uint64_t);
+    int soa_layout(size_t R) {                                // (kGoOn, or the call's error)
+        DevBuf &b_soa = c->buf(Buf::soa);
+        HIP_TRY(b_soa.ensure(R * (kSoaRowBytes + (p->barcodes ? kSoaRecOffBytes : 0)) + 256));
+        Carve w(b_soa);
+        soa.cig_off = w.u64(R);
+        if (p->barcodes) soa.rec_off = w.u64(R);
+        soa.tid = w.take<int32_t>(R); soa.pos = w.take<int32_t>(R); soa.flag_nc = w.u32(R);
+        soa.n_ev = w.u32(R); ev_base = w.u32(R); long_list = w.u32(R);
+        soa.strand = w.u8(R); CARVE_TRY(w, "soa");
         soa_cap = R;
-        return hipSuccess;
+        return kGoOn;
     }
     uint32_t n_events = 0, n_long = 0; uint64_t n_iterated = 0;
     // every way out while the side stream's launch may still run (an error in the prefix's framing, say: the next call on this context must not meet

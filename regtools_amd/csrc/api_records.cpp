@@ -10,7 +10,7 @@ int EventsRun::stage_footers_and_header() {
     // Host input whose members the host scan vouched for: no round trip here.  The header comes from the host's own inflate of the file's head,
     // the stages behind the inflate are enqueued on the assumption that every member inflates to its footer's length (what a well-formed file
     // does), and the launch's verdict is read with the framing's counts: anything else starts over on the device-resident path below.
-    DevBuf &b_arena = c->buf("arena"), &b_hdr = c->buf("hdr_arena"), &b_lens = c->buf("inflate_scratch");
+    DevBuf &b_arena = c->buf(Buf::arena), &b_hdr = c->buf(Buf::hdr_arena), &b_lens = c->buf(Buf::inflate_scratch);
     BamHeader hdr_host;
     mean_rec = 0;                                    // mean size of the file's first records (0 = unknown: 16 KiB segments)
     spec = overlap && !d_true_sizes && !geom_chunked_hint && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hdr_host, nullptr, &mean_rec);
@@ -37,7 +37,7 @@ int EventsRun::stage_footers_and_header() {
         }
         if (lies) {
             mark("footer mismatch: probing");
-            DevBuf &b_slots = c->buf("probe_slots"), &b_sizes = c->buf("probe_sizes");
+            DevBuf &b_slots = c->buf(Buf::probe_slots), &b_sizes = c->buf(Buf::probe_sizes);
             HIP_TRY(b_slots.ensure((size_t)n_members_all * kBgzfMaxBlock + 256));
             HIP_TRY(b_sizes.ensure((size_t)n_members_all * 4 + 64));
             HIP_TRY(b_lens.ensure(inflate_scratch_bytes(std::max<uint32_t>(n_members_all, 64))));
@@ -160,7 +160,7 @@ int EventsRun::stage_bounds_and_chains() {
             delete c->fasta; c->fasta = new Fasta(); c->fasta_path.clear();
             if (!c->fasta->load(p->fasta_path)) { delete c->fasta; c->fasta = nullptr; return fail(err, errlen, RGX_ERR_FASTA,
                 "Unable to open FASTA file.\n\n"); }
-            DevBuf &bf = c->buf("fasta");
+            DevBuf &bf = c->buf(Buf::fasta);
             HIP_TRY(bf.ensure(c->fasta->size + 256));
             HIP_TRY(hipMemcpy(bf.p, c->fasta->data, c->fasta->size, hipMemcpyHostToDevice));
             c->fasta_path = p->fasta_path;
@@ -181,10 +181,10 @@ int EventsRun::stage_bounds_and_chains() {
                     tab[(size_t)t].offset = s.offset; tab[(size_t)t].len = s.len; tab[(size_t)t].line_blen = s.line_blen;
                         tab[(size_t)t].line_len = s.line_len; tab[(size_t)t].present = 1;
                 }
-        DevBuf &bt = c->buf("fasta_tab");
+        DevBuf &bt = c->buf(Buf::fasta_tab);
         HIP_TRY(bt.ensure(tab.size() * sizeof(FaContig) + 64));
         HIP_TRY(hipMemcpy(bt.p, tab.data(), tab.size() * sizeof(FaContig), hipMemcpyHostToDevice));
-        cfg.fa_data = c->buf("fasta").as<uint8_t>(); cfg.fa_tab = bt.as<FaContig>(); cfg.fa_missing = &d_sc->fa_missing;
+        cfg.fa_data = c->buf(Buf::fasta).as<uint8_t>(); cfg.fa_tab = bt.as<FaContig>(); cfg.fa_missing = &d_sc->fa_missing;
     }
 
     // -- region queries: one record chain per chunk of the iterator -----------------------------------------------------------------
@@ -234,7 +234,7 @@ int EventsRun::stage_bounds_and_chains() {
         }
         if (seg_chunks.empty()) lim = pos0;
         else {
-            DevBuf &b_ch = c->buf("seg_chunks");
+            DevBuf &b_ch = c->buf(Buf::seg_chunks);
             HIP_TRY(b_ch.ensure(seg_chunks.size() * sizeof(SegChunk) + 64));
             HIP_TRY(hipMemcpyAsync(b_ch.p, seg_chunks.data(), seg_chunks.size() * sizeof(SegChunk), hipMemcpyHostToDevice, st));
             geom.chunks = b_ch.as<SegChunk>(); geom.n_chunks = (uint32_t)seg_chunks.size();
@@ -247,7 +247,7 @@ int EventsRun::stage_bounds_and_chains() {
 
 int EventsRun::stage_framing() {
     // -- record framing ------------------------------------------------------------------------------------------------
-    arena = c->buf("arena").as<uint8_t>();
+    arena = c->buf(Buf::arena).as<uint8_t>();
     span = lim - pos0;
     n_seg = (uint32_t)((span + seg_bytes - 1) / seg_bytes);
     geom.pos0 = pos0; geom.lim = lim; geom.data_end = lim; geom.seg_bytes = seg_bytes;
@@ -262,7 +262,7 @@ int EventsRun::stage_framing() {
         geom.data_end = total;
     }
     n_rec = 0;
-    DevBuf &b_seg = c->buf("seg"), &b_tmp = c->buf("tmp");
+    DevBuf &b_seg = c->buf(Buf::seg), &b_tmp = c->buf(Buf::tmp);
     HIP_TRY(hipEventRecord(c->ev[2], st));
     // Early tail (round 4): while the side stream's launch still inflates the members of the last upload chunks, the segments that lie wholly
     // in front of their part of the arena (one member's margin: a walk only ever reads the 36 bytes behind its segment, a guess that
@@ -278,13 +278,13 @@ int EventsRun::stage_framing() {
     if (n_seg) {
         const size_t per = (size_t)n_seg;
         HIP_TRY(b_seg.ensure(per * (8 + 8 + 4) * 2 + per * 4 + per * 12 + 64));
-        HIP_TRY(c->buf("seg_cp").ensure(per * kSegCpSlots * 2 + 64));
-        seg_cp = c->buf("seg_cp").as<uint16_t>();
-        uint8_t *q = b_seg.as<uint8_t>();
-        for (int k = 0; k < 2; ++k) { seg_start[k] = (uint64_t *)q; q += per * 8; seg_exit[k] = (uint64_t *)q; q += per * 8; }
-        for (int k = 0; k < 2; ++k) { seg_cnt[k] = (uint32_t *)q; q += per * 4; }
-        seg_base = (uint32_t *)q; q += per * 4;
-        seg_iter_e = (uint32_t *)q; q += per * 4; seg_long_e = (uint32_t *)q; q += per * 4; seg_long_base_e = (uint32_t *)q;
+        HIP_TRY(c->buf(Buf::seg_cp).ensure(per * kSegCpSlots * 2 + 64));
+        seg_cp = c->buf(Buf::seg_cp).as<uint16_t>();
+        Carve q(b_seg);
+        for (int k = 0; k < 2; ++k) { seg_start[k] = q.u64(per); seg_exit[k] = q.u64(per); }
+        for (int k = 0; k < 2; ++k) seg_cnt[k] = q.u32(per);
+        seg_base = q.u32(per);
+        seg_iter_e = q.u32(per); seg_long_e = q.u32(per); seg_long_base_e = q.u32(per); CARVE_TRY(q, "seg");
         HIP_TRY(b_tmp.ensure(scan_tmp_words(n_seg) * 4 + 64));
         bool early = split_B && spec && !geom.chunks && seg_bytes == kSegBytes && cut_hi == UINT64_MAX && !empty_stream && lim == total;
         const bool env_early_emit = true;
@@ -299,7 +299,7 @@ int EventsRun::stage_framing() {
             HIP_TRY(hipMemsetAsync(&d_sc->wait_timed_out, 0, 4, st));
             for (size_t i = 0; i <= j; ++i) {
                 const uint32_t w_end = early_parts[i].waves, w_beg = i ? early_parts[i - 1].waves : 0u;
-                if (w_end > waves_done) { launch_wait_done(c->buf("gate_done").as<uint32_t>() + i, w_end - w_beg, &d_sc->wait_timed_out, st); waves_done = w_end; }
+                if (w_end > waves_done) { launch_wait_done(c->buf(Buf::gate_done).as<uint32_t>() + i, w_end - w_beg, &d_sc->wait_timed_out, st); waves_done = w_end; }
             }
             HIP_TRY(fetch(h_sc->wait_timed_out));      // (read behind the framing's first wait for the stream)
             if (trace) fprintf(stderr, "[rgx trace] early tail: part %zu: members < %u, segments [%u, %u) of %u\n", j, ep.members, sA, sJ, n_seg);
@@ -329,7 +329,7 @@ int EventsRun::stage_framing() {
                 (sA && n_rec_J > soa_cap)) { early = false; sA = 0; emit_parts_ok = false; emit_parts = 0; emit_rows = 0; break; }
             if (!sA) {
                 // rows for the whole file, estimated from the first part (+ 1/8); when the estimate turns out short the decode is simply made again below
-                HIP_TRY(soa_layout((size_t)((double)n_rec_J * ((double)n_seg / sJ) * 1.125) + 65536));
+                { const int rc = soa_layout((size_t)((double)n_rec_J * ((double)n_seg / sJ) * 1.125) + 65536); if (rc != kGoOn) return rc; }
                 cfg.insane_out = nullptr;
                 if (lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
             }
@@ -338,11 +338,11 @@ int EventsRun::stage_framing() {
             // sized: a first call, or a block that turns out too small, emits everything at the end as before).  ev_base counts from the part's
             // first row; the totals of the parts stay on the device, k_emit_short adds those in front of its part.
             if (!sA) {
-                DevBuf &b_ev0 = c->buf("events");
-                ev_lay = b_ev0.cap > 256 ? (b_ev0.cap - 256) / 33 : 0;
+                DevBuf &b_ev0 = c->buf(Buf::events);
+                ev_lay = b_ev0.cap > 256 ? (b_ev0.cap - 256) / kEventRowBytes : 0;
                 emit_parts_ok = env_early_emit && ev_lay >= 4096;
                 if (emit_parts_ok) { HIP_TRY(b_tmp.ensure(scan_tmp_words((uint32_t)std::min<size_t>(soa_cap, 0xffffffffu)) * 4 + 64));
-                    ev_e = ev_layout(b_ev0.as<uint8_t>(), ev_lay); }
+                    Carve w(b_ev0); ev_e = ev_layout(w, ev_lay); CARVE_TRY(w, "events"); }
             }
             if (emit_parts_ok && emit_parts < kGateParts - 1) {
                 launch_scan_u32(soa.n_ev + emit_rows, ev_base + emit_rows, n_rec_J - emit_rows, d_sc->part_events + emit_parts, b_tmp.as<uint32_t>(), st);
@@ -388,7 +388,7 @@ int EventsRun::stage_framing() {
 
 int EventsRun::stage_decode() {
     // -- decode + count -----------------------------------------------------------------------------------------------------
-    DevBuf &b_tmp = c->buf("tmp");
+    DevBuf &b_tmp = c->buf(Buf::tmp);
     n_events = 0; n_long = 0;
     n_iterated = 0;
     if (n_rec) {
@@ -397,7 +397,7 @@ int EventsRun::stage_decode() {
         //  ended after all, everything is decoded again)
         uint32_t s_from = sA;
         if (sA && (R > soa_cap || chain_ended)) s_from = 0;
-        if (!s_from) { HIP_TRY(soa_layout(R)); emit_parts_ok = false; }
+        if (!s_from) { const int rc = soa_layout(R); if (rc != kGoOn) return rc; emit_parts_ok = false; }
         HIP_TRY(b_tmp.ensure(scan_tmp_words(n_rec) * 4 + 64));
         // per-segment outputs (no hot atomics): reuse the spare segment arrays as seg_iter / seg_long
         uint32_t *seg_iter = sA ? seg_iter_e : seg_cnt[cur ^ 1], *seg_long = sA ? seg_long_e : (uint32_t *)seg_start[cur ^ 1], *seg_long_base = sA ?
@@ -469,7 +469,7 @@ int EventsRun::stage_decode() {
         if (cfg.odd_count && h_sc->odd_aux) {
             // damaged files only: the marked rows' (tid, pos, end) come to the host; what was counted (a second decode pass counts again) bounds the list
             const uint32_t cap = h_sc->odd_aux;
-            DevBuf &b_odd = c->buf("odd_aux");
+            DevBuf &b_odd = c->buf(Buf::odd_aux);
             HIP_TRY(b_odd.ensure((size_t)cap * 12 + 16));
             HIP_TRY(hipMemsetAsync(&d_sc->odd_aux, 0, 4, st));
             launch_collect_odd_aux(arena, soa, n_rec, cap, &d_sc->odd_aux, b_odd.as<int32_t>(), st);
@@ -492,14 +492,14 @@ int EventsRun::stage_decode() {
 
 int EventsRun::stage_emit() {
     // -- emit -----------------------------------------------------------------------------------------------------------------
-    DevBuf &b_ev = c->buf("events");
+    DevBuf &b_ev = c->buf(Buf::events);
     EventSoA ev; memset(&ev, 0, sizeof ev);
     if (n_events) {
         const size_t E = n_events;
         if (emit_parts_ok && n_rec) ev = ev_e;                  // (early tail: every part's rows are out already)
         else {
-            HIP_TRY(b_ev.ensure(E * (4 * 8 + 1) + 256));
-            ev = ev_layout(b_ev.as<uint8_t>(), E);
+            HIP_TRY(b_ev.ensure(E * kEventRowBytes + 256));
+            Carve w(b_ev); ev = ev_layout(w, E); CARVE_TRY(w, "events");
             launch_emit_short(arena, n_rec, cfg, soa, ev_base, ev, st);
             launch_emit_long(arena, long_list, n_long, cfg, soa, ev_base, ev, st);
         }

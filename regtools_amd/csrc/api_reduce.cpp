@@ -5,8 +5,8 @@
 int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bits, uint32_t ilen_bits, const uint32_t *rank_of_group_host,
                          uint32_t n_groups, HostRows &R, char *err, size_t errlen, bool view_only, RowMap *row_map, TableSink *sink, bool allow_preagg) {
     hipStream_t st = c->stream;
-    Scalars *d_sc = c->buf("scalars").as<Scalars>(), *h_sc = (Scalars *)c->pinned;
-    DevBuf &b_sort = c->buf("sort"), &b_uni = c->buf("unique");
+    Scalars *d_sc = c->buf(Buf::scalars).as<Scalars>(), *h_sc = (Scalars *)c->pinned;
+    DevBuf &b_sort = c->buf(Buf::sort), &b_uni = c->buf(Buf::unique);
     c->last_rows_valid = false;            // the "rows_out" block is about to be overwritten
     uint32_t n_unique = 0;
     UniqueSoA u; memset(&u, 0, sizeof u);
@@ -18,16 +18,17 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
         // rows.  Callers that need every event's row (the -b pass: row_map) keep the event form.
         const bool preagg = !row_map && allow_preagg;
         PartialSoA pr; memset(&pr, 0, sizeof pr);
-        uint32_t *ev_flag = nullptr;           // preagg: one word per EVENT (first-seen flags, then their scan)
+        uint32_t *ev_flag = nullptr, *ev_flag_tmp = nullptr;    // preagg: one word per EVENT (first-seen flags, then their scan) and that scan's scratch
         EventSoA sev = ev;                     // what is sorted: the events, or the partial rows
         uint32_t n_s = n_events;
         if (preagg) {
-            DevBuf &b_par = c->buf("partials");
+            DevBuf &b_par = c->buf(Buf::partials);
             const size_t Ev = n_events;
             HIP_TRY(b_par.ensure(Ev * 4 * 9 + scan_tmp_words(n_events) * 4 + 512));
             Carve q(b_par);
             pr.tid = q.u32(Ev); pr.start = q.u32(Ev); pr.ilen_cls = q.u32(Ev); pr.ts = q.u32(Ev); pr.te = q.u32(Ev);
-            pr.count = q.u32(Ev); pr.first = q.u32(Ev); pr.last = q.u32(Ev); ev_flag = q.u32(Ev + scan_tmp_words(n_events)); CARVE_TRY(q, "partials");
+            pr.count = q.u32(Ev); pr.first = q.u32(Ev); pr.last = q.u32(Ev); ev_flag = q.u32(Ev); ev_flag_tmp = q.u32(scan_tmp_words(n_events));
+            CARVE_TRY(q, "partials");
             HIP_TRY(hipMemsetAsync(&d_sc->counts.n_partial, 0, 4, st));
             launch_preagg(ev, n_events, pr, &d_sc->counts.n_partial, st);
             HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->counts.n_partial, st));
@@ -73,12 +74,12 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
             // first-seen naming (junctions_extractor.cc:152-157): rank of the key's first event among all keys -- flags over the EVENTS
             HIP_TRY(hipMemsetAsync(ev_flag, 0, (size_t)n_events * 4, st));
             launch_reduce_finish_partials(ev.strand, n_unique, u, ev_flag, st);
-            launch_scan_u32(ev_flag, ev_flag, n_events, nullptr, ev_flag + n_events, st);
+            launch_scan_u32(ev_flag, ev_flag, n_events, nullptr, ev_flag_tmp, st);
             launch_name_rank(n_unique, ev_flag, u, st);
         } else {
             launch_reduce(ev, sorted, head, seg_excl, n_events, u, head_pos, st);
             if (row_map) {
-                DevBuf &b_map = c->buf("row_map");
+                DevBuf &b_map = c->buf(Buf::row_map);
                 HIP_TRY(b_map.ensure((E + U) * 4 + 256));
                 Carve wm(b_map);
                 row_map->ev_urow = wm.u32(E); row_map->urow_pos = wm.u32(U); CARVE_TRY(wm, "row_map");
@@ -95,7 +96,7 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
         // output order (junctions_extractor.h:117-140): rank of the group (chrom string order), thick_start, thick_end, name
         uint32_t rk = 0;
         for (uint32_t i = 0; i < n_groups; ++i) rk = std::max(rk, rank_of_group_host[i]);
-        DevBuf &b_rank = c->buf("rank");
+        DevBuf &b_rank = c->buf(Buf::rank);
         HIP_TRY(b_rank.ensure((size_t)n_groups * 4 + 64));
         // (outlives the asynchronous copy: every call ends with a sync of the stream)
         c->rank_stage.assign(rank_of_group_host, rank_of_group_host + n_groups);
@@ -114,11 +115,11 @@ int reduce_events(rgx_ctx *c, EventSoA ev, uint32_t n_events, uint32_t group_bit
     if (n_unique) {
         // rows in final order: gathered on the device into one block of ten columns, ONE copy into pinned memory
         const size_t U = n_unique;
-        DevBuf &b_out = c->buf("rows_out");
+        DevBuf &b_out = c->buf(Buf::rows_out);
         HIP_TRY(b_out.ensure(U * 40 + 256));
         launch_rows_out(u, final_perm, n_unique, b_out.as<uint32_t>(), st);
         if (sink) {
-            DevBuf &b_tab = c->buf("table_dev");
+            DevBuf &b_tab = c->buf(Buf::table_dev);
             const size_t bytes = table_block_bytes(U);
             HIP_TRY(b_tab.ensure(bytes + 256));
             launch_rows_table(u, final_perm, n_unique, sink->min_anchor, b_tab.as<uint8_t>(), st);
@@ -168,8 +169,8 @@ int barcode_rows(rgx_ctx *c, const Prep &P, const RowMap &rm, const rgx_extract_
     t->bc_row_begin = (uint64_t *)calloc(U + 1, 8);
     if (!E) { t->bc_count = (uint32_t *)calloc(1, 4); t->bc_str_begin = (uint64_t *)calloc(1, 8); t->bc_text = (char *)calloc(1, 1);
         t->bc_insert_rank = (uint32_t *)calloc(1, 4); return RGX_OK; }
-    Scalars *d_sc = c->buf("scalars").as<Scalars>(), *h_sc = (Scalars *)c->pinned;
-    DevBuf &b_bc = c->buf("barcodes");
+    Scalars *d_sc = c->buf(Buf::scalars).as<Scalars>(), *h_sc = (Scalars *)c->pinned;
+    DevBuf &b_bc = c->buf(Buf::barcodes);
     const size_t rtmp = radix_tmp_words((uint32_t)E) + scan_tmp_words((uint32_t)E) + 64;
     HIP_TRY(b_bc.ensure(E * (8 + 4 * 4 + 4 * 4 + 8 + 4 * 5) + rtmp * 4 + 512));
     Carve q(b_bc);
@@ -203,7 +204,7 @@ int barcode_rows(rgx_ctx *c, const Prep &P, const RowMap &rm, const rgx_extract_
     HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->barcode_text_len, st));
     HIP_TRY(hipStreamSynchronize(st));
     const size_t text_len = h_sc->barcode_text_len;
-    DevBuf &b_txt = c->buf("barcode_text");
+    DevBuf &b_txt = c->buf(Buf::barcode_text);
     HIP_TRY(b_txt.ensure(text_len + 256));
     launch_bc_gather(P.arena, n_pairs, pair_off, pair_len, str_begin, b_txt.as<uint8_t>(), st);
     std::vector<uint32_t> h_row(n_pairs), h_first(n_pairs), h_count(n_pairs), h_begin(n_pairs), h_len(n_pairs);

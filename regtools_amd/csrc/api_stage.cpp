@@ -27,7 +27,7 @@ extern "C" int rgx_k_scan_u32(rgx_ctx *c, const uint32_t *d_in, uint32_t *d_out,
     if (!c || (n && (!d_in || !d_out))) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
     HIP_ENTER(c->device);
     hipStream_t st = c->stream;
-    DevBuf &b = c->buf("stage");
+    DevBuf &b = c->buf(Buf::stage);
     const size_t tmp_words = scan_tmp_words(n);
     HIP_TRY(b.ensure((tmp_words + kGuardWords) * 4 + 256));
     Carve q(b);
@@ -52,7 +52,7 @@ extern "C" int rgx_k_radix_sort(rgx_ctx *c, uint32_t n, uint32_t n_scratch, uint
     HIP_ENTER(c->device);
     hipStream_t st = c->stream;
     // (reduce_events' "sort" buffer: two permutations, two key columns, the scratch of a pass and of a scan)
-    DevBuf &b = c->buf("stage");
+    DevBuf &b = c->buf(Buf::stage);
     const size_t E = n_scratch, rtmp = radix_tmp_words(n_scratch) + scan_tmp_words(n_scratch) + 64;
     HIP_TRY(b.ensure((E * 4 + rtmp + kGuardWords) * 4 + 256));
     Carve q(b);
@@ -88,7 +88,7 @@ extern "C" int rgx_k_group_by(rgx_ctx *c, const uint32_t *d_tid, const uint32_t 
     *n_rows_out = 0;
     HIP_ENTER(c->device);
     hipStream_t st = c->stream;
-    HIP_TRY(c->buf("scalars").ensure(sizeof(Scalars)));
+    HIP_TRY(c->buf(Buf::scalars).ensure(sizeof(Scalars)));
     EventSoA ev; memset(&ev, 0, sizeof ev);
     ev.tid = (uint32_t *)d_tid; ev.start = (uint32_t *)d_start; ev.ilen_cls = (uint32_t *)d_ilen_cls; ev.ts = (uint32_t *)d_ts; ev.te = (uint32_t *)d_te;
     ev.strand = (uint8_t *)d_strand;
@@ -97,7 +97,7 @@ extern "C" int rgx_k_group_by(rgx_ctx *c, const uint32_t *d_tid, const uint32_t 
                                  form == 2 ? &rm : nullptr, nullptr, /*allow_preagg=*/form == 0);
     c->last_rows_valid = false;            // these rows are no extraction's table (rgx_last_table_pack_device)
     if (rc != RGX_OK) return rc;
-    if (R.n) HIP_TRY(hipMemcpyAsync(d_rows_out, c->buf("rows_out").p, R.n * 40, hipMemcpyDeviceToDevice, st));
+    if (R.n) HIP_TRY(hipMemcpyAsync(d_rows_out, c->buf(Buf::rows_out).p, R.n * 40, hipMemcpyDeviceToDevice, st));
     if (form == 2 && n_events) {
         HIP_TRY(hipMemcpyAsync(d_ev_urow, rm.ev_urow, (size_t)n_events * 4, hipMemcpyDeviceToDevice, st));
         if (R.n) HIP_TRY(hipMemcpyAsync(d_urow_pos, rm.urow_pos, R.n * 4, hipMemcpyDeviceToDevice, st));
@@ -114,7 +114,7 @@ extern "C" int rgx_k_components(rgx_ctx *c, uint32_t n_vertices, uint32_t n_edge
     HIP_ENTER(c->device);
     hipStream_t st = c->stream;
     // (rgx_cohort_cluster's loop: the labels live in the caller's array, the scratch is the rounds' flag words)
-    DevBuf &b = c->buf("stage");
+    DevBuf &b = c->buf(Buf::stage);
     HIP_TRY(b.ensure((kCcBatch + kGuardWords) * 4 + 256));
     Carve q(b);
     uint32_t *flags = q.u32(kCcBatch), *guard_at = q.u32(kGuardWords); CARVE_TRY(q, "stage");

@@ -149,7 +149,7 @@ extern "C" int rgx_cohort_add(rgx_cohort *co, rgx_ctx *src, const rgx_junction_t
             // behind the source context's last kernel, and in front of its next one: the next call there overwrites the rows
             HIP_TRY(hipEventRecord(co->ev_src, src->stream));
             HIP_TRY(hipStreamWaitEvent(co->stream, co->ev_src, 0));
-            launch_cohort_append(src->buf("rows_out").as<uint32_t>(), n, n, 9, d_map, (uint32_t)map.size(), min_anchor, co->p.only_anchored != 0, sample,
+            launch_cohort_append(src->buf(Buf::rows_out).as<uint32_t>(), n, n, 9, d_map, (uint32_t)map.size(), min_anchor, co->p.only_anchored != 0, sample,
                                  co->d_fill, cap, co->d_blocks, co->stream);
             HIP_TRY(hipEventRecord(co->ev_done, co->stream));
             HIP_TRY(hipStreamWaitEvent(src->stream, co->ev_done, 0));

@@ -40,7 +40,7 @@ static int gtf_upload(rgx_ctx *c, rgx_gtf *g, char *err, size_t errlen, bool poo
         E * 4},
                              {o_ee, m.ee.data(), E * 4}, {o_bk, m.bin_key.data(), B * 8}, {o_bt, m.bin_tx.data(), B * 4}, {o_bs, m.bin_start.data(), S * 4}};
     if (pooled) {
-        DevBuf &b = c->buf("gtf_tables");
+        DevBuf &b = c->buf(Buf::gtf_tables);
         HIP_TRY(b.ensure(total));
         d = b.as<uint8_t>();
         g->dev = nullptr;                                          // (the context's: rgx_gtf_free leaves it alone)
@@ -125,13 +125,13 @@ static int variant_windows(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32
     if (!n) return RGX_OK;
     hipStream_t st = c->stream;
     HIP_ENTER(c->device);
-    DevBuf &b = c->buf("cse_variants"), &sc = c->buf("scalars");
+    DevBuf &b = c->buf(Buf::cse_variants), &sc = c->buf(Buf::scalars);
     HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t N = n;
     HIP_TRY(b.ensure(N * 4 * 7 + scan_tmp_words(n) * 4 + 256));
-    uint32_t *w = b.as<uint32_t>();
-    int32_t *d_chrom = (int32_t *)w; w += N; uint32_t *d_pos = w; w += N; uint32_t *d_cnt = w; w += N; uint32_t *d_base = w; w += N;
-    uint32_t *d_ces = w; w += N; uint32_t *d_cee = w; w += N; uint32_t *d_last = w; w += N; uint32_t *d_tmp = w;
+    Carve w(b);
+    int32_t *d_chrom = w.take<int32_t>(N); uint32_t *d_pos = w.u32(N), *d_cnt = w.u32(N), *d_base = w.u32(N);
+    uint32_t *d_ces = w.u32(N), *d_cee = w.u32(N), *d_last = w.u32(N), *d_tmp = w.u32(scan_tmp_words(n)); CARVE_TRY(w, "cse_variants");
     uint32_t *d_total = &sc.as<Scalars>()->variant_hits;
     HIP_TRY(hipMemcpyAsync(d_chrom, chrom.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_pos, pos0.data(), N * 4, hipMemcpyHostToDevice, st));
@@ -153,9 +153,10 @@ static int variant_windows(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32
     HIP_TRY(hipMemcpy(H.off.data(), d_base, N * 4, hipMemcpyDeviceToHost));
     H.off[N] = total;
     if (total) {
-        DevBuf &bh = c->buf("cse_variant_hits");
+        DevBuf &bh = c->buf(Buf::cse_variant_hits);
         HIP_TRY(bh.ensure((size_t)total * 12 + 256));
-        uint32_t *d_tx = bh.as<uint32_t>(), *d_ad = d_tx + total;
+        Carve wh(bh);
+        uint32_t *d_tx = wh.u32(total), *d_ad = wh.u32(2 * (size_t)total); CARVE_TRY(wh, "cse_variant_hits");
         ktime_begin(c, 0);
         launch_variant_scan(true, g->view, n, d_chrom, d_pos, o, d_cnt, d_base, d_ces, d_cee, d_tx, d_ad, nullptr, st);
         ktime_end(c);
@@ -205,13 +206,14 @@ static int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<in
     if (!n) return RGX_OK;
     hipStream_t st = c->stream;
     HIP_ENTER(c->device);
-    DevBuf &b = c->buf("cse_junctions"), &sc = c->buf("scalars");
+    DevBuf &b = c->buf(Buf::cse_junctions), &sc = c->buf(Buf::scalars);
     HIP_TRY(sc.ensure(sizeof(Scalars)));
     const size_t N = n;
     HIP_TRY(b.ensure(N * 4 * 7 + N + scan_tmp_words(n) * 4 + 512));
-    uint32_t *w = b.as<uint32_t>();
-    int32_t *d_chrom = (int32_t *)w; w += N; uint32_t *d_js = w; w += N; uint32_t *d_je = w; w += N; uint32_t *d_cnt = w; w += N; uint32_t *d_base = w; w += N;
-    uint32_t *d_flags = w; w += N; uint32_t *d_visit_each = w; w += N; uint32_t *d_tmp = w; w += scan_tmp_words(n) + 8; uint8_t *d_strand = (uint8_t *)w;
+    Carve w(b);
+    int32_t *d_chrom = w.take<int32_t>(N); uint32_t *d_js = w.u32(N), *d_je = w.u32(N), *d_cnt = w.u32(N), *d_base = w.u32(N);
+    uint32_t *d_flags = w.u32(N), *d_visit_each = w.u32(N), *d_tmp = w.u32(scan_tmp_words(n) + 8); uint8_t *d_strand = w.u8(N);
+    CARVE_TRY(w, "cse_junctions");
     uint32_t *d_total = &sc.as<Scalars>()->junction_items;
     HIP_TRY(hipMemcpyAsync(d_chrom, chrom.data(), N * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_js, js.data(), N * 4, hipMemcpyHostToDevice, st));
@@ -239,9 +241,10 @@ static int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<in
     HIP_TRY(hipMemcpy(off.data(), d_base, N * 4, hipMemcpyDeviceToHost));
     off[N] = total;
     if (total) {
-        DevBuf &bi = c->buf("cse_junction_items");
+        DevBuf &bi = c->buf(Buf::cse_junction_items);
         HIP_TRY(bi.ensure((size_t)total * 12 + 256));
-        uint32_t *d_k = bi.as<uint32_t>(), *d_a = d_k + total, *d_b = d_a + total;
+        Carve wi(bi);
+        uint32_t *d_k = wi.u32(total), *d_a = wi.u32(total), *d_b = wi.u32(total); CARVE_TRY(wi, "cse_junction_items");
         ktime_begin(c, 1);
         launch_junction_scan(true, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, d_base, d_flags, d_k, d_a, d_b, nullptr, nullptr, st);
         ktime_end(c);
@@ -308,13 +311,14 @@ static int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_
     const uint32_t W = (uint32_t)w_tid.size();
     if (!W || !P.n_events) return RGX_OK;
     hipStream_t st = c->stream;
-    DevBuf &b = c->buf("cse_windows"), &sc = c->buf("scalars");
+    DevBuf &b = c->buf(Buf::cse_windows), &sc = c->buf(Buf::scalars);
     const size_t Wn = W;
     const size_t Sn = Wn * kWinSlices;                               // count / base: one entry per (window, slice)
     HIP_TRY(b.ensure(Wn * 4 * 5 + Sn * 4 * 2 + scan_tmp_words((uint32_t)Sn) * 4 + 256));
-    uint32_t *w = b.as<uint32_t>();
-    int32_t *d_tid = (int32_t *)w; w += Wn; int32_t *d_beg = (int32_t *)w; w += Wn; int32_t *d_end = (int32_t *)w; w += Wn;
-    uint32_t *d_lo = w; w += Wn; uint32_t *d_hi = w; w += Wn; uint32_t *d_cnt = w; w += Sn; uint32_t *d_base = w; w += Sn; uint32_t *d_tmp = w;
+    Carve w(b);
+    int32_t *d_tid = w.take<int32_t>(Wn), *d_beg = w.take<int32_t>(Wn), *d_end = w.take<int32_t>(Wn);
+    uint32_t *d_lo = w.u32(Wn), *d_hi = w.u32(Wn), *d_cnt = w.u32(Sn), *d_base = w.u32(Sn), *d_tmp = w.u32(scan_tmp_words((uint32_t)Sn));
+    CARVE_TRY(w, "cse_windows");
     uint32_t *d_span = &sc.as<Scalars>()->max_span, *d_total = &sc.as<Scalars>()->window_pairs;
     HIP_TRY(hipMemcpyAsync(d_tid, w_tid.data(), Wn * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_beg, w_beg.data(), Wn * 4, hipMemcpyHostToDevice, st));
@@ -345,13 +349,14 @@ static int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_
         n_pairs += total;
         if (total) {
             launch_scan_u32(d_cnt + (size_t)w0 * kWinSlices, d_base + (size_t)w0 * kWinSlices, nw * kWinSlices, d_total, d_tmp, st);
-            DevBuf &bp = c->buf("cse_pairs");
+            DevBuf &bp = c->buf(Buf::cse_pairs);
             const size_t Pn = total;
             HIP_TRY(bp.ensure(Pn * 4 * 7 + Pn + 256));
-            uint32_t *q = bp.as<uint32_t>();
-            uint32_t *pair_ev = q; q += Pn; uint32_t *pair_win = q; q += Pn;
+            Carve q(bp);
+            uint32_t *pair_ev = q.u32(Pn), *pair_win = q.u32(Pn);
             EventSoA pe; memset(&pe, 0, sizeof pe);
-            pe.tid = q; q += Pn; pe.start = q; q += Pn; pe.ilen_cls = q; q += Pn; pe.ts = q; q += Pn; pe.te = q; q += Pn; pe.strand = (uint8_t *)q;
+            pe.tid = q.u32(Pn); pe.start = q.u32(Pn); pe.ilen_cls = q.u32(Pn); pe.ts = q.u32(Pn); pe.te = q.u32(Pn); pe.strand = q.u8(Pn);
+            CARVE_TRY(q, "cse_pairs");
             ktime_begin(c, 2);
             launch_window_pairs(true, P.ev, P.n_events, nw, d_tid + w0, d_beg + w0, d_end + w0, d_span, d_lo + w0, d_hi + w0,
                 d_cnt + (size_t)w0 * kWinSlices, d_base + (size_t)w0 * kWinSlices, pair_ev, pair_win, st);
@@ -399,12 +404,13 @@ static int window_join_by_seeks(rgx_ctx *c, const uint8_t *d_file, size_t bam_le
         if (total && nw) {
             if (total >= (1ull << 31)) return fail(err, errlen, RGX_ERR_ARG,
                 "regtools_amd: %zu junction-supporting reads in one batch of windows; more than the join handles\n", total);
-            DevBuf &bp = c->buf("cse_pairs");
+            DevBuf &bp = c->buf(Buf::cse_pairs);
             HIP_TRY(bp.ensure(total * 4 * 7 + total + 256));
-            uint32_t *q = bp.as<uint32_t>() + 2 * total;          // (window_join's layout: the pair lists' place stays empty)
+            Carve q(bp);
+            (void)q.u32(total); (void)q.u32(total);               // (window_join's layout: the pair lists' place stays empty)
             EventSoA pe; memset(&pe, 0, sizeof pe);
-            pe.tid = q; q += total; pe.start = q; q += total; pe.ilen_cls = q; q += total; pe.ts = q; q += total; pe.te = q; q += total;
-                pe.strand = (uint8_t *)q;
+            pe.tid = q.u32(total); pe.start = q.u32(total); pe.ilen_cls = q.u32(total); pe.ts = q.u32(total); pe.te = q.u32(total);
+            pe.strand = q.u8(total); CARVE_TRY(q, "cse_pairs");
             uint32_t *dst[5] = {pe.tid, pe.start, pe.ilen_cls, pe.ts, pe.te};
             for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(dst[k], h_col[k].data(), total * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(pe.strand, h_strand.data(), total, hipMemcpyHostToDevice, st));
@@ -887,13 +893,14 @@ static int prepare_events_sharded(const std::vector<rgx_ctx *> &cs, const uint8_
     if (N >= 0xfffffff0ull) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: %llu junction events; more than the join handles\n", (unsigned long long)N);
     rgx_ctx *c0 = cs[0];
     HIP_TRY(hipSetDevice(c0->device));
-    DevBuf &ball = c0->buf("cse_events_all");
+    DevBuf &ball = c0->buf(Buf::cse_events_all);
     const size_t Nn = (size_t)N, stride = (Nn * 4 + 255) & ~(size_t)255;
     HIP_TRY(ball.ensure(stride * 8 + 256));
-    uint8_t *q = ball.as<uint8_t>();
+    Carve q(ball);
+    auto column = [&] { return (uint32_t *)q.u8(stride); };          // (columns start 256 bytes apart at the least, whatever N is)
     EventSoA all; memset(&all, 0, sizeof all);
-    all.tid = (uint32_t *)q; all.start = (uint32_t *)(q + stride); all.ilen_cls = (uint32_t *)(q + 2 * stride); all.ts = (uint32_t *)(q + 3 * stride);
-    all.te = (uint32_t *)(q + 4 * stride); all.rpos = (uint32_t *)(q + 5 * stride); all.rend = (uint32_t *)(q + 6 * stride); all.strand = q + 7 * stride;
+    all.tid = column(); all.start = column(); all.ilen_cls = column(); all.ts = column();
+    all.te = column(); all.rpos = column(); all.rend = column(); all.strand = q.u8(stride); CARVE_TRY(q, "cse_events_all");
     size_t off = 0;
     for (int g = 0; g < used; ++g) {
         const Prep &pg = parts[(size_t)g];
@@ -1088,14 +1095,13 @@ static int identify_run(rgx_ctx *c, const std::vector<rgx_ctx *> *shards, const 
                 it->second; wces[w] = H.ces[vi]; wcee[w] = H.cee[vi]; }
             hipStream_t st = c->stream;
             HIP_ENTER(c->device);
-            DevBuf &b = c->buf("cse_assoc"), &sc = c->buf("scalars");
+            DevBuf &b = c->buf(Buf::cse_assoc), &sc = c->buf(Buf::scalars);
             HIP_TRY(sc.ensure(sizeof(Scalars)));
             const size_t Wn = W, Jn = J, Cn = chrom_off.size();
             HIP_TRY(b.ensure((Wn * 5 + Jn * 2 + Cn + scan_tmp_words(W)) * 4 + 512));
-            uint32_t *w = b.as<uint32_t>();
-            int32_t *d_wch = (int32_t *)w; w += Wn; uint32_t *d_ces = w; w += Wn; uint32_t *d_cee = w; w += Wn; uint32_t *d_cnt = w; w += Wn;
-                uint32_t *d_base = w; w += Wn;
-            uint32_t *d_js = w; w += Jn; uint32_t *d_je = w; w += Jn; uint32_t *d_off = w; w += Cn; uint32_t *d_tmp = w;
+            Carve w(b);
+            int32_t *d_wch = w.take<int32_t>(Wn); uint32_t *d_ces = w.u32(Wn), *d_cee = w.u32(Wn), *d_cnt = w.u32(Wn), *d_base = w.u32(Wn);
+            uint32_t *d_js = w.u32(Jn), *d_je = w.u32(Jn), *d_off = w.u32(Cn), *d_tmp = w.u32(scan_tmp_words(W)); CARVE_TRY(w, "cse_assoc");
             uint32_t *d_total = &sc.as<Scalars>()->assoc_pairs;
             HIP_TRY(hipMemcpyAsync(d_wch, wch.data(), Wn * 4, hipMemcpyHostToDevice, st)); HIP_TRY(hipMemcpyAsync(d_ces, wces.data(), Wn * 4,
                 hipMemcpyHostToDevice, st));
@@ -1114,9 +1120,10 @@ static int identify_run(rgx_ctx *c, const std::vector<rgx_ctx *> *shards, const 
               if (t64 >= (1ull << 31)) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: %llu (variant, junction) pairs; more than the join handles\n",
                   (unsigned long long)t64); }
             if (total) {
-                DevBuf &bp = c->buf("cse_pairs");
+                DevBuf &bp = c->buf(Buf::cse_pairs);
                 HIP_TRY(bp.ensure((size_t)total * 8 + 256));
-                uint32_t *d_pj = bp.as<uint32_t>(), *d_pw = d_pj + total;
+                Carve wp(bp);
+                uint32_t *d_pj = wp.u32(total), *d_pw = wp.u32(total); CARVE_TRY(wp, "cse_pairs");
                 launch_assoc_pairs(true, W, d_wch, d_ces, d_cee, d_off, d_js, d_je, d_cnt, d_base, d_pj, d_pw, st);
                 pj.resize(total); pw.resize(total);
                 HIP_TRY(hipMemcpyAsync(pj.data(), d_pj, (size_t)total * 4, hipMemcpyDeviceToHost, st));

@@ -1,4 +1,4 @@
-// scalars.h -- the per-call scalar block: c->buf("scalars") in HBM (512 bytes) and its mirror at the start of the page-locked c->pinned (4 KiB).  Kernels
+// scalars.h -- the per-call scalar block: c->buf(Buf::scalars) in HBM (512 bytes) and its mirror at the start of the page-locked c->pinned (4 KiB).  Kernels
 // leave totals, verdicts and flags here; the host reads them back member by member (fetch_scalar).  stage_upload clears the whole block and presets the
 // four members marked "preset ~0".  Members read back by ONE copy form one nested struct, so that they cannot drift apart.
 #pragma once

@@ -255,3 +255,20 @@ extern "C" double emu_gtf_load_ms(const char *gtf_path) {
     delete m;
     return e.empty() ? ms : -1.0;
 }
+
+// carve.h on its own, over a host array of `cap` bytes: take k asks for count[k] elements of width[k] bytes (1, 4 or 8); off[k] receives the offset of
+// the pointer it returned.  Returns Carve::over behind the last take (-1: a width Carve has no form for).
+#include "../../regtools_amd/csrc/carve.h"
+extern "C" int emu_carve(size_t cap, size_t n_takes, const uint32_t *width, const size_t *count, size_t *off) {
+    std::vector<uint8_t> mem(cap ? cap : 1);
+    Carve w(mem.data(), cap);
+    for (size_t k = 0; k < n_takes; ++k) {
+        const uint8_t *r = nullptr;
+        if (width[k] == 1) r = w.u8(count[k]);
+        else if (width[k] == 4) r = (const uint8_t *)w.u32(count[k]);
+        else if (width[k] == 8) r = (const uint8_t *)w.u64(count[k]);
+        else return -1;
+        off[k] = (size_t)(r - mem.data());
+    }
+    return w.over ? 1 : 0;
+}

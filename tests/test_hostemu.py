@@ -276,3 +276,38 @@ def test_worker_pool_parallel_sort_and_huge_page_vectors(emu, threads):
     the contents, class types are constructed)."""
     for seed, n in ((1, 5), (2, 1000), (3, 16384), (4, 100_001), (5, 300_000)):
         assert emu.emu_pool_selftest(seed, n, threads) == 0, (seed, n, threads)
+
+
+def test_carve_hands_out_running_offsets_and_refuses_what_does_not_fit(emu):
+    """Carve (csrc/carve.h) cuts every device workspace into its arrays: no padding, and an array that does not fit sets `over`, gets the
+    current position and moves nothing -- also when its byte size does not fit a size_t."""
+    emu.emu_carve.restype = ctypes.c_int
+    emu.emu_carve.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    size_max = ctypes.c_size_t(-1).value
+
+    def carve(cap, takes):
+        width = (ctypes.c_uint32 * len(takes))(*[w for w, _ in takes])
+        count = (ctypes.c_size_t * len(takes))(*[n for _, n in takes])
+        off = (ctypes.c_size_t * len(takes))()
+        over = emu.emu_carve(cap, len(takes), width, count, off)
+        assert over in (0, 1)
+        return list(off), bool(over)
+
+    takes = [(8, 5), (4, 7), (1, 3), (4, 2), (8, 1), (1, 9)]
+    sums = [0]
+    for w, n in takes:
+        sums.append(sums[-1] + w * n)
+    # an exact fit of mixed widths: the offsets are the running sums
+    assert carve(sums[-1], takes) == (sums[:-1], False)
+    # one byte short: the last take fails and is handed the position the take before it left; no later take advances (8 bytes are left)
+    off, over = carve(sums[-1] - 1, takes + [(8, 2), (4, 3), (1, 9)])
+    assert over and off == sums[:-1] + [sums[-2]] * 3
+    # ... and a failing take in the middle moves nothing: the later ones that do fit start where it stood
+    off, over = carve(sums[3] + 3, takes[:3] + [(4, 1), (1, 2), (8, 1)])
+    assert over and off == sums[:3] + [sums[3], sums[3], sums[3] + 2]
+    # a count whose byte size overflows size_t: refused, nothing wraps
+    off, over = carve(64, [(4, 3), (4, size_max // 4 + 1), (8, size_max // 8 + 1), (4, 1)])
+    assert over and off == [0, 12, 12, 12]
+    # a take of zero elements has no effect, in a full buffer either
+    assert carve(12, [(4, 0), (4, 3), (8, 0), (1, 0)]) == ([0, 0, 12, 12], False)
+    assert carve(0, [(8, 0)]) == ([0], False)
