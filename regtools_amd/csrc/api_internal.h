@@ -6,7 +6,7 @@
 //   api_records.cpp  EventsRun: footers and header, record framing, decode, emit
 //   api_reduce.cpp   group-by, output order, barcodes, the finished table
 //   api_entry.cpp    the extract entry points, packing and merging of tables
-//   cse_api.cpp      identify / associate / annotate (rows a9-a12, f2, f3)
+//   cse_*.cpp        identify / associate / annotate (rows a9-a12, f2, f3), split by command: cse_internal.h
 #pragma once
 //
 //   members (host BSIZE walk) -> [K] inflate -> header/BAI -> [K] segment chains + verify -> [K] fill offsets
@@ -404,7 +404,7 @@ struct Prep {
     std::vector<OddAux> odd_aux;
     // the file's bytes in HBM as this call left them (the context's "bam" block, or the caller's device buffer): whole only for an unsharded call.  identify
     // on a
-    // damaged file reads every window through the index on its own from here (cse_api.cpp window_join_by_seeks)
+    // damaged file reads every window through the index on its own from here (cse_join.cpp window_join_by_seeks)
     const uint8_t *d_file = nullptr;
 };
 
@@ -630,6 +630,16 @@ struct HostRows {
     // the same rows as ten u32 columns of n entries in the context's pinned staging block (valid until the next call on the context);
     // filled instead of the vectors when the caller asks for the view only
     const uint32_t *cols = nullptr;
+    // the rows of a batch of windows behind these (the window join), window indices made absolute; name ranks stay batch-local (callers only use them
+    // inside a window)
+    void append(const HostRows &batch, uint32_t first_window) {
+        auto app = [](std::vector<uint32_t> &dst, const std::vector<uint32_t> &src) { dst.insert(dst.end(), src.begin(), src.end()); };
+        for (uint32_t g : batch.group) group.push_back(g + first_window);
+        app(start, batch.start); app(end, batch.end); app(ts, batch.ts); app(te, batch.te); app(count, batch.count);
+        app(name_rank, batch.name_rank); app(first_seen, batch.first_seen); app(last_seen, batch.last_seen);
+        strand.insert(strand.end(), batch.strand.begin(), batch.strand.end());
+        n += batch.n;
+    }
 };
 
 // where each event ended up: its unique row, and each unique row's position in the output order (device arrays; the -b pass keys on them)

@@ -142,7 +142,7 @@ int EventsRun::stage_bounds_and_chains() {
     // (`junctions extract` only: identify's per-window extractions upstream meet such a read only inside a window -- DESIGN 8)
     if ((p->strandness == 0 || p->barcodes) && !want_read_span) { cfg.abort_out = &d_sc->abort_row; HIP_TRY(hipMemsetAsync(&d_sc->abort_row, 0xff, 4, st)); }
     if (p->barcodes && !want_read_span) { cfg.bc0 = (uint8_t)p->barcode_tag[0]; cfg.bc1 = (uint8_t)p->barcode_tag[1]; }
-    // (identify: the same reads counted and marked; which of them a window reads is known when the windows are, cse_api.cpp)
+    // (identify: the same reads counted and marked; which of them a window reads is known when the windows are, cse_identify.cpp)
     if (p->strandness == 0 && want_read_span) { cfg.odd_count = &d_sc->odd_aux; HIP_TRY(hipMemsetAsync(&d_sc->odd_aux, 0, 4, st)); }
     P.odd_aux.clear();
     cfg.min_anchor = p->min_anchor; cfg.min_intron = p->min_intron; cfg.max_intron = p->max_intron;

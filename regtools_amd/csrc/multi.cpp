@@ -114,7 +114,7 @@ rgx_ctx *context_for(int device, int nth, char *err, size_t errlen, int &rc) {
 }
 
 }  // namespace
-// (for rgx_identify_multi, cse_api.cpp: the same cache)
+// (for rgx_identify_multi, cse_identify.cpp: the same cache)
 rgx_ctx *rgx_multi_context(int device, int nth, char *err, size_t errlen, int *rc) { int r = RGX_OK; rgx_ctx *c = context_for(device, nth, err, errlen, r);
     if (rc) *rc = r; return c; }
 namespace {

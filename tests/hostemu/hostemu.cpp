@@ -272,3 +272,34 @@ extern "C" int emu_carve(size_t cap, size_t n_takes, const uint32_t *width, cons
     }
     return w.over ? 1 : 0;
 }
+
+// cse_table.h on its own: the first-insert junction table of `identify` / `associate`.  names / vnames: contig names of the junctions and of the variants
+// (equal names may repeat); cand: n_cand x (contig, start, end, variant contig, variant pos, src), indices into names / vnames, in arrival order.
+// threads: the pool finish() sorts on (0 = none given: its own).  rows: per junction in table order (contig, start, end, src of the row that stayed,
+// v0, v1) with [v0, v1) its variants in vars: (variant contig, pos) -- contigs as the first index that bears the name.  Returns the number of rows, -1 when
+// they do not fit, -2 when a junction's fields were asked for more than once.
+#include "../../regtools_amd/csrc/cse_table.h"
+extern "C" long emu_jtable(size_t n_names, const char *const *names, size_t n_vnames, const char *const *vnames, size_t n_cand, const uint32_t *cand,
+                           uint32_t threads, uint32_t *rows, size_t rows_cap, uint32_t *vars, size_t vars_cap, size_t *n_vars) {
+    std::vector<std::string> nm(names, names + n_names), vnm(vnames, vnames + n_vnames);
+    JTable t;
+    std::vector<uint32_t> crank_of, vrank_of;
+    string_ranks(nm, crank_of, t.chrom_name);
+    run_string_ranks(n_cand, [&](size_t k) -> const std::string & { return vnm[cand[6 * k + 3]]; }, vrank_of, t.vchrom_name);
+    for (size_t k = 0; k < n_cand; ++k) t.add(crank_of[cand[6 * k]], cand[6 * k + 1], cand[6 * k + 2], vrank_of[k], cand[6 * k + 4], cand[6 * k + 5]);
+    size_t asked = 0;
+    auto entry_of = [&](uint32_t src) { ++asked; return JEntry{src, 0, 0, "+", "", 2}; };
+    if (threads) { rgx::WorkerPool pool(threads); t.finish(entry_of, &pool); }
+    else t.finish(entry_of, nullptr);
+    if (asked != t.size()) return -2;
+    if (t.size() > rows_cap || t.vars.size() > vars_cap) return -1;
+    auto first_index = [](const std::vector<std::string> &v, const std::string &s) { return (uint32_t)(std::find(v.begin(), v.end(), s) - v.begin()); };
+    for (size_t i = 0; i < t.size(); ++i) {
+        const JTable::Row &r = t.rows[i];
+        const uint32_t out[6] = {first_index(nm, t.chrom_name[r.crank]), r.js, r.jend, r.e.ts, r.v0, r.v1};
+        memcpy(rows + 6 * i, out, sizeof out);
+    }
+    for (size_t k = 0; k < t.vars.size(); ++k) { vars[2 * k] = first_index(vnm, t.vchrom_name[t.vars[k].first]); vars[2 * k + 1] = t.vars[k].second; }
+    *n_vars = t.vars.size();
+    return (long)t.size();
+}

@@ -311,3 +311,61 @@ def test_carve_hands_out_running_offsets_and_refuses_what_does_not_fit(emu):
     # a take of zero elements has no effect, in a full buffer either
     assert carve(12, [(4, 0), (4, 3), (8, 0), (1, 0)]) == ([0, 0, 12, 12], False)
     assert carve(0, [(8, 0)]) == ([0], False)
+
+
+def _jtable(emu, names, vnames, cands, threads):
+    emu.emu_jtable.restype = ctypes.c_long
+    emu.emu_jtable.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    cn = (ctypes.c_char_p * max(1, len(names)))(*[s.encode() for s in names])
+    vn = (ctypes.c_char_p * max(1, len(vnames)))(*[s.encode() for s in vnames])
+    flat = (ctypes.c_uint32 * max(1, 6 * len(cands)))(*[x for cand in cands for x in cand])
+    rows = (ctypes.c_uint32 * max(1, 6 * len(cands)))()
+    vars_ = (ctypes.c_uint32 * max(1, 2 * len(cands)))()
+    n_vars = ctypes.c_size_t(0)
+    n = emu.emu_jtable(len(names), cn, len(vnames), vn, len(cands), flat, threads, rows, len(cands), vars_, len(cands), ctypes.byref(n_vars))
+    assert n >= 0, n
+    got, at = [], 0
+    for i in range(n):
+        c, s, e, src, v0, v1 = rows[6 * i:6 * i + 6]
+        assert v0 == at and v1 >= v0                     # the variants of the rows lie one behind the other
+        got.append(((names[c], s, e), src, [(vnames[vars_[2 * k]], vars_[2 * k + 1]) for k in range(v0, v1)]))
+        at = v1
+    assert at == n_vars.value
+    return got
+
+
+def _jtable_model(names, vnames, cands):
+    """std::map<(chrom string, start, end)>::insert -- the first row of a key stays -- and a std::set of (chrom string, pos) per key."""
+    table = {}
+    for c, s, e, vc, vp, src in cands:
+        table.setdefault((names[c], s, e), (src, []))[1].append((vnames[vc], vp))
+    return [(key, src, sorted(set(links))) for key, (src, links) in sorted(table.items())]
+
+
+def test_junction_table_iterates_like_the_map_and_sets_it_replaces(emu):
+    """JTable (csrc/cse_table.h) against a dict whose first insert wins, iterated in sorted() order of (name string, start, end), with sorted(set())
+    of (variant name string, pos) per key: names whose string order is neither arrival nor numeric order, repeated keys with different rows, a
+    variant linked twice, variants on several contigs, nothing, one candidate, and 20,000 candidates (the sort's threaded path) with and without a pool."""
+    names = ["chr10", "chr2", "chr1", "chrX", "chr2"]       # ("chr2" arrives twice: one rank)
+    vnames = ["chr2", "chr10", "chrX", "chr10"]
+    cands = [  # (contig, start, end, variant contig, variant pos, src)
+        (1, 500, 900, 0, 70, 0), (0, 500, 900, 1, 70, 1), (4, 500, 900, 2, 5, 2), (1, 500, 900, 0, 70, 3), (1, 500, 900, 3, 9, 4),
+        (2, 10, 20, 0, 1, 5), (3, 10, 20, 0, 1, 6), (2, 10, 19, 1, 1, 7), (2, 9, 20, 3, 2, 8), (0, 500, 900, 1, 69, 9), (4, 500, 901, 0, 70, 10),
+    ]
+    for threads in (0, 1, 3):
+        assert _jtable(emu, names, vnames, cands, threads) == _jtable_model(names, vnames, cands)
+        assert _jtable(emu, names, vnames, [], threads) == []
+        assert _jtable(emu, names, vnames, cands[2:3], threads) == [(("chr2", 500, 900), 2, [("chrX", 5)])]
+    got = _jtable(emu, names, vnames, cands, 0)
+    assert [key[0] for key, _, _ in got] == ["chr1", "chr1", "chr1", "chr10", "chr2", "chr2", "chrX"]
+    assert got[4] == (("chr2", 500, 900), 0, [("chr10", 9), ("chr2", 70), ("chrX", 5)])       # the first arrival's row, every variant once
+    rnd = random.Random(20)
+    keys = [(rnd.randrange(len(names)), rnd.randrange(1000), rnd.randrange(1000, 2000)) for _ in range(50)]
+    big = [keys[rnd.randrange(50)] + (rnd.randrange(len(vnames)), rnd.randrange(40), src) for src in range(20000)]
+    assert len(big) >= 1 << 14
+    want = _jtable_model(names, vnames, big)
+    assert 40 <= len(want) <= 50
+    for threads in (0, 4):
+        assert _jtable(emu, names, vnames, big, threads) == want

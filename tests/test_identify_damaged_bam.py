@@ -1,7 +1,7 @@
 """`cis-splice-effects identify` on a BAM whose record stream ENDS somewhere (a member that does not inflate, a file cut short): upstream reads every variant's
 window through the index on its own (cis_splice_effects_identifier.cc:288-290), so the windows BEHIND the damage still see their reads, and a window that runs
 into the damage keeps what it read before.  One pass over the file stops at the damage; for such files the product reads every window by its own region
-extraction (cse_api.cpp window_join_by_seeks).  CPU: the oracle against the real reference; GPU: the tool's two output files against the oracle's, also with the
+extraction (cse_join.cpp window_join_by_seeks).  CPU: the oracle against the real reference; GPU: the tool's two output files against the oracle's, also with the
 extraction sharded."""
 import os
 import shutil

@@ -1,7 +1,7 @@
 """`cis-splice-effects identify -s XS` and a spliced read whose strand tag lies behind an aux field of unknown type (tests/odd_aux_cases.py): upstream extracts
 every splice-relevant variant's window on its own, and the first window that READS such a read ends the process inside bam_aux_get (abort(), sam.c:1233-1252)
 behind that variant's echo; a read no window reads ends nothing.  The product extracts once: the decode kernels mark such reads, the host asks which window
-reads one (cse_api.cpp).  Status, streams and the files of the runs that complete are the real reference's (tests/golden/cli/cli_odd_aux_streams.json)."""
+reads one (cse_identify.cpp).  Status, streams and the files of the runs that complete are the real reference's (tests/golden/cli/cli_odd_aux_streams.json)."""
 import json
 import os
 import subprocess
