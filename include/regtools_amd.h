@@ -287,9 +287,9 @@ size_t rgx_cohort_format_counts(const rgx_cohort_matrix *m, char *buf, size_t ca
 /* =====================================================================================================
  * Intron clusters of a cohort matrix: the junctions that hang together through shared splice sites, and per cluster and sample the reads
  * on it -- the denominators of the ratio "reads on this junction / reads on its cluster" that differential-splicing tools work with.
- * The reference has no counterpart; this is the cohort's own rule.  It is the FIRST step of LeafCutter-style clustering only: it makes no
- * claim to equal LeafCutter's iterative refinement (which removes weak introns and clusters again), and there is NO re-clustering behind
- * the filters here -- a component is kept or dropped whole.
+ * The reference has no counterpart; this is the cohort's own rule.  rgx_cohort_cluster is the FIRST step of LeafCutter-style clustering only:
+ * there is NO re-clustering behind its filters -- a component is kept or dropped whole.  The refinement modelled on LeafCutter's (weak and
+ * over-long introns leave, the rest is clustered again) is rgx_cohort_refine, further down.
  *   input                 any rgx_cohort_matrix m: from rgx_cohort_finish or rgx_cohort_merge_host, filtered or not
  *   graph                 rows i and j are linked when they have the same tid, the same strand class (m->strand[i]: '+' 0, '-' 1, anything
  *                         else 2) and the same start or the same end; a cluster is a connected component (transitive: A and B sharing a
@@ -318,6 +318,7 @@ typedef struct {
     uint32_t   n_rounds;        /* hook + jump rounds the component search ran, the one that changed nothing included (the twin: 0) */
     double     ms_cluster;      /* this call, wall, up to the result being in host memory */
     uint64_t   n_components;    /* before the filters */
+    uint64_t   n_ineligible, n_weak;   /* rgx_cohort_refine: rows over max_intron, rows removed as weak (rgx_cohort_cluster: 0, 0) */
 } rgx_cohort_clusters;
 void rgx_cluster_params_default(rgx_cluster_params *p);                     /* 1, 0: everything is kept */
 /* On the cohort's device and stream.  When m is the matrix of co's most recent finish its image is still in HBM and is read in place;
@@ -336,6 +337,39 @@ void rgx_cohort_clusters_free(rgx_cohort_clusters *cl);
  * sample -- the row's count in the sample over the cluster's, "0/0" where the sample has no reads in the cluster.  Rows with
  * RGX_NO_CLUSTER are left out.  Buffer protocol of rgx_cohort_format_counts. */
 size_t rgx_cohort_format_cluster_counts(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, char *buf, size_t cap);
+
+/* -----------------------------------------------------------------------------------------------------
+ * Refined clusters, modelled on LeafCutter's refinement: introns that are too long never take part, junctions that are weak in their
+ * cluster are removed, and what is left is clustered again, so one weak junction no longer ties strong clusters together and the
+ * denominators are sums over the surviving rows only.  No claim of byte equality with LeafCutter: its ratio test is in floating point
+ * (this one is exact) and its clusters start from overlapping introns (these from shared splice sites).  LeafCutter's customary settings
+ * correspond to max_intron 100000, min_reads 5, ratio 1/1000, min_rows 2, min_total 30.
+ *   eligible rows         max_intron == 0 || end - start <= max_intron; n_ineligible counts the others, which link nothing
+ *   stage 1               the components of the eligible rows under the link rule above; T(i) = the sum of m->total over the eligible
+ *                         rows of i's component
+ *   weak rows             an eligible row is weak when total[i] < min_reads or total[i] * ratio_den < ratio_num * T(i) -- compared on the
+ *                         whole products (up to 96 bits), equality passes; n_weak counts them
+ *   stage 2               the components of the eligible rows that are not weak; one is kept when it has at least min_rows rows and its
+ *                         summed total is at least min_total; kept clusters are numbered by their lowest row; ineligible rows, weak rows and
+ *                         the rows of a dropped component get RGX_NO_CLUSTER; cl_* and cs_* are over member rows only; n_components counts
+ *                         the stage-2 components; n_rounds is the sum of both searches' rounds
+ *   one pass              removing rows and splitting components can only lower T, so a row that passed the ratio test passes it against
+ *                         every later T, and min_reads does not depend on T: a second removal would remove nothing
+ *   arguments             ratio_den == 0 or ratio_num > ratio_den is RGX_ERR_ARG; the limits are rgx_cohort_cluster's; an empty matrix gives
+ *                         n_clusters = 0 without a launch
+ * With the default parameters the result equals rgx_cohort_cluster's with the same min_rows / min_total in every array and count.  The
+ * result is the same struct: the formatter above and rgx_cohort_clusters_free take it.  Both matrix paths apply (rgx_cohort_cluster_path).
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t max_intron;            /* rows with end - start > max_intron take no part; 0 = no limit */
+                 uint64_t min_reads;             /* a row whose m->total is below this is weak */
+                 uint32_t ratio_num, ratio_den;  /* a row is weak when total * ratio_den < ratio_num * T (T: its stage-1 component's total) */
+                 uint32_t min_rows; uint64_t min_total;   /* the cluster filters of rgx_cluster_params, applied to the FINAL components */
+} rgx_refine_params;
+void rgx_refine_params_default(rgx_refine_params *p);   /* 0, 0, 0/1, 1, 0: nothing is removed */
+int  rgx_cohort_refine(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_refine_params *p, rgx_cohort_clusters **out,
+                       char *err, size_t errlen);
+/* Host twin: union-find twice and unsigned __int128 for the ratio test, no device.  NOT a fallback. */
+int  rgx_cohort_refine_host(const rgx_cohort_matrix *m, const rgx_refine_params *p, rgx_cohort_clusters **out, char *err, size_t errlen);
 
 /* Library/build identification: "regtools_amd <version> gfx950". */
 const char *rgx_version(void);

@@ -54,7 +54,8 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts",
            "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by",
            "rgx_cluster_params_default", "rgx_cohort_cluster", "rgx_cohort_cluster_path", "rgx_cohort_cluster_host", "rgx_cohort_clusters_free",
-           "rgx_cohort_format_cluster_counts", "rgx_k_components"]
+           "rgx_cohort_format_cluster_counts", "rgx_k_components",
+           "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host"]
 
 
 class CohortParams(C.Structure):
@@ -79,7 +80,13 @@ class CohortClusters(C.Structure):
     _fields_ = [("n_rows", C.c_uint64), ("n_clusters", C.c_uint64), ("cluster", C.POINTER(C.c_uint32)), ("cl_begin", C.POINTER(C.c_uint64)),
                 ("cl_row", C.POINTER(C.c_uint32)), ("cl_total", C.POINTER(C.c_uint64)), ("cs_begin", C.POINTER(C.c_uint64)),
                 ("cs_sample", C.POINTER(C.c_uint32)), ("cs_total", C.POINTER(C.c_uint64)),
-                ("n_rounds", C.c_uint32), ("ms_cluster", C.c_double), ("n_components", C.c_uint64)]
+                ("n_rounds", C.c_uint32), ("ms_cluster", C.c_double), ("n_components", C.c_uint64),
+                ("n_ineligible", C.c_uint64), ("n_weak", C.c_uint64)]
+
+
+class RefineParams(C.Structure):
+    _fields_ = [("max_intron", C.c_uint32), ("min_reads", C.c_uint64), ("ratio_num", C.c_uint32), ("ratio_den", C.c_uint32),
+                ("min_rows", C.c_uint32), ("min_total", C.c_uint64)]
 
 
 class IdentifyParams(C.Structure):
@@ -226,6 +233,9 @@ def lib():
         L.rgx_cohort_clusters_free.argtypes = [P(CohortClusters)]
         L.rgx_cohort_format_cluster_counts.argtypes = [P(CohortMatrix), P(CohortClusters), C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_cluster_counts.restype = C.c_size_t
+        L.rgx_refine_params_default.argtypes = [P(RefineParams)]
+        L.rgx_cohort_refine.argtypes = [C.c_void_p, P(CohortMatrix), P(RefineParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_refine_host.argtypes = [P(CohortMatrix), P(RefineParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -87,6 +87,7 @@ class CohortClusters(object):
         c = handle.contents
         self.n_rows, self.n_clusters, self.n_components = int(c.n_rows), int(c.n_clusters), int(c.n_components)
         self.n_rounds, self.ms_cluster = int(c.n_rounds), c.ms_cluster
+        self.n_ineligible, self.n_weak = int(c.n_ineligible), int(c.n_weak)          # (0, 0 unless the clusters are refined ones)
 
         def view(ptr, k, dtype):
             return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
@@ -129,6 +130,25 @@ def cluster_host(matrix, min_rows=1, min_total=0):
     out = C.POINTER(_ffi.CohortClusters)()
     err = C.create_string_buffer(512)
     rc = _ffi.lib().rgx_cohort_cluster_host(matrix._h, C.byref(p), C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortClusters(out)
+
+
+def _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total):
+    p = _ffi.RefineParams()
+    _ffi.lib().rgx_refine_params_default(C.byref(p))
+    p.max_intron, p.min_reads, (p.ratio_num, p.ratio_den), p.min_rows, p.min_total = max_intron, min_reads, min_ratio, min_rows, min_total
+    return p
+
+
+def refine_host(matrix, max_intron=0, min_reads=0, min_ratio=(0, 1), min_rows=1, min_total=0):
+    """rgx_cohort_refine_host: the refined clusters of a CohortMatrix by the library's plain C++ twin, no device involved.  min_ratio is an exact
+    fraction (numerator, denominator)."""
+    p = _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total)
+    out = C.POINTER(_ffi.CohortClusters)()
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_refine_host(matrix._h, C.byref(p), C.byref(out), err, len(err))
     if rc != 0:
         raise RegtoolsError(rc, err.value.decode())
     return CohortClusters(out)
@@ -203,6 +223,19 @@ class Cohort(object):
         out = C.POINTER(_ffi.CohortClusters)()
         err = C.create_string_buffer(512)
         rc = self._lib.rgx_cohort_cluster(self._h, matrix._h, C.byref(p), C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
+        return CohortClusters(out)
+
+    def refine(self, matrix, max_intron=0, min_reads=0, min_ratio=(0, 1), min_rows=1, min_total=0):
+        """The refined clusters of `matrix` on this cohort's device (rgx_cohort_refine): introns longer than max_intron take no part, junctions
+        with fewer than min_reads reads or less than min_ratio = (numerator, denominator) of their cluster's reads are removed, and the rest is
+        clustered again.  The matrix is found as in cluster()."""
+        p = _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total)
+        out = C.POINTER(_ffi.CohortClusters)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_refine(self._h, matrix._h, C.byref(p), C.byref(out), err, len(err))
         if rc != 0:
             raise RegtoolsError(rc, err.value.decode())
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))

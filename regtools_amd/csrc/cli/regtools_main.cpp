@@ -255,6 +255,12 @@ void cohort_usage(std::ostream &out) {
         << "\t\t\t per sample, laid out as LeafCutter's perind.counts.\n"
         << "\t\t-K INT\tKeep clusters of at least INT junctions. [1]\n"
         << "\t\t-T INT\tKeep clusters with at least INT reads over all samples. [0]\n"
+        << "\t\t-l INT\tThe longest intron that takes part in clustering. [0: no limit]\n"
+        << "\t\t-J INT\tJunctions with fewer than INT reads over all samples are removed from their cluster. [0]\n"
+        << "\t\t-p DEC\tJunctions that carry less than this share of their cluster's reads are removed; a decimal in [0, 1] with at most\n"
+        << "\t\t\t nine digits behind the point, read exactly. [0]\n"
+        << "\t\t\t With -l, -J or -p the clusters are refined: those junctions leave and the rest is clustered again, as LeafCutter does\n"
+        << "\t\t\t (its customary settings: -l 100000 -J 5 -p 0.001 -K 2 -T 30).\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -263,6 +269,22 @@ void cohort_usage(std::ostream &out) {
 }
 
 struct CohortInput { std::string path, name; };
+
+// -p: "digits[.digits]" read exactly as num / 10^k, k <= 9, value in [0, 1]
+bool cohort_parse_ratio(const char *arg, uint32_t *num, uint32_t *den) {
+    const std::string s = arg;
+    const size_t dot = s.find('.');
+    const std::string whole = s.substr(0, dot), frac = dot == std::string::npos ? "" : s.substr(dot + 1);
+    if (whole.empty() && frac.empty()) return false;
+    if (whole.size() > 9 || frac.size() > 9) return false;
+    for (char ch : whole + frac) if (ch < '0' || ch > '9') return false;
+    uint64_t d = 1, v = 0;
+    for (char ch : whole) v = v * 10 + (uint64_t)(ch - '0');
+    for (char ch : frac) { v = v * 10 + (uint64_t)(ch - '0'); d *= 10; }
+    if (v > d) return false;
+    *num = (uint32_t)v; *den = (uint32_t)d;
+    return true;
+}
 
 std::string cohort_default_name(const std::string &path) {
     std::string b = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
@@ -309,10 +331,13 @@ int junctions_cohort(int argc, char **argv) {
         rgx_cohort_params_default(&cp);
         rgx_cluster_params kp;
         rgx_cluster_params_default(&kp);
+        rgx_refine_params rp;
+        rgx_refine_params_default(&rp);
+        bool refine = false;
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -328,6 +353,11 @@ int junctions_cohort(int argc, char **argv) {
                 case 'k': clusters = optarg; break;
                 case 'K': kp.min_rows = (uint32_t)atoi(optarg); break;
                 case 'T': kp.min_total = (uint64_t)atoll(optarg); break;
+                case 'l': rp.max_intron = (uint32_t)atoi(optarg); refine = true; break;
+                case 'J': rp.min_reads = (uint64_t)atoll(optarg); refine = true; break;
+                case 'p':
+                    if (!cohort_parse_ratio(optarg, &rp.ratio_num, &rp.ratio_den)) throw std::runtime_error("Unrecognized ratio argument!\n\n");
+                    refine = true; break;
                 case 's': {
                     std::string s = optarg;
                     if (s == "XS") o.strandness = 0; else if (s == "RF") o.strandness = 1; else if (s == "FR") o.strandness = 2;
@@ -401,7 +431,9 @@ int junctions_cohort(int argc, char **argv) {
         rgx_cohort_matrix *m = nullptr;
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
-        if (ok && clusters != "NA" && rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
+        if (ok && clusters != "NA" && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
+            failure = err; ok = false; }
         if (!ok) {
             if (m) rgx_cohort_matrix_free(m);
             rgx_pipeline_destroy(pl);                       // (runs what is still queued to its end: the buffers below were promised to it)
@@ -437,8 +469,9 @@ int junctions_cohort(int argc, char **argv) {
             fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
                     (unsigned long long)m->n_triples, (unsigned long long)m->n, m->ms_add_total, m->ms_finish);
         if (cl && getenv("REGTOOLS_AMD_STATS"))
-            fprintf(stderr, "[regtools_amd] clusters: %llu of %llu components kept, %u rounds, %.3f ms\n", (unsigned long long)cl->n_clusters,
-                    (unsigned long long)cl->n_components, cl->n_rounds, cl->ms_cluster);
+            fprintf(stderr, "[regtools_amd] clusters: %llu of %llu components kept, %u rounds, %.3f ms, %llu rows over the intron limit, %llu weak\n",
+                    (unsigned long long)cl->n_clusters, (unsigned long long)cl->n_components, cl->n_rounds, cl->ms_cluster,
+                    (unsigned long long)cl->n_ineligible, (unsigned long long)cl->n_weak);
         rgx_cohort_clusters_free(cl);
         rgx_cohort_matrix_free(m);
         rgx_cohort_destroy(co);

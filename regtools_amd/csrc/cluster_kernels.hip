@@ -185,6 +185,83 @@ __global__ __launch_bounds__(256) void k_cluster_cs_begin(const uint32_t *__rest
     cs_begin[c] = lo;
 }
 
+// ---- refinement (rgx_cohort_refine): rows leave the graph, the sorted orders are compacted to the rows that stay, the search runs again ----------
+// alive[i] = the row takes part in clustering at all (max_intron 0: every row)
+__global__ __launch_bounds__(256) void k_refine_eligible(const uint32_t *__restrict__ start, const uint32_t *__restrict__ end, uint32_t n,
+                                                         uint32_t max_intron, uint32_t *__restrict__ alive) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    alive[i] = (max_intron == 0 || end[i] - start[i] <= max_intron) ? 1u : 0u;
+}
+
+// flag[j] = alive[order[j]]: the flag seen through the permutation, for the scan that gives every survivor its place
+__global__ __launch_bounds__(256) void k_refine_flag(const uint32_t *__restrict__ order, const uint32_t *__restrict__ alive, uint32_t k,
+                                                     uint32_t *__restrict__ flag) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j < k) flag[j] = alive[order[j]];
+}
+
+// out[pos[j]] = order[j] for the survivors (pos = exclusive scan of the flags: below the survivors' count, which is at most k).  Stable: a
+// sorted order stays sorted.
+__global__ __launch_bounds__(256) void k_refine_scatter(const uint32_t *__restrict__ order, const uint32_t *__restrict__ alive,
+                                                        const uint32_t *__restrict__ pos, uint32_t k, uint32_t *__restrict__ out) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const uint32_t r = order[j];
+    if (alive[r]) out[pos[j]] = r;
+}
+
+// k_cluster_edges over a compacted order whose length only the device knows: *n_live (at most cap) positions hold rows, the slots behind them
+// become self loops of row 0
+__global__ __launch_bounds__(256) void k_refine_edges(const uint32_t *__restrict__ perm, const uint32_t *__restrict__ n_live,
+                                                      const uint32_t *__restrict__ tid, const uint32_t *__restrict__ cls,
+                                                      const uint32_t *__restrict__ site, uint32_t cap, uint32_t *__restrict__ ea,
+                                                      uint32_t *__restrict__ eb) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= cap) return;
+    uint32_t r0 = 0, r1 = 0;
+    if (i < min(*n_live, cap)) {
+        r0 = r1 = perm[i];
+        if (i) { const uint32_t q = perm[i - 1]; if (tid[q] == tid[r1] && cls[q] == cls[r1] && site[q] == site[r1]) r0 = q; }
+    }
+    ea[i] = r0; eb[i] = r1;
+}
+
+// k_cluster_tally over the rows that are alive (cnt may be null: stage 1 needs the totals only)
+__global__ __launch_bounds__(256) void k_refine_tally(const uint32_t *__restrict__ label, const unsigned long long *__restrict__ total,
+                                                      const uint32_t *__restrict__ alive, uint32_t n, uint32_t *cnt, unsigned long long *tot) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !alive[i]) return;
+    const uint32_t r = label[i];
+    if (cnt) atomicAdd(&cnt[r], 1u);
+    atomicAdd(&tot[r], total[i]);
+}
+
+// The weak test: an alive row leaves when total < min_reads or total * den < num * T, T = tot[its root].  Both products are taken whole (a 64-bit
+// factor times a 32-bit one: 96 bits, as a high and a low 64-bit word) and compared exactly; equality stays.  Lane i is the only writer of alive[i].
+__global__ __launch_bounds__(256) void k_refine_mark(const uint32_t *__restrict__ label, const unsigned long long *__restrict__ total,
+                                                     const unsigned long long *__restrict__ tot, uint32_t n, unsigned long long min_reads,
+                                                     uint32_t num, uint32_t den, uint32_t *__restrict__ alive) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !alive[i]) return;
+    const unsigned long long t = total[i], T = tot[label[i]];
+    const unsigned long long l_hi = __umul64hi(t, (unsigned long long)den), l_lo = t * den;
+    const unsigned long long r_hi = __umul64hi(T, (unsigned long long)num), r_lo = T * num;
+    const bool below = l_hi < r_hi || (l_hi == r_hi && l_lo < r_lo);
+    if (t < min_reads || below) alive[i] = 0;
+}
+
+// k_cluster_roots where a row that is not alive is no root and is not kept
+__global__ __launch_bounds__(256) void k_refine_roots(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
+                                                      const unsigned long long *__restrict__ tot, const uint32_t *__restrict__ alive, uint32_t n,
+                                                      uint32_t min_rows, unsigned long long min_total, uint32_t *__restrict__ is_root,
+                                                      uint32_t *__restrict__ keep) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool root = alive[i] != 0 && label[i] == i;
+    is_root[i] = root; keep[i] = root && cnt[i] >= min_rows && tot[i] >= min_total;
+}
+
 static inline dim3 cluster_grid(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 void launch_cluster_class(const uint8_t *strand, uint32_t n, uint32_t *cls, hipStream_t st) {
@@ -246,6 +323,35 @@ void launch_cluster_cs_sum(const uint32_t *perm, const uint32_t *e_cluster, cons
 }
 void launch_cluster_cs_begin(const uint32_t *seg_cluster, uint32_t n_seg, uint32_t n_clusters, unsigned long long *cs_begin, hipStream_t st) {
     hipLaunchKernelGGL(k_cluster_cs_begin, cluster_grid((uint64_t)n_clusters + 1), dim3(256), 0, st, seg_cluster, n_seg, n_clusters, cs_begin);
+}
+
+void launch_refine_eligible(const uint32_t *start, const uint32_t *end, uint32_t n, uint32_t max_intron, uint32_t *alive, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_refine_eligible, cluster_grid(n), dim3(256), 0, st, start, end, n, max_intron, alive);
+}
+void launch_refine_compact(const uint32_t *order, uint32_t k, const uint32_t *alive, uint32_t *pos, uint32_t *out, uint32_t *n_live, uint32_t *tmp,
+                           hipStream_t st) {
+    if (!k) { launch_scan_u32(nullptr, nullptr, 0, n_live, tmp, st); return; }
+    hipLaunchKernelGGL(k_refine_flag, cluster_grid(k), dim3(256), 0, st, order, alive, k, pos);
+    launch_scan_u32(pos, pos, k, n_live, tmp, st);
+    hipLaunchKernelGGL(k_refine_scatter, cluster_grid(k), dim3(256), 0, st, order, alive, pos, k, out);
+}
+void launch_refine_edges(const uint32_t *perm, const uint32_t *n_live, const uint32_t *tid, const uint32_t *cls, const uint32_t *site, uint32_t cap,
+                         uint32_t *ea, uint32_t *eb, hipStream_t st) {
+    if (cap) hipLaunchKernelGGL(k_refine_edges, cluster_grid(cap), dim3(256), 0, st, perm, n_live, tid, cls, site, cap, ea, eb);
+}
+void launch_refine_tally(const uint32_t *label, const unsigned long long *total, const uint32_t *alive, uint32_t n, uint32_t *cnt,
+                         unsigned long long *tot, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_refine_tally, cluster_grid(n), dim3(256), 0, st, label, total, alive, n, cnt, tot);
+}
+void launch_refine_mark(const uint32_t *label, const unsigned long long *total, const unsigned long long *tot, uint32_t n, uint64_t min_reads,
+                        uint32_t ratio_num, uint32_t ratio_den, uint32_t *alive, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_refine_mark, cluster_grid(n), dim3(256), 0, st, label, total, tot, n, (unsigned long long)min_reads, ratio_num, ratio_den,
+                              alive);
+}
+void launch_refine_roots(const uint32_t *label, const uint32_t *cnt, const unsigned long long *tot, const uint32_t *alive, uint32_t n, uint32_t min_rows,
+                         uint64_t min_total, uint32_t *is_root, uint32_t *keep, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_refine_roots, cluster_grid(n), dim3(256), 0, st, label, cnt, tot, alive, n, min_rows, (unsigned long long)min_total,
+                              is_root, keep);
 }
 
 }  // namespace rgx

@@ -352,5 +352,21 @@ void launch_cluster_cs_heads(const uint32_t *perm, const uint32_t *e_cluster, co
 void launch_cluster_cs_sum(const uint32_t *perm, const uint32_t *e_cluster, const uint32_t *e_sample, const uint32_t *e_count, const uint32_t *seg_start,
                            uint32_t n, uint32_t n_seg, uint32_t *seg_cluster, uint32_t *cs_sample, unsigned long long *cs_total, hipStream_t st);
 void launch_cluster_cs_begin(const uint32_t *seg_cluster, uint32_t n_seg, uint32_t n_clusters, unsigned long long *cs_begin /* n_clusters + 1 */, hipStream_t st);
+// Refinement (rgx_cohort_refine): alive[i] = 1 while row i takes part.  eligible: end - start <= max_intron (0: every row).  compact: out = the
+// entries of order[0 .. k) whose row is alive, in order (stable: a sorted order stays sorted); pos = k words of scratch, *n_live (device) = how
+// many; out holds up to k words.  edges: launch_cluster_edges over the first *n_live (device) entries of perm, self loops in the slots up to cap.
+// tally / roots: their cluster namesakes over the alive rows only (cnt may be null in tally).  mark: an alive row whose total is below min_reads,
+// or for which total * ratio_den < ratio_num * tot[label] on the whole products, stops being alive.
+void launch_refine_eligible(const uint32_t *start, const uint32_t *end, uint32_t n, uint32_t max_intron, uint32_t *alive, hipStream_t st);
+void launch_refine_compact(const uint32_t *order, uint32_t k, const uint32_t *alive, uint32_t *pos, uint32_t *out, uint32_t *n_live, uint32_t *tmp,
+                           hipStream_t st);
+void launch_refine_edges(const uint32_t *perm, const uint32_t *n_live, const uint32_t *tid, const uint32_t *cls, const uint32_t *site, uint32_t cap,
+                         uint32_t *ea, uint32_t *eb, hipStream_t st);
+void launch_refine_tally(const uint32_t *label, const unsigned long long *total, const uint32_t *alive, uint32_t n, uint32_t *cnt,
+                         unsigned long long *tot, hipStream_t st);
+void launch_refine_mark(const uint32_t *label, const unsigned long long *total, const unsigned long long *tot, uint32_t n, uint64_t min_reads,
+                        uint32_t ratio_num, uint32_t ratio_den, uint32_t *alive, hipStream_t st);
+void launch_refine_roots(const uint32_t *label, const uint32_t *cnt, const unsigned long long *tot, const uint32_t *alive, uint32_t n, uint32_t min_rows,
+                         uint64_t min_total, uint32_t *is_root, uint32_t *keep, hipStream_t st);
 
 }  // namespace rgx

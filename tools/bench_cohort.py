@@ -12,6 +12,12 @@
                     rgx_cohort_cluster_host on the same matrix and the ms_finish of the same run; the results are compared word for word; bytes
                     moved per count entry by step 4 (counted from the passes, see cluster_bytes_per_entry) over ms_cluster against 8 TB/s
 
+  --refine          rgx_cohort_refine (ms_cluster of its result) on the same cohorts, beside rgx_cohort_cluster on the same matrix in
+                    the same process and rgx_cohort_refine_host: first and warm calls on both paths, the removal counts and rounds, and whether
+                    every result was identical word for word between the paths and to the twin.  A size may end in ":heavy" (a sparse cohort with
+                    heavy-tailed counts: a row counts up to 8,192 times as much in its home sample), the case in which the refinement bites;
+                    --refine-params "max_intron,min_reads,num/den,min_rows,min_total" (default LeafCutter's customary 100000,5,1/1000,2,30)
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -36,7 +42,8 @@ class Sample(object):
 
 
 MIXES = {"sparse": (5, 5, 10 / 3.0),      # a fifth of a sample's keys are in every sample, a fifth in no other, the rest drawn from a pool of 2 x rows
-         "shared": (6, 150, 5.0)}          # a sixth in every sample, 1 in 150 private, the rest from a pool of 5 x as many: most keys are in dozens of samples
+         "shared": (6, 150, 5.0),          # a sixth in every sample, 1 in 150 private, the rest from a pool of 5 x as many: most keys are in dozens of samples
+         "heavy": (5, 5, 10 / 3.0)}        # sparse, with heavy-tailed counts and long-range junctions (make_sample): the input a refinement bites on
 
 
 def make_sample(g, rows, rng, mix):
@@ -56,6 +63,14 @@ def make_sample(g, rows, rng, mix):
     t[:, 3] = start - ANCHOR - (ids * 3 + g * 5) % 20
     t[:, 4] = end + ANCHOR + (ids * 7 + g * 11) % 20
     t[:, 5] = 1 + (ids * 7 + g) % 9
+    if mix == "heavy":
+        # one key in 16 shares its start with a key far away on the contig (a long intron that ties clusters together), and a key counts up to
+        # 8,192 times as much in its home sample (ids % 64 == g % 64)
+        far = ids % 16 == 0
+        end = np.where(far, start + 150_000 + 3 * (ids % 4096), end)
+        t[:, 2], t[:, 4] = end, end + ANCHOR + (ids * 7 + g * 11) % 20
+        boost = np.uint64(1) << (((ids.astype(np.uint64) * np.uint64(2654435761)) >> np.uint64(7)) % np.uint64(14))
+        t[:, 5] = np.where(ids % 64 == g % 64, t[:, 5].astype(np.uint64) * boost, t[:, 5]).astype(np.uint32)
     t[:, 10] = np.where(ids % 3 == 0, ord("-"), ord("+"))
     proto = _ffi.JunctionTable()
     arr = (C.c_char_p * 23)(*[b"c%02d" % k for k in range(23)])
@@ -185,6 +200,62 @@ def part_cluster(a):
         print(json.dumps(line), flush=True)
 
 
+def part_refine(a):
+    import regtools_amd
+    from regtools_amd import _ffi, cohort
+    f = a.refine_params.split(",")
+    num, den = [int(x) for x in f[2].split("/")]
+    kw = dict(max_intron=int(f[0]), min_reads=int(f[1]), min_ratio=(num, den), min_rows=int(f[3]), min_total=int(f[4]))
+    ctx = regtools_amd.Context(0)
+    for size in a.sizes.split(","):
+        shape, _, mix = size.partition(":")
+        mix = mix or "sparse"
+        n_samples, rows = [int(x) for x in shape.lower().split("x")]
+        rng = np.random.default_rng(3)
+        tables = [make_sample(g, rows, rng, mix) for g in range(n_samples)]
+        co = regtools_amd.Cohort(ctx=ctx)
+        for g, t in enumerate(tables):
+            co.add(Sample(t), "s%04d" % g)
+        for _ in range(2):                           # (the second finish is a warm one)
+            m = co.finish()
+        other = regtools_amd.Cohort(ctx=ctx)
+        plain, in_hbm, uploaded, same_paths, results = [], [], [], True, []
+        for _ in range(a.reps):                      # cluster and refine alternate on the same matrix, in the same process
+            cl = co.cluster(m, min_rows=kw["min_rows"], min_total=kw["min_total"])
+            plain.append(round(cl.ms_cluster, 3))
+            rf = co.refine(m, **kw)
+            in_hbm.append(round(rf.ms_cluster, 3))
+            up = other.refine(m, **kw)
+            uploaded.append(round(up.ms_cluster, 3))
+            same_paths &= (rf.n_ineligible, rf.n_weak, rf.n_components) == (up.n_ineligible, up.n_weak, up.n_components) and all(
+                np.array_equal(getattr(rf, k), getattr(up, k)) for k in CLUSTER_ARRAYS)
+            results.append(rf)
+        assert co.cluster_paths == [1, 1] * a.reps and other.cluster_paths == [0] * a.reps
+        sizes, plain_sizes = np.diff(rf.cl_begin), np.diff(cl.cl_begin)
+        line = {"part": "refine", "mix": mix, "samples": n_samples, "rows_per_sample": rows, "rows": m.n, "count_entries": int(m.row_begin[-1]), "params": kw,
+                "n_ineligible": rf.n_ineligible, "n_weak": rf.n_weak, "components": rf.n_components, "clusters": rf.n_clusters,
+                "largest_cluster_rows": int(sizes.max()) if len(sizes) else 0, "rows_clustered": int(rf.cl_begin[-1]),
+                "unrefined_clusters": cl.n_clusters, "unrefined_largest_cluster_rows": int(plain_sizes.max()) if len(plain_sizes) else 0,
+                "n_rounds": rf.n_rounds, "n_rounds_cluster": cl.n_rounds, "ms_refine_in_hbm": in_hbm, "ms_refine_uploaded": uploaded, "ms_cluster": plain,
+                "ms_refine_best_warm": min(in_hbm[1:] or in_hbm), "ms_cluster_best_warm": min(plain[1:] or plain), "paths_equal_every_time": bool(same_paths)}
+        assert same_paths, "the two paths differ"
+        if not a.no_host:
+            h = cohort.refine_host(m, **kw)
+            line["ms_refine_host"] = round(h.ms_cluster, 1)
+            line["device_over_host"] = round(h.ms_cluster / line["ms_refine_best_warm"], 1)
+            same = all((r.n_clusters, r.n_components, r.n_ineligible, r.n_weak) == (h.n_clusters, h.n_components, h.n_ineligible, h.n_weak) and all(
+                np.array_equal(getattr(r, k), getattr(h, k)) for k in CLUSTER_ARRAYS) for r in results)
+            line["identical_to_host_every_time"] = bool(same)
+            assert same, "the device's refined clusters differ from the host twin's"
+            h.close()
+        for r in results:
+            r.close()
+        m.close(); co.close(); other.close()
+        for t in tables:
+            _ffi.lib().rgx_table_free(t)
+        print(json.dumps(line), flush=True)
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -239,6 +310,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", default="all", choices=["all", "pipeline", "finish"])
     ap.add_argument("--cluster", action="store_true", help="the cluster part, alone")
+    ap.add_argument("--refine", action="store_true", help="the refine part, alone")
+    ap.add_argument("--refine-params", default="100000,5,1/1000,2,30", help="max_intron,min_reads,num/den,min_rows,min_total")
     ap.add_argument("--reads", type=int, default=50_000_000)
     ap.add_argument("--files", type=int, default=24)
     ap.add_argument("--reps", type=int, default=5)
@@ -247,6 +320,8 @@ def main():
     a = ap.parse_args()
     if a.cluster:
         return part_cluster(a)
+    if a.refine:
+        return part_refine(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
