@@ -371,6 +371,72 @@ int  rgx_cohort_refine(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_ref
 /* Host twin: union-find twice and unsigned __int128 for the ratio test, no device.  NOT a fallback. */
 int  rgx_cohort_refine_host(const rgx_cohort_matrix *m, const rgx_refine_params *p, rgx_cohort_clusters **out, char *err, size_t errlen);
 
+/* -----------------------------------------------------------------------------------------------------
+ * The splicing phenotype table of a clustered cohort: per clustered junction and sample the intron-excision ratio, filtered, standardised
+ * across samples and rank-normalised across junctions -- the table an sQTL mapper takes.  MODELLED ON LeafCutter's
+ * prepare_phenotype_table.py, which is not available to this project: nothing here was compared against it, its means behind the
+ * imputation are computed in another order, and its per-chromosome files and principal components are not written.
+ *   input                 a matrix m and a cluster result cl OF THAT MATRIX (rgx_cohort_cluster, rgx_cohort_refine or their twins);
+ *                         cl->n_rows != m->n, or a cluster number at or above cl->n_clusters, is RGX_ERR_ARG.  S = m->n_samples
+ *   parameters            na_num / na_den: the share of missing samples a row may have (na_den == 0 or na_num > na_den is RGX_ERR_ARG);
+ *                         min_sd: the least deviation a row must show (negative or NaN is RGX_ERR_ARG).  Defaults 4 / 10 and 0.005
+ *   candidates            the rows with cl->cluster[i] != RGX_NO_CLUSTER, n_clustered of them
+ *   ratio                 for candidate row i of cluster c and sample s: num = the row's count in s, den = the cluster's cs_total in s,
+ *                         either 0 where the CSR has no entry.  The entry is MISSING when den == 0; otherwise
+ *                         x = ((double)num + 0.5) / ((double)den + 0.5)
+ *   summation order       a sum over a row's present samples is 64 partials P[l], each starting at +0.0 and taking the present samples
+ *                         with s % 64 == l in ascending s; then for off = 32, 16, 8, 4, 2, 1: P[l] = P[l] + P[l + off] for l < off; the
+ *                         sum is P[0].  (A wave's strided loop and its __shfl_down halving.)  Part of the contract: mean and sd are
+ *                         the same bits wherever they are computed
+ *   row statistics        n_na = the missing samples; mean = sum(x) / (double)(S - n_na); sd = sqrt(sum(d * d) / (double)S), d = x - mean
+ *                         over the present samples (a missing entry is imputed with the mean and adds nothing); d * d is a rounded
+ *                         product, never fused into the add
+ *   row filters           in this order: a row is dropped as missing when n_na == S or (uint64)n_na * na_den > (uint64)S * na_num
+ *                         (n_drop_na); a row that stays is dropped as flat when !(sd > 0) or sd < min_sd (n_drop_sd); K rows are
+ *                         kept, in matrix order
+ *   standardised entry    z = (x - mean) / sd for a present entry, +0.0 for a missing one
+ *   rank                  inside each sample's column over the K kept rows, z ascending, -0.0 equal to +0.0 (no NaN can occur):
+ *                         rank2 = lo + hi, the 1-based first and last place of the entry's run of equal values -- twice its average
+ *                         rank, an integer in [2, 2 K]
+ *   quantile              rgx_pheno_quantile(rank2, K) = the standard normal quantile of rank2 / (2 (K + 1)), evaluated on the HOST by
+ *                         Wichura's rational approximation AS 241 (PPND16): it needs log, which does not round alike on host and
+ *                         device, and depends on (rank2, K) alone.  The result carries the integers; the text carries the quantiles
+ *   limits                n_clustered * S at most 2^32 - 2^16 (RGX_ERR_ARG beyond, before any launch); RGX_ERR_DEVICE when workspace
+ *                         cannot be had; no candidates, S == 0 or K == 0 give empty arrays
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t na_num, na_den;        /* a row is dropped when n_na * na_den > S * na_num */
+                 double   min_sd;                /* ... or when its sd is below this (or not above 0) */
+} rgx_pheno_params;
+/* Structure-of-arrays, owned by the library (rgx_cohort_phenotypes_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t  *row;             /* K: the kept rows of m, ascending */
+    uint32_t  *n_na;            /* K: missing samples */
+    double    *mean, *sd;       /* K */
+    uint32_t  *rank2;           /* K * S, row-major: twice the average rank of the entry in its sample's column */
+    /* statistics */
+    uint64_t   n_clustered, n_drop_na, n_drop_sd;
+    double     ms_pheno;        /* this call, wall, up to the result being in host memory */
+} rgx_pheno_table;
+void rgx_pheno_params_default(rgx_pheno_params *p);                         /* 4, 10, 0.005 */
+/* On the cohort's device and stream; the matrix is found as rgx_cohort_cluster finds it (rgx_cohort_cluster_path reports which way).  A wave
+ * per row for the statistics, a scan for the kept rows' places, one stable radix sort of the K * S entries by (sample, z), head flags and a scan
+ * for the tie runs. */
+int  rgx_cohort_phenotypes(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_params *p,
+                           rgx_pheno_table **out, char *err, size_t errlen);
+/* Host twin: the same summation order in plain C++ and std::stable_sort per column, no device.  NOT a fallback. */
+int  rgx_cohort_phenotypes_host(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_params *p,
+                                rgx_pheno_table **out, char *err, size_t errlen);
+void rgx_cohort_phenotypes_free(rgx_pheno_table *ph);
+/* rank2 in [1, 2 K + 1]; anything else gives NaN. */
+double rgx_pheno_quantile(uint32_t rank2, uint64_t n_rows);
+/* "#Chr\tstart\tend\tID" and one "\t<sample name>" per sample, then one line per kept row: contig, start, end, the row's ID in
+ * rgx_cohort_format_cluster_counts ("<contig>:<start>:<end>:clu_<k>_<s>") and per sample a tab and the quantile as %.17g.  ph must come from
+ * (m, cl); 0 when the three do not fit together.  Buffer protocol of rgx_cohort_format_counts. */
+size_t rgx_cohort_format_phenotypes(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, char *buf,
+                                    size_t cap);
+
 /* Library/build identification: "regtools_amd <version> gfx950". */
 const char *rgx_version(void);
 

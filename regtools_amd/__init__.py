@@ -5,7 +5,7 @@ extractor.py (host mirror of the reference's JunctionsExtractor interface), coho
 CisSpliceEffectsAssociator / VariantsAnnotator / JunctionsAnnotator), synth.py (synthetic inputs), distributed.py (shard merge).
 """
 from .extractor import Context, Junction, JunctionsExtractor, PinnedBuffer, Pipeline, RegtoolsError, extract_multi, junctions_extract  # noqa: F401
-from .cohort import Cohort, CohortClusters, CohortMatrix  # noqa: F401
+from .cohort import Cohort, CohortClusters, CohortMatrix, CohortPhenotypes  # noqa: F401
 from .cse import (CisSpliceEffectsAssociator, CisSpliceEffectsIdentifier, JunctionsAnnotator, VariantsAnnotator,  # noqa: F401
                   cis_splice_effects_identify)
 

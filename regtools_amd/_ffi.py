@@ -55,7 +55,9 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by",
            "rgx_cluster_params_default", "rgx_cohort_cluster", "rgx_cohort_cluster_path", "rgx_cohort_cluster_host", "rgx_cohort_clusters_free",
            "rgx_cohort_format_cluster_counts", "rgx_k_components",
-           "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host"]
+           "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host",
+           "rgx_pheno_params_default", "rgx_cohort_phenotypes", "rgx_cohort_phenotypes_host", "rgx_cohort_phenotypes_free", "rgx_pheno_quantile",
+           "rgx_cohort_format_phenotypes"]
 
 
 class CohortParams(C.Structure):
@@ -87,6 +89,16 @@ class CohortClusters(C.Structure):
 class RefineParams(C.Structure):
     _fields_ = [("max_intron", C.c_uint32), ("min_reads", C.c_uint64), ("ratio_num", C.c_uint32), ("ratio_den", C.c_uint32),
                 ("min_rows", C.c_uint32), ("min_total", C.c_uint64)]
+
+
+class PhenoParams(C.Structure):
+    _fields_ = [("na_num", C.c_uint32), ("na_den", C.c_uint32), ("min_sd", C.c_double)]
+
+
+class PhenoTable(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("row", C.POINTER(C.c_uint32)), ("n_na", C.POINTER(C.c_uint32)),
+                ("mean", C.POINTER(C.c_double)), ("sd", C.POINTER(C.c_double)), ("rank2", C.POINTER(C.c_uint32)),
+                ("n_clustered", C.c_uint64), ("n_drop_na", C.c_uint64), ("n_drop_sd", C.c_uint64), ("ms_pheno", C.c_double)]
 
 
 class IdentifyParams(C.Structure):
@@ -236,6 +248,14 @@ def lib():
         L.rgx_refine_params_default.argtypes = [P(RefineParams)]
         L.rgx_cohort_refine.argtypes = [C.c_void_p, P(CohortMatrix), P(RefineParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
         L.rgx_cohort_refine_host.argtypes = [P(CohortMatrix), P(RefineParams), P(P(CohortClusters)), C.c_char_p, C.c_size_t]
+        L.rgx_pheno_params_default.argtypes = [P(PhenoParams)]
+        L.rgx_cohort_phenotypes.argtypes = [C.c_void_p, P(CohortMatrix), P(CohortClusters), P(PhenoParams), P(P(PhenoTable)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_phenotypes_host.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoParams), P(P(PhenoTable)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_phenotypes_free.argtypes = [P(PhenoTable)]
+        L.rgx_pheno_quantile.argtypes = [C.c_uint32, C.c_uint64]
+        L.rgx_pheno_quantile.restype = C.c_double
+        L.rgx_cohort_format_phenotypes.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_phenotypes.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -154,6 +154,77 @@ def refine_host(matrix, max_intron=0, min_reads=0, min_ratio=(0, 1), min_rows=1,
     return CohortClusters(out)
 
 
+class CohortPhenotypes(object):
+    """rgx_pheno_table: the splicing phenotype table of a clustered matrix -- the kept rows, their missing samples, mean and sd of the
+    intron-excision ratio, and rank2 (K x S), twice the average rank of each standardised entry in its sample's column.  The array attributes
+    are numpy VIEWS of memory this object owns: copy what must outlive it."""
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        p = handle.contents
+        self.n_rows, self.n_samples = int(p.n_rows), int(p.n_samples)
+        self.n_clustered, self.n_drop_na, self.n_drop_sd, self.ms_pheno = int(p.n_clustered), int(p.n_drop_na), int(p.n_drop_sd), p.ms_pheno
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        K = self.n_rows
+        self.row, self.n_na = view(p.row, K, np.uint32), view(p.n_na, K, np.uint32)
+        self.mean, self.sd = view(p.mean, K, np.float64), view(p.sd, K, np.float64)
+        self.rank2 = view(p.rank2, K * self.n_samples, np.uint32).reshape(K, self.n_samples)
+
+    def quantiles(self):
+        """K x S float64: rgx_pheno_quantile of every entry (the numbers the text prints)."""
+        import numpy as np
+        q = self._lib.rgx_pheno_quantile
+        table = np.array([q(r, self.n_rows) for r in range(2 * self.n_rows + 1)], np.float64) if self.n_rows else np.zeros(1)
+        return table[self.rank2]
+
+    def text(self, matrix, clusters):
+        """The table as text: "#Chr start end ID" and the samples, one line per kept row.  matrix and clusters are what this came from."""
+        fn = self._lib.rgx_cohort_format_phenotypes
+        n = fn(matrix._h, clusters._h, self._h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, clusters._h, self._h, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_phenotypes_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def quantile(rank2, n_rows):
+    """rgx_pheno_quantile: the standard normal quantile of rank2 / (2 (n_rows + 1)), on the host."""
+    return _ffi.lib().rgx_pheno_quantile(rank2, n_rows)
+
+
+def _pheno_params(max_missing, min_sd):
+    p = _ffi.PhenoParams()
+    _ffi.lib().rgx_pheno_params_default(C.byref(p))
+    (p.na_num, p.na_den), p.min_sd = max_missing, min_sd
+    return p
+
+
+def phenotypes_host(matrix, clusters, max_missing=(4, 10), min_sd=0.005):
+    """rgx_cohort_phenotypes_host: the phenotype table of a CohortMatrix and its CohortClusters by the library's plain C++ twin, no device
+    involved.  max_missing is an exact fraction (numerator, denominator)."""
+    p = _pheno_params(max_missing, min_sd)
+    out = C.POINTER(_ffi.PhenoTable)()
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_phenotypes_host(matrix._h, clusters._h, C.byref(p), C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortPhenotypes(out)
+
+
 def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1):
     """rgx_cohort_merge_host over the tables the extractors hold (each with its own min_anchor_length_): no device involved."""
     lib = _ffi.lib()
@@ -240,6 +311,19 @@ class Cohort(object):
             raise RegtoolsError(rc, err.value.decode())
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
         return CohortClusters(out)
+
+    def phenotypes(self, matrix, clusters, max_missing=(4, 10), min_sd=0.005):
+        """The splicing phenotype table of `matrix` and its `clusters` on this cohort's device (rgx_cohort_phenotypes): intron-excision ratios,
+        rows dropped when more than max_missing = (numerator, denominator) of the samples have no reads on the cluster or when their sd is
+        below min_sd, each row standardised, each sample's column ranked.  The matrix is found as in cluster()."""
+        p = _pheno_params(max_missing, min_sd)
+        out = C.POINTER(_ffi.PhenoTable)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_phenotypes(self._h, matrix._h, clusters._h, C.byref(p), C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
+        return CohortPhenotypes(out)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

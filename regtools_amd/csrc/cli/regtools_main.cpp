@@ -261,6 +261,11 @@ void cohort_usage(std::ostream &out) {
         << "\t\t\t nine digits behind the point, read exactly. [0]\n"
         << "\t\t\t With -l, -J or -p the clusters are refined: those junctions leave and the rest is clustered again, as LeafCutter does\n"
         << "\t\t\t (its customary settings: -l 100000 -J 5 -p 0.001 -K 2 -T 30).\n"
+        << "\t\t-q FILE\tThe phenotype table for sQTL mapping: per clustered junction and sample the intron-excision ratio, standardised\n"
+        << "\t\t\t across samples and rank-normalised across junctions, modelled on LeafCutter's prepare_phenotype_table.py.\n"
+        << "\t\t\t The clusters are those -k writes with the same -K, -T, -l, -J and -p, whether or not -k is given.\n"
+        << "\t\t-x DEC\tJunctions whose cluster has no reads in more than this share of the samples are left out of -q; a decimal as -p. [0.4]\n"
+        << "\t\t-d DEC\tJunctions whose ratio varies by less than this standard deviation are left out of -q. [0.005]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -326,7 +331,9 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA", clusters = "NA";
+        std::string counts = "NA", clusters = "NA", phenotypes = "NA";
+        rgx_pheno_params qp;
+        rgx_pheno_params_default(&qp);
         rgx_cohort_params cp;
         rgx_cohort_params_default(&cp);
         rgx_cluster_params kp;
@@ -337,7 +344,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -358,6 +365,16 @@ int junctions_cohort(int argc, char **argv) {
                 case 'p':
                     if (!cohort_parse_ratio(optarg, &rp.ratio_num, &rp.ratio_den)) throw std::runtime_error("Unrecognized ratio argument!\n\n");
                     refine = true; break;
+                case 'q': phenotypes = optarg; break;
+                case 'x':
+                    if (!cohort_parse_ratio(optarg, &qp.na_num, &qp.na_den)) throw std::runtime_error("Unrecognized ratio argument!\n\n");
+                    break;
+                case 'd': {
+                    char *end = nullptr;
+                    qp.min_sd = strtod(optarg, &end);
+                    if (end == optarg || *end || !(qp.min_sd >= 0)) throw std::runtime_error("Unrecognized deviation argument!\n\n");
+                    break;
+                }
                 case 's': {
                     std::string s = optarg;
                     if (s == "XS") o.strandness = 0; else if (s == "RF") o.strandness = 1; else if (s == "FR") o.strandness = 2;
@@ -432,9 +449,12 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        if (ok && clusters != "NA" && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
+        if (ok && (clusters != "NA" || phenotypes != "NA") && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
+        rgx_pheno_table *ph = nullptr;
+        if (ok && phenotypes != "NA" && rgx_cohort_phenotypes(co, m, cl, &qp, &ph, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         if (!ok) {
+            if (cl) rgx_cohort_clusters_free(cl);
             if (m) rgx_cohort_matrix_free(m);
             rgx_pipeline_destroy(pl);                       // (runs what is still queued to its end: the buffers below were promised to it)
             for (Flight &f : fl) if (f.bam) rgx_host_free(f.bam);
@@ -449,7 +469,9 @@ int junctions_cohort(int argc, char **argv) {
         size_t nc = 0; std::unique_ptr<char[]> tsv;
         if (counts != "NA") { nc = rgx_cohort_format_counts(m, nullptr, 0); tsv.reset(new char[nc + 1]); rgx_cohort_format_counts(m, tsv.get(), nc); }
         size_t nk = 0; std::unique_ptr<char[]> ktx;
-        if (cl) { nk = rgx_cohort_format_cluster_counts(m, cl, nullptr, 0); ktx.reset(new char[nk + 1]); rgx_cohort_format_cluster_counts(m, cl, ktx.get(), nk); }
+        if (cl && clusters != "NA") { nk = rgx_cohort_format_cluster_counts(m, cl, nullptr, 0); ktx.reset(new char[nk + 1]); rgx_cohort_format_cluster_counts(m, cl, ktx.get(), nk); }
+        size_t nq = 0; std::unique_ptr<char[]> qtx;
+        if (ph) { nq = rgx_cohort_format_phenotypes(m, cl, ph, nullptr, 0); qtx.reset(new char[nq + 1]); rgx_cohort_format_phenotypes(m, cl, ph, qtx.get(), nq); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -459,10 +481,15 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + counts + "\n\n");
             short_write |= fwrite(tsv.get(), 1, nc, g) != nc; short_write |= fclose(g) != 0;
         }
-        if (cl) {
+        if (cl && clusters != "NA") {
             FILE *g = fopen(clusters.c_str(), "w");
             if (!g) throw std::runtime_error("Unable to write " + clusters + "\n\n");
             short_write |= fwrite(ktx.get(), 1, nk, g) != nk; short_write |= fclose(g) != 0;
+        }
+        if (ph) {
+            FILE *g = fopen(phenotypes.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + phenotypes + "\n\n");
+            short_write |= fwrite(qtx.get(), 1, nq, g) != nq; short_write |= fclose(g) != 0;
         }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
@@ -472,6 +499,11 @@ int junctions_cohort(int argc, char **argv) {
             fprintf(stderr, "[regtools_amd] clusters: %llu of %llu components kept, %u rounds, %.3f ms, %llu rows over the intron limit, %llu weak\n",
                     (unsigned long long)cl->n_clusters, (unsigned long long)cl->n_components, cl->n_rounds, cl->ms_cluster,
                     (unsigned long long)cl->n_ineligible, (unsigned long long)cl->n_weak);
+        if (ph && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] phenotypes: %llu rows kept of %llu clustered, %llu dropped as missing, %llu as flat, %.3f ms\n",
+                    (unsigned long long)ph->n_rows, (unsigned long long)ph->n_clustered, (unsigned long long)ph->n_drop_na,
+                    (unsigned long long)ph->n_drop_sd, ph->ms_pheno);
+        rgx_cohort_phenotypes_free(ph);
         rgx_cohort_clusters_free(cl);
         rgx_cohort_matrix_free(m);
         rgx_cohort_destroy(co);

@@ -73,6 +73,23 @@ int components_run(uint32_t n_vertices, const EdgeList *lists, int n_lists, uint
     return RGX_OK;
 }
 
+int cohort_matrix_image(rgx_cohort *co, const rgx_cohort_matrix *m, hipStream_t st, CohortImage *in, char *err, size_t errlen) {
+    const uint32_t n = (uint32_t)m->n, nnz = (uint32_t)m->row_begin[m->n];
+    const MatrixLayout L = matrix_layout(n, nnz);
+    uint8_t *base = co->image.as<uint8_t>();
+    if (((const MatrixBox *)m)->serial != co->image_serial) {           // m is the first member of its box
+        // the columns needed, where the image has them: total, row_begin, tid, start, end in front of the thick bounds; col_sample, val_count, strand behind n_with
+        if (co->cl_in.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
+            "regtools_amd: no device memory to upload the matrix (%u rows, %u counts)\n", n, nnz); }
+        base = co->cl_in.as<uint8_t>();
+        const uint8_t *h = (const uint8_t *)m->total - L.total;
+        HIP_TRY(hipMemcpyAsync(base, h, L.ts, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + L.col, h + L.col, L.strand + n - L.col, hipMemcpyHostToDevice, st));
+    }
+    *in = image_at(base, L);
+    return RGX_OK;
+}
+
 extern "C" void rgx_cluster_params_default(rgx_cluster_params *p) { if (p) { p->min_rows = 1; p->min_total = 0; } }
 
 extern "C" int rgx_cohort_cluster_path(rgx_cohort *co) { return co ? co->cluster_path : 0; }
@@ -127,18 +144,8 @@ struct ClusterRun {
             max_start = std::max(max_start, m->start[i]); max_end = std::max(max_end, m->end[i]); max_tid = std::max(max_tid, m->tid[i]);
             if (max_intron && m->end[i] - m->start[i] > max_intron) ++n_ineligible;
         }
-        const MatrixLayout L = matrix_layout(n, nnz);
-        uint8_t *base = co->image.as<uint8_t>();
-        if (!in_hbm) {
-            // the columns needed, where the image has them: total, row_begin, tid, start, end in front of the thick bounds; col_sample, val_count, strand behind n_with
-            if (co->cl_in.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
-                "regtools_amd: no device memory to upload the matrix (%u rows, %u counts)\n", n, nnz); }
-            base = co->cl_in.as<uint8_t>();
-            const uint8_t *h = (const uint8_t *)m->total - L.total;
-            HIP_TRY(hipMemcpyAsync(base, h, L.ts, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(base + L.col, h + L.col, L.strand + n - L.col, hipMemcpyHostToDevice, st));
-        }
-        in = image_at(base, L);
+        const int rc_image = cohort_matrix_image(co, m, st, &in, err, errlen);
+        if (rc_image != RGX_OK) return rc_image;
         mark("matrix in HBM");
 
         const size_t Nn = (size_t)n + 64;

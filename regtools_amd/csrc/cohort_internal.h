@@ -82,4 +82,10 @@ struct rgx_cohort {
     uint64_t image_serial = 0;
     int cluster_path = 0;
     DevBuf cl_in, cl_rows, cl_entries;
+    // rgx_cohort_phenotypes (cohort_pheno.cpp): the uploaded cluster result, the row and the entry workspace
+    DevBuf ph_in, ph_rows, ph_entries;
 };
+
+// cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the
+// columns the cluster and phenotype kernels need, uploaded on st into co->cl_in
+int cohort_matrix_image(rgx_cohort *co, const rgx_cohort_matrix *m, hipStream_t st, CohortImage *in, char *err, size_t errlen);

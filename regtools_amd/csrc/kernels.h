@@ -369,4 +369,24 @@ void launch_refine_mark(const uint32_t *label, const unsigned long long *total, 
 void launch_refine_roots(const uint32_t *label, const uint32_t *cnt, const unsigned long long *tot, const uint32_t *alive, uint32_t n, uint32_t min_rows,
                          uint64_t min_total, uint32_t *is_root, uint32_t *keep, hipStream_t st);
 
+// ---- the cohort's splicing phenotype table (pheno_kernels.hip; host side in cohort_pheno.cpp; per-entry arithmetic in pheno_core.h) ----------------
+// what the kernels read: the matrix's CSR image and, of its cluster result, the rows' clusters and the denominators
+struct PhenoIn { const uint32_t *cluster; const unsigned long long *row_begin; const uint32_t *col_sample, *val_count;
+                 const unsigned long long *cs_begin; const uint32_t *cs_sample; const unsigned long long *cs_total; };
+// per matrix row: missing samples, mean, sd (rows with a cluster only), keep = clustered and past both filters, drop_na = clustered and dropped as missing
+void launch_pheno_row_stats(PhenoIn in, uint32_t n, uint32_t n_samples, uint32_t na_num, uint32_t na_den, double min_sd, uint32_t *n_na, double *mean,
+                            double *sd, uint32_t *keep, uint32_t *drop_na, hipStream_t st);
+// pos = exclusive scan of keep: the kept rows' statistics side by side, in matrix order
+void launch_pheno_scatter(const uint32_t *keep, const uint32_t *pos, const uint32_t *n_na, const double *mean, const double *sd, uint32_t n,
+                          uint32_t *o_row, uint32_t *o_n_na, double *o_mean, double *o_sd, hipStream_t st);
+// entry k * n_samples + s: the order-preserving 64-bit key of its z as two words, and s; n_kept * n_samples below 2^32 - 2^16
+void launch_pheno_z(PhenoIn in, const uint32_t *o_row, const double *o_mean, const double *o_sd, uint32_t n_kept, uint32_t n_samples, uint32_t *z_lo,
+                    uint32_t *z_hi, uint32_t *e_sample, hipStream_t st);
+// perm = the n = n_kept * n_samples entries in stable order of (sample, z): head flags of the runs of equal z inside a column, then -- behind a scan
+// and launch_cohort_row_start -- rank2[entry] = first + last 1-based place of its run in its column
+void launch_pheno_tie_heads(const uint32_t *perm, const uint32_t *z_lo, const uint32_t *z_hi, uint32_t n, uint32_t n_kept, uint32_t *head,
+                            hipStream_t st);
+void launch_pheno_rank(const uint32_t *perm, const uint32_t *head, const uint32_t *seg_excl, const uint32_t *run_start, uint32_t n, uint32_t n_kept,
+                       uint32_t *rank2, hipStream_t st);
+
 }  // namespace rgx

@@ -18,6 +18,11 @@
                     heavy-tailed counts: a row counts up to 8,192 times as much in its home sample), the case in which the refinement bites;
                     --refine-params "max_intron,min_reads,num/den,min_rows,min_total" (default LeafCutter's customary 100000,5,1/1000,2,30)
 
+  --pheno           rgx_cohort_phenotypes (ms_pheno) on the same cohorts, behind rgx_cohort_refine with --refine-params: first and warm
+                    calls on both paths beside ms_cluster of the refinement in the same process and rgx_cohort_phenotypes_host, the kept rows and
+                    the two drop counts, and whether the paths and the twin were identical (integers, and mean / sd as bit patterns);
+                    --pheno-params "num/den,min_sd" (default 4/10,0.005); bytes moved per table entry (pheno_bytes_per_entry) over ms_pheno
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -256,6 +261,81 @@ def part_refine(a):
         print(json.dumps(line), flush=True)
 
 
+def pheno_bytes_per_entry(sample_bits):
+    """HBM bytes per entry of the K x S table that rgx_cohort_phenotypes reads and writes behind the row statistics: the keys (12
+    out), the sort -- per 8-bit pass a histogram read of the key (4) and a scatter of key and permutation in and out (16); four passes on the low
+    word, a gather (permutation 4 + word 4 in, 4 out) and four passes on the high word, a gather and the sample word's passes -- the tie heads (two
+    permutation entries and their two words each: 24 in, 4 out), their scan (4 in twice, 4 out), the run starts (8 in) and the ranks (permutation,
+    head, scan and two run starts: 20 in, 4 out).  The CSR lookups of the statistics and of the keys (per row: they stay in cache across a row's
+    samples), per-row words and the copy to the host are not counted."""
+    passes = 8 + (sample_bits + 7) // 8
+    return 12 + passes * 20 + 2 * 12 + 28 + 12 + 8 + 24
+
+
+PHENO_ARRAYS = ("row", "n_na", "rank2")
+
+
+def same_pheno(a, b):
+    return (a.n_rows, a.n_clustered, a.n_drop_na, a.n_drop_sd) == (b.n_rows, b.n_clustered, b.n_drop_na, b.n_drop_sd) and all(
+        np.array_equal(getattr(a, k), getattr(b, k)) for k in PHENO_ARRAYS) and all(
+        np.array_equal(getattr(a, k).view(np.uint64), getattr(b, k).view(np.uint64)) for k in ("mean", "sd"))
+
+
+def part_pheno(a):
+    import regtools_amd
+    from regtools_amd import _ffi, cohort
+    f = a.refine_params.split(",")
+    num, den = [int(x) for x in f[2].split("/")]
+    kw = dict(max_intron=int(f[0]), min_reads=int(f[1]), min_ratio=(num, den), min_rows=int(f[3]), min_total=int(f[4]))
+    share, min_sd = a.pheno_params.split(",")
+    pkw = dict(max_missing=tuple(int(x) for x in share.split("/")), min_sd=float(min_sd))
+    ctx = regtools_amd.Context(0)
+    for size in a.sizes.split(","):
+        shape, _, mix = size.partition(":")
+        mix = mix or "sparse"
+        n_samples, rows = [int(x) for x in shape.lower().split("x")]
+        rng = np.random.default_rng(3)
+        tables = [make_sample(g, rows, rng, mix) for g in range(n_samples)]
+        co = regtools_amd.Cohort(ctx=ctx)
+        for g, t in enumerate(tables):
+            co.add(Sample(t), "s%04d" % g)
+        for _ in range(2):                           # (the second finish is a warm one)
+            m = co.finish()
+        other = regtools_amd.Cohort(ctx=ctx)
+        refine, in_hbm, uploaded, same_paths, ph = [], [], [], True, None
+        for _ in range(a.reps):                      # refine and phenotypes alternate on the same matrix, in the same process
+            rf = co.refine(m, **kw)
+            refine.append(round(rf.ms_cluster, 3))
+            ph = co.phenotypes(m, rf, **pkw)
+            in_hbm.append(round(ph.ms_pheno, 3))
+            up = other.phenotypes(m, rf, **pkw)
+            uploaded.append(round(up.ms_pheno, 3))
+            same_paths &= same_pheno(ph, up)
+        assert co.cluster_paths == [1, 1] * a.reps and other.cluster_paths == [0] * a.reps
+        entries = ph.n_rows * n_samples
+        bpe = pheno_bytes_per_entry(max(1, (n_samples - 1).bit_length()))
+        best = min(in_hbm[1:] or in_hbm)
+        line = {"part": "pheno", "mix": mix, "samples": n_samples, "rows_per_sample": rows, "rows": m.n, "count_entries": int(m.row_begin[-1]),
+                "refine_params": kw, "pheno_params": {"max_missing": list(pkw["max_missing"]), "min_sd": pkw["min_sd"]},
+                "n_clustered": ph.n_clustered, "n_drop_na": ph.n_drop_na, "n_drop_sd": ph.n_drop_sd, "rows_kept": ph.n_rows, "table_entries": entries,
+                "ms_pheno_in_hbm": in_hbm, "ms_pheno_uploaded": uploaded, "ms_refine_same_run": refine, "ms_pheno_best_warm": best,
+                "ms_refine_best_warm": min(refine[1:] or refine), "paths_equal_every_time": bool(same_paths),
+                "bytes_per_entry_counted": bpe, "TBps_over_ms_pheno": round(bpe * entries / best / 1e9, 3),
+                "share_of_8TBps": round(bpe * entries / best / 1e9 / 8.0, 4)}
+        assert same_paths, "the two paths differ"
+        if not a.no_host:
+            h = cohort.phenotypes_host(m, rf, **pkw)
+            line["ms_pheno_host"] = round(h.ms_pheno, 1)
+            line["device_over_host"] = round(h.ms_pheno / best, 1)
+            line["identical_to_host"] = bool(same_pheno(ph, h))
+            assert line["identical_to_host"], "the device's phenotype table differs from the host twin's"
+            h.close()
+        ph.close(); up.close(); rf.close(); m.close(); co.close(); other.close()
+        for t in tables:
+            _ffi.lib().rgx_table_free(t)
+        print(json.dumps(line), flush=True)
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -311,6 +391,8 @@ def main():
     ap.add_argument("--part", default="all", choices=["all", "pipeline", "finish"])
     ap.add_argument("--cluster", action="store_true", help="the cluster part, alone")
     ap.add_argument("--refine", action="store_true", help="the refine part, alone")
+    ap.add_argument("--pheno", action="store_true", help="the phenotype part, alone")
+    ap.add_argument("--pheno-params", default="4/10,0.005", help="num/den of the missing share, min_sd")
     ap.add_argument("--refine-params", default="100000,5,1/1000,2,30", help="max_intron,min_reads,num/den,min_rows,min_total")
     ap.add_argument("--reads", type=int, default=50_000_000)
     ap.add_argument("--files", type=int, default=24)
@@ -322,6 +404,8 @@ def main():
         return part_cluster(a)
     if a.refine:
         return part_refine(a)
+    if a.pheno:
+        return part_pheno(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
