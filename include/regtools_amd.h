@@ -375,7 +375,7 @@ int  rgx_cohort_refine_host(const rgx_cohort_matrix *m, const rgx_refine_params 
  * The splicing phenotype table of a clustered cohort: per clustered junction and sample the intron-excision ratio, filtered, standardised
  * across samples and rank-normalised across junctions -- the table an sQTL mapper takes.  MODELLED ON LeafCutter's
  * prepare_phenotype_table.py, which is not available to this project: nothing here was compared against it, its means behind the
- * imputation are computed in another order, and its per-chromosome files and principal components are not written.
+ * imputation are computed in another order, and its per-chromosome files are not written (its principal components: the next block).
  *   input                 a matrix m and a cluster result cl OF THAT MATRIX (rgx_cohort_cluster, rgx_cohort_refine or their twins);
  *                         cl->n_rows != m->n, or a cluster number at or above cl->n_clusters, is RGX_ERR_ARG.  S = m->n_samples
  *   parameters            na_num / na_den: the share of missing samples a row may have (na_den == 0 or na_num > na_den is RGX_ERR_ARG);
@@ -436,6 +436,53 @@ double rgx_pheno_quantile(uint32_t rank2, uint64_t n_rows);
  * (m, cl); 0 when the three do not fit together.  Buffer protocol of rgx_cohort_format_counts. */
 size_t rgx_cohort_format_phenotypes(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, char *buf,
                                     size_t cap);
+
+/* -----------------------------------------------------------------------------------------------------
+ * The principal components of the phenotype table: the covariates of an sQTL run, the .PCs file of LeafCutter's
+ * prepare_phenotype_table.py (which calls sklearn's PCA on the quantile-normalised table; the tests compare with that library).
+ *   input                 a phenotype table ph, of which only n_rows = K, n_samples = S and rank2 are read, and n_pcs
+ *   errors                RGX_ERR_ARG, before any launch: K < 2 (or K > 2^31 - 1), S == 0, S > 2048, n_pcs == 0, n_pcs > min(K, S).
+ *                         RGX_ERR_ARG also for a rank2 outside [2, 2 K]: the device notices it in its gather and reports it through a flag,
+ *                         the twin when it meets it
+ *   quantile table        T[r] = rgx_pheno_quantile(r, K) for r = 2 .. 2 K, computed on the HOST (2 K - 1 doubles, uploaded; log never runs
+ *                         on the device); q[k][s] = T[rank2[k][s]]
+ *   summation order       n_chunks = min(64, ceil(K / 1024)), L = ceil(K / n_chunks); chunk j is rows [j L, min(K, (j + 1) L)).  For
+ *                         s <= t the chunk partial starts at +0.0 and takes acc = fma(q[k][s], q[k][t], acc) in ascending k;
+ *                         gram[s][t] is the chunk partials added in ascending j from +0.0 by plain rounded adds, gram[t][s] = gram[s][t].
+ *                         col_sum[s] likewise with acc = acc + q[k][s].  No floating-point atomics anywhere.  Part of the contract:
+ *                         gram and col_sum are the same bits wherever they are computed
+ *   covariance            on the host, by one function for the device path and the twin, contraction off:
+ *                         cov[s][t] = (gram[s][t] - col_sum[s] * col_sum[t] / (double)K) / (double)(K - 1) for s <= t, mirrored
+ *   eigen-decomposition   on the host, by that same function: cyclic Jacobi written here (no LAPACK).  variance = all S eigenvalues in
+ *                         descending order; component = the first n_pcs unit eigenvectors, n_pcs x S row-major, each signed so that its
+ *                         entry of largest absolute value (the first on ties) is positive -- sklearn 1.7's svd_flip(u_based_decision=False)
+ *   limits                S <= 2048: the chunk partials are at most 64 S^2 doubles (2 GiB there) and the eigen-decomposition is O(S^3)
+ *                         on one host thread.  RGX_ERR_DEVICE when workspace cannot be had
+ * ----------------------------------------------------------------------------------------------------- */
+/* Owned by the library (rgx_cohort_pheno_pcs_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_pcs;
+    double    *col_sum;         /* S */
+    double    *gram;            /* S * S, both triangles */
+    double    *variance;        /* S: the eigenvalues of the covariance, descending */
+    double    *component;       /* n_pcs * S, row-major */
+    /* statistics, wall */
+    double     ms_pcs;          /* this call */
+    double     ms_gram;         /* behind the quantile table: the uploads, the kernels and the copy back (the twin: its Gram loops) */
+    double     ms_eigen;        /* the host part: covariance, Jacobi, order and signs */
+} rgx_pheno_pcs;
+/* On the cohort's device and stream: rank2 and T are uploaded, k_pca_gram writes one partial per (pair of 64-sample tiles, chunk),
+ * k_pca_reduce adds the chunks in order; one copy back and one host wait in front of the host part. */
+int  rgx_cohort_pheno_pcs(rgx_cohort *co, const rgx_pheno_table *ph, uint32_t n_pcs, rgx_pheno_pcs **out, char *err, size_t errlen);
+/* Host twin: the same order in plain C++ (std::fma), no device.  NOT a fallback. */
+int  rgx_cohort_pheno_pcs_host(const rgx_pheno_table *ph, uint32_t n_pcs, rgx_pheno_pcs **out, char *err, size_t errlen);
+void rgx_cohort_pheno_pcs_free(rgx_pheno_pcs *pcs);
+/* "id" and one "\t<sample name>" per sample of m, then one line per component: its 1-based number and per sample a tab and the entry as
+ * %.17g -- LeafCutter's .PCs layout.  pcs == NULL writes the header line alone; 0 when pcs is not of m's samples.  Buffer protocol of
+ * rgx_cohort_format_counts. */
+size_t rgx_cohort_format_pheno_pcs(const rgx_cohort_matrix *m, const rgx_pheno_pcs *pcs, char *buf, size_t cap);
 
 /* Library/build identification: "regtools_amd <version> gfx950". */
 const char *rgx_version(void);

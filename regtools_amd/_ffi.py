@@ -57,7 +57,8 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_cohort_format_cluster_counts", "rgx_k_components",
            "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host",
            "rgx_pheno_params_default", "rgx_cohort_phenotypes", "rgx_cohort_phenotypes_host", "rgx_cohort_phenotypes_free", "rgx_pheno_quantile",
-           "rgx_cohort_format_phenotypes"]
+           "rgx_cohort_format_phenotypes",
+           "rgx_cohort_pheno_pcs", "rgx_cohort_pheno_pcs_host", "rgx_cohort_pheno_pcs_free", "rgx_cohort_format_pheno_pcs"]
 
 
 class CohortParams(C.Structure):
@@ -99,6 +100,12 @@ class PhenoTable(C.Structure):
     _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("row", C.POINTER(C.c_uint32)), ("n_na", C.POINTER(C.c_uint32)),
                 ("mean", C.POINTER(C.c_double)), ("sd", C.POINTER(C.c_double)), ("rank2", C.POINTER(C.c_uint32)),
                 ("n_clustered", C.c_uint64), ("n_drop_na", C.c_uint64), ("n_drop_sd", C.c_uint64), ("ms_pheno", C.c_double)]
+
+
+class PhenoPCs(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_pcs", C.c_uint32), ("col_sum", C.POINTER(C.c_double)),
+                ("gram", C.POINTER(C.c_double)), ("variance", C.POINTER(C.c_double)), ("component", C.POINTER(C.c_double)),
+                ("ms_pcs", C.c_double), ("ms_gram", C.c_double), ("ms_eigen", C.c_double)]
 
 
 class IdentifyParams(C.Structure):
@@ -256,6 +263,11 @@ def lib():
         L.rgx_pheno_quantile.restype = C.c_double
         L.rgx_cohort_format_phenotypes.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_phenotypes.restype = C.c_size_t
+        L.rgx_cohort_pheno_pcs.argtypes = [C.c_void_p, P(PhenoTable), C.c_uint32, P(P(PhenoPCs)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_pheno_pcs_host.argtypes = [P(PhenoTable), C.c_uint32, P(P(PhenoPCs)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_pheno_pcs_free.argtypes = [P(PhenoPCs)]
+        L.rgx_cohort_format_pheno_pcs.argtypes = [P(CohortMatrix), P(PhenoPCs), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_pheno_pcs.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -225,6 +225,76 @@ def phenotypes_host(matrix, clusters, max_missing=(4, 10), min_sd=0.005):
     return CohortPhenotypes(out)
 
 
+class CohortPCs(object):
+    """rgx_pheno_pcs: the principal components of a phenotype table -- col_sum (S) and gram (S x S) of its quantiles, variance (all S eigenvalues
+    of their covariance, descending) and component (n_pcs x S, unit length, the largest entry positive).  The array attributes are numpy VIEWS of
+    memory this object owns: copy what must outlive it."""
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_pcs = int(p.n_rows), int(p.n_samples), int(p.n_pcs)
+        self.ms_pcs, self.ms_gram, self.ms_eigen = p.ms_pcs, p.ms_gram, p.ms_eigen
+        S = self.n_samples
+        self.col_sum = np.ctypeslib.as_array(p.col_sum, shape=(S,))
+        self.gram = np.ctypeslib.as_array(p.gram, shape=(S, S))
+        self.variance = np.ctypeslib.as_array(p.variance, shape=(S,))
+        self.component = np.ctypeslib.as_array(p.component, shape=(self.n_pcs, S))
+
+    def text(self, matrix):
+        """The components as text, LeafCutter's .PCs layout: "id" and the samples of `matrix`, one line per component."""
+        fn = self._lib.rgx_cohort_format_pheno_pcs
+        n = fn(matrix._h, self._h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, self._h, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_pheno_pcs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlantedPhenotypes(object):
+    """A K x S uint32 array as the rgx_pheno_table the principal component calls read (n_rows, n_samples and rank2 alone are set).  The memory is
+    the array's own (a C-contiguous copy when it is not one already), kept alive by this object."""
+
+    def __init__(self, rank2):
+        import numpy as np
+        a = np.ascontiguousarray(rank2, dtype=np.uint32)
+        if a.ndim != 2:
+            raise ValueError("rank2 must be a K x S array")
+        self.rank2 = a
+        self.n_rows, self.n_samples = int(a.shape[0]), int(a.shape[1])
+        self._table = _ffi.PhenoTable()
+        self._table.n_rows, self._table.n_samples = self.n_rows, self.n_samples
+        self._table.rank2 = a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._h = C.pointer(self._table)
+
+
+def pheno_table_from_rank2(rank2):
+    """Wraps a K x S array of rank2 values as a table for Cohort.pheno_pcs and pheno_pcs_host."""
+    return PlantedPhenotypes(rank2)
+
+
+def pheno_pcs_host(ph, n_pcs):
+    """rgx_cohort_pheno_pcs_host: the first n_pcs principal components of a phenotype table by the library's plain C++ twin, no device involved."""
+    out = C.POINTER(_ffi.PhenoPCs)()
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_pheno_pcs_host(ph._h, n_pcs, C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortPCs(out)
+
+
 def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1):
     """rgx_cohort_merge_host over the tables the extractors hold (each with its own min_anchor_length_): no device involved."""
     lib = _ffi.lib()
@@ -324,6 +394,16 @@ class Cohort(object):
             raise RegtoolsError(rc, err.value.decode())
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
         return CohortPhenotypes(out)
+
+    def pheno_pcs(self, ph, n_pcs):
+        """The first n_pcs principal components of the phenotype table `ph` on this cohort's device (rgx_cohort_pheno_pcs): the Gram matrix of
+        its quantiles in HBM, the eigen-decomposition of their covariance on the host."""
+        out = C.POINTER(_ffi.PhenoPCs)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.rgx_cohort_pheno_pcs(self._h, ph._h, n_pcs, C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        return CohortPCs(out)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

@@ -266,6 +266,9 @@ void cohort_usage(std::ostream &out) {
         << "\t\t\t The clusters are those -k writes with the same -K, -T, -l, -J and -p, whether or not -k is given.\n"
         << "\t\t-x DEC\tJunctions whose cluster has no reads in more than this share of the samples are left out of -q; a decimal as -p. [0.4]\n"
         << "\t\t-d DEC\tJunctions whose ratio varies by less than this standard deviation are left out of -q. [0.005]\n"
+        << "\t\t-P FILE\tThe principal components of the -q table, the covariates of an sQTL run, laid out as LeafCutter's .PCs file: one line\n"
+        << "\t\t\t per component, one column per sample. The table is computed as for -q, whether or not -q is given.\n"
+        << "\t\t-C INT\tThe number of components -P writes, at most the table's rows and the samples. [10]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -331,7 +334,8 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA", clusters = "NA", phenotypes = "NA";
+        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA";
+        uint32_t n_components = 10;
         rgx_pheno_params qp;
         rgx_pheno_params_default(&qp);
         rgx_cohort_params cp;
@@ -344,7 +348,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -366,6 +370,16 @@ int junctions_cohort(int argc, char **argv) {
                     if (!cohort_parse_ratio(optarg, &rp.ratio_num, &rp.ratio_den)) throw std::runtime_error("Unrecognized ratio argument!\n\n");
                     refine = true; break;
                 case 'q': phenotypes = optarg; break;
+                case 'P': components = optarg; break;
+                case 'C': {
+                    char *end = nullptr;
+                    errno = 0;
+                    const long long v = strtoll(optarg, &end, 10);
+                    if (end == optarg || *end || errno || v < 1 || v > 0xffffffffll || optarg[0] == ' ' || optarg[0] == '+')
+                        throw std::runtime_error("Unrecognized component count argument!\n\n");
+                    n_components = (uint32_t)v;
+                    break;
+                }
                 case 'x':
                     if (!cohort_parse_ratio(optarg, &qp.na_num, &qp.na_den)) throw std::runtime_error("Unrecognized ratio argument!\n\n");
                     break;
@@ -449,11 +463,17 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        if (ok && (clusters != "NA" || phenotypes != "NA") && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
+        const bool want_pheno = phenotypes != "NA" || components != "NA";
+        if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
         rgx_pheno_table *ph = nullptr;
-        if (ok && phenotypes != "NA" && rgx_cohort_phenotypes(co, m, cl, &qp, &ph, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        if (ok && want_pheno && rgx_cohort_phenotypes(co, m, cl, &qp, &ph, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        // -C clipped to the table; a table of fewer than two rows (or of no samples) has no components: the file is its header line
+        rgx_pheno_pcs *pcs = nullptr;
+        const uint32_t n_pcs = ph && components != "NA" && ph->n_rows >= 2 ? (uint32_t)std::min<uint64_t>({n_components, ph->n_rows, ph->n_samples}) : 0;
+        if (ok && n_pcs && rgx_cohort_pheno_pcs(co, ph, n_pcs, &pcs, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         if (!ok) {
+            if (ph) rgx_cohort_phenotypes_free(ph);
             if (cl) rgx_cohort_clusters_free(cl);
             if (m) rgx_cohort_matrix_free(m);
             rgx_pipeline_destroy(pl);                       // (runs what is still queued to its end: the buffers below were promised to it)
@@ -471,7 +491,9 @@ int junctions_cohort(int argc, char **argv) {
         size_t nk = 0; std::unique_ptr<char[]> ktx;
         if (cl && clusters != "NA") { nk = rgx_cohort_format_cluster_counts(m, cl, nullptr, 0); ktx.reset(new char[nk + 1]); rgx_cohort_format_cluster_counts(m, cl, ktx.get(), nk); }
         size_t nq = 0; std::unique_ptr<char[]> qtx;
-        if (ph) { nq = rgx_cohort_format_phenotypes(m, cl, ph, nullptr, 0); qtx.reset(new char[nq + 1]); rgx_cohort_format_phenotypes(m, cl, ph, qtx.get(), nq); }
+        if (ph && phenotypes != "NA") { nq = rgx_cohort_format_phenotypes(m, cl, ph, nullptr, 0); qtx.reset(new char[nq + 1]); rgx_cohort_format_phenotypes(m, cl, ph, qtx.get(), nq); }
+        size_t np = 0; std::unique_ptr<char[]> ptx;
+        if (components != "NA") { np = rgx_cohort_format_pheno_pcs(m, pcs, nullptr, 0); ptx.reset(new char[np + 1]); rgx_cohort_format_pheno_pcs(m, pcs, ptx.get(), np); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -486,10 +508,15 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + clusters + "\n\n");
             short_write |= fwrite(ktx.get(), 1, nk, g) != nk; short_write |= fclose(g) != 0;
         }
-        if (ph) {
+        if (ph && phenotypes != "NA") {
             FILE *g = fopen(phenotypes.c_str(), "w");
             if (!g) throw std::runtime_error("Unable to write " + phenotypes + "\n\n");
             short_write |= fwrite(qtx.get(), 1, nq, g) != nq; short_write |= fclose(g) != 0;
+        }
+        if (components != "NA") {
+            FILE *g = fopen(components.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + components + "\n\n");
+            short_write |= fwrite(ptx.get(), 1, np, g) != np; short_write |= fclose(g) != 0;
         }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
@@ -503,6 +530,10 @@ int junctions_cohort(int argc, char **argv) {
             fprintf(stderr, "[regtools_amd] phenotypes: %llu rows kept of %llu clustered, %llu dropped as missing, %llu as flat, %.3f ms\n",
                     (unsigned long long)ph->n_rows, (unsigned long long)ph->n_clustered, (unsigned long long)ph->n_drop_na,
                     (unsigned long long)ph->n_drop_sd, ph->ms_pheno);
+        if (components != "NA" && ph && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] pcs: %llu rows, %u samples, %u components written, %.3f ms (gram %.3f ms, eigen %.3f ms)\n",
+                    (unsigned long long)ph->n_rows, ph->n_samples, n_pcs, pcs ? pcs->ms_pcs : 0.0, pcs ? pcs->ms_gram : 0.0, pcs ? pcs->ms_eigen : 0.0);
+        rgx_cohort_pheno_pcs_free(pcs);
         rgx_cohort_phenotypes_free(ph);
         rgx_cohort_clusters_free(cl);
         rgx_cohort_matrix_free(m);

@@ -84,6 +84,8 @@ struct rgx_cohort {
     DevBuf cl_in, cl_rows, cl_entries;
     // rgx_cohort_phenotypes (cohort_pheno.cpp): the uploaded cluster result, the row and the entry workspace
     DevBuf ph_in, ph_rows, ph_entries;
+    // rgx_cohort_pheno_pcs (cohort_pcs.cpp): rank2 and the quantile table, the chunk partials, the Gram matrix with the column sums
+    DevBuf pc_in, pc_part, pc_out;
 };
 
 // cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the

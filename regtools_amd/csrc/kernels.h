@@ -389,4 +389,11 @@ void launch_pheno_tie_heads(const uint32_t *perm, const uint32_t *z_lo, const ui
 void launch_pheno_rank(const uint32_t *perm, const uint32_t *head, const uint32_t *seg_excl, const uint32_t *run_start, uint32_t n, uint32_t n_kept,
                        uint32_t *rank2, hipStream_t st);
 
+// ---- the phenotype table's principal components (pca_kernels.hip; host side in cohort_pcs.cpp; arithmetic in pca_core.h) ---------------------------
+// With n_tiles = ceil(S / 64) and n_chunks = pca_n_chunks(K): part takes n_tiles (n_tiles + 1) / 2 * n_chunks tiles of 64 x 64 doubles, col_part
+// n_chunks * n_tiles * 64 doubles; T has the 2 K - 1 quantiles of rank2 = 2 .. 2 K; *bad (zeroed by the caller) becomes 1 when a rank2 is outside that
+void launch_pca_gram(const uint32_t *rank2, const double *T, uint64_t K, uint32_t S, double *part, double *col_part, uint32_t *bad, hipStream_t st);
+// gram (S x S, both triangles) and col_sum (S): the chunk partials in ascending chunk order
+void launch_pca_reduce(const double *part, const double *col_part, uint64_t K, uint32_t S, double *gram, double *col_sum, hipStream_t st);
+
 }  // namespace rgx

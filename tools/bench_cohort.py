@@ -23,6 +23,12 @@
                     the two drop counts, and whether the paths and the twin were identical (integers, and mean / sd as bit patterns);
                     --pheno-params "num/den,min_sd" (default 4/10,0.005); bytes moved per table entry (pheno_bytes_per_entry) over ms_pheno
 
+  --pcs             rgx_cohort_pheno_pcs (ms_pcs, ms_gram, ms_eigen) on the phenotype tables of the same cohorts (behind
+                    rgx_cohort_refine and rgx_cohort_phenotypes, whose ms_pheno of the same run is printed beside it), then on planted tables
+                    --planted "SAMPLESxROWS,..." (a low-rank signal plus noise, ranked per column): first and warm calls, --n-pcs components
+                    (default 10, clipped to the table), rgx_cohort_pheno_pcs_host's times, whether every array was identical to the twin's as bit
+                    patterns, and K S (S + 1) / 2 fused multiply-adds over ms_gram as GFMA/s
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -336,6 +342,99 @@ def part_pheno(a):
         print(json.dumps(line), flush=True)
 
 
+def planted_rank2(n_samples, rows, n_f=5, seed=7):
+    """rows x n_samples uint32: twice the rank per column of X = F L + 0.5 N (tests/pca_cases.py's construction in float32, no ties), made 64 columns
+    at a time."""
+    rng = np.random.default_rng(seed)
+    F = rng.standard_normal((rows, n_f), dtype=np.float32)
+    out = np.empty((rows, n_samples), np.uint32)
+    for s0 in range(0, n_samples, 64):
+        w = min(64, n_samples - s0)
+        L = rng.standard_normal((n_f, w), dtype=np.float32) * (3 * 0.7 ** np.arange(n_f, dtype=np.float32))[:, None]
+        X = F @ L + 0.5 * rng.standard_normal((rows, w), dtype=np.float32)
+        order = np.argsort(X, axis=0, kind="stable")
+        rank = np.empty_like(order)
+        np.put_along_axis(rank, order, np.arange(1, rows + 1, dtype=order.dtype)[:, None], axis=0)
+        out[:, s0:s0 + w] = 2 * rank
+    return out
+
+
+PCS_ARRAYS = ("col_sum", "gram", "variance", "component")
+
+
+def same_pcs(a, b):
+    return (a.n_rows, a.n_samples, a.n_pcs) == (b.n_rows, b.n_samples, b.n_pcs) and all(
+        np.array_equal(np.ascontiguousarray(getattr(a, k)).view(np.uint64), np.ascontiguousarray(getattr(b, k)).view(np.uint64)) for k in PCS_ARRAYS)
+
+
+def pcs_line(a, co, ph, line):
+    """The --pcs measurements of one table, added to `line` and printed."""
+    from regtools_amd import cohort
+    K, S = ph.n_rows, ph.n_samples
+    line.update({"rows_kept": K, "samples": S})
+    if K < 2 or S < 1 or S > 2048:
+        line["skipped"] = "a table of %d rows and %d samples has no components" % (K, S)
+        print(json.dumps(line), flush=True)
+        return
+    n_pcs = min(a.n_pcs, K, S)
+    runs = [co.pheno_pcs(ph, n_pcs) for _ in range(a.reps)]
+    warm = runs[1:] or runs
+    best = min(warm, key=lambda p: p.ms_gram)
+    fmas = K * S * (S + 1) // 2
+    line.update({"n_pcs": n_pcs, "n_chunks": min(64, -(-K // 1024)), "tile_pairs": (-(-S // 64)) * (-(-S // 64) + 1) // 2,
+                 "ms_pcs": [round(p.ms_pcs, 3) for p in runs], "ms_gram": [round(p.ms_gram, 3) for p in runs],
+                 "ms_eigen": [round(p.ms_eigen, 3) for p in runs], "ms_gram_best_warm": round(best.ms_gram, 3),
+                 "ms_eigen_best_warm": round(min(p.ms_eigen for p in warm), 3), "fmas": fmas, "GFMA_per_s_over_ms_gram": round(fmas / best.ms_gram / 1e6, 1),
+                 "identical_every_time": bool(all(same_pcs(runs[0], p) for p in runs[1:]))})
+    assert line["identical_every_time"], "two device runs differ"
+    if not a.no_host:
+        h = cohort.pheno_pcs_host(ph, n_pcs)
+        line.update({"ms_pcs_host": round(h.ms_pcs, 1), "ms_gram_host": round(h.ms_gram, 1), "ms_eigen_host": round(h.ms_eigen, 1),
+                     "gram_device_over_host": round(h.ms_gram / best.ms_gram, 1), "identical_to_host": bool(same_pcs(runs[0], h))})
+        assert line["identical_to_host"], "the device's principal components differ from the host twin's"
+        h.close()
+    for p in runs:
+        p.close()
+    print(json.dumps(line), flush=True)
+
+
+def part_pcs(a):
+    import regtools_amd
+    from regtools_amd import _ffi, cohort
+    f = a.refine_params.split(",")
+    num, den = [int(x) for x in f[2].split("/")]
+    kw = dict(max_intron=int(f[0]), min_reads=int(f[1]), min_ratio=(num, den), min_rows=int(f[3]), min_total=int(f[4]))
+    share, min_sd = a.pheno_params.split(",")
+    pkw = dict(max_missing=tuple(int(x) for x in share.split("/")), min_sd=float(min_sd))
+    ctx = regtools_amd.Context(0)
+    for size in [x for x in a.sizes.split(",") if x]:
+        shape, _, mix = size.partition(":")
+        mix = mix or "sparse"
+        n_samples, rows = [int(x) for x in shape.lower().split("x")]
+        rng = np.random.default_rng(3)
+        tables = [make_sample(g, rows, rng, mix) for g in range(n_samples)]
+        co = regtools_amd.Cohort(ctx=ctx)
+        for g, t in enumerate(tables):
+            co.add(Sample(t), "s%04d" % g)
+        m = co.finish()
+        pheno = []
+        for _ in range(a.reps):
+            rf = co.refine(m, **kw)
+            ph = co.phenotypes(m, rf, **pkw)
+            pheno.append(round(ph.ms_pheno, 3))
+        pcs_line(a, co, ph, {"part": "pcs", "table": "cohort", "mix": mix, "rows_per_sample": rows, "rows": m.n, "ms_pheno_same_run": pheno})
+        ph.close(); rf.close(); m.close(); co.close()
+        for t in tables:
+            _ffi.lib().rgx_table_free(t)
+    co = regtools_amd.Cohort(ctx=ctx)
+    for size in [x for x in a.planted.split(",") if x]:
+        n_samples, rows = [int(x) for x in size.lower().split("x")]
+        t0 = time.time()
+        ph = cohort.pheno_table_from_rank2(planted_rank2(n_samples, rows))
+        pcs_line(a, co, ph, {"part": "pcs", "table": "planted", "s_generate": round(time.time() - t0, 1)})
+    co.close()
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -392,6 +491,9 @@ def main():
     ap.add_argument("--cluster", action="store_true", help="the cluster part, alone")
     ap.add_argument("--refine", action="store_true", help="the refine part, alone")
     ap.add_argument("--pheno", action="store_true", help="the phenotype part, alone")
+    ap.add_argument("--pcs", action="store_true", help="the principal component part, alone")
+    ap.add_argument("--planted", default="", help="--pcs: planted tables, SAMPLESxROWS, comma separated")
+    ap.add_argument("--n-pcs", type=int, default=10, help="--pcs: components asked for (clipped to the table)")
     ap.add_argument("--pheno-params", default="4/10,0.005", help="num/den of the missing share, min_sd")
     ap.add_argument("--refine-params", default="100000,5,1/1000,2,30", help="max_intron,min_reads,num/den,min_rows,min_total")
     ap.add_argument("--reads", type=int, default=50_000_000)
@@ -406,6 +508,8 @@ def main():
         return part_refine(a)
     if a.pheno:
         return part_pheno(a)
+    if a.pcs:
+        return part_pcs(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
