@@ -201,6 +201,8 @@ int EventsRun::stage_upload() {
             uint32_t *gate_flags = gated ? c->buf(Buf::gate_flags).as<uint32_t>() : nullptr;
             const uint32_t gate_epoch = c->gate_epoch;
             hipStream_t gate_q = c->side[0] ? c->side[0] : copy_q;
+            if (trace && (up_lo || up_hi < bam_len)) fprintf(stderr, "[rgx trace] shard %d of %d: bytes [%zu, %zu) of %zu go up behind the header's [0, %zu)\n",
+                p->shard, p->n_shards, up_lo, up_hi, bam_len, hdr_hi);
             up.th = std::thread([this, dst, hdr_hi, up_lo, gate_q, gate_flags, gate_epoch] {
                 if (hipSetDevice(c->device) != hipSuccess) { up.err = 1; up.recorded = (uint32_t)up.end.size(); return; }
                 if (hdr_hi && hipMemcpyAsync(dst, h_bam, hdr_hi, hipMemcpyHostToDevice, copy_q) != hipSuccess) up.err = 1;
@@ -208,6 +210,7 @@ int EventsRun::stage_upload() {
                 for (size_t j = 0; j < up.end.size(); ++j) {
                     if ((up.end[j] > o && hipMemcpyAsync(dst + o, h_bam + o, up.end[j] - o, hipMemcpyHostToDevice, copy_q) != hipSuccess) ||
                         hipEventRecord(c->chunk_ev[j], copy_q) != hipSuccess) up.err = 1;
+                    if (trace && j == 0) fprintf(stderr, "[rgx trace] first chunk enqueued         %8.3f ms after the call's entry\n", now_ms() - t_begin);
                     // (the flag's one-lane kernel goes to a side stream behind the chunk's event: on the copy stream itself it sat between two
                     //  copies, ~30 us of an idle bus per chunk)
                     if (gate_flags) {
@@ -259,9 +262,10 @@ int EventsRun::stage_members() {
     std::vector<Member> &hm = c->hm_scratch;
     DevBuf &b_members = c->buf(Buf::members), &b_disc = c->buf(Buf::discover);
     if (overlap) {
-        // the member list came from the host scan: what the discovery kernels would have left in HBM
-        // (in page-locked host memory, read in place by the kernels -- 24 bytes per member, once: an upload would queue behind the file's
-        // chunks on the copy engine, measured 4 ms)
+        // the member list came from the host scan: what the discovery kernels would have left in HBM.  It goes there from page-locked host memory
+        // by a kernel on the pipeline's stream, one coalesced pass (a copy would queue behind the file's chunks on the copy engine, measured 4 ms).
+        // Read in place by the kernels instead -- the lane sort, then every lane of the gated launch its own 24 bytes at wave start, 169 k scattered
+        // reads whose completions share the link's direction with the upload -- it made the chunk under the launch take 1.04 ms instead of 0.59.
         n_cand = (uint32_t)hm.size();
         const size_t need = ((size_t)n_cand + 1) * sizeof(Member);
         if (need > c->pinned_members_cap) {
@@ -271,6 +275,8 @@ int EventsRun::stage_members() {
             c->pinned_members_cap = need + need / 4;
         }
         memcpy(c->pinned_members, hm.data(), (size_t)n_cand * sizeof(Member));
+        HIP_TRY(b_members.ensure(need + 16));
+        launch_members_fetch((const Member *)c->pinned_members, b_members.as<Member>(), n_cand, st);
         h_sc->n_members = n_cand; h_sc->total_inflated = hm_total;
         HIP_TRY(hipMemcpyAsync(&d_sc->n_members, &h_sc->n_members, 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(&d_sc->total_inflated, &h_sc->total_inflated, 8, hipMemcpyHostToDevice, st));
@@ -298,7 +304,8 @@ int EventsRun::stage_members() {
     CARVE_TRY(wc, "cand");
     launch_magic_fill(d_bam, bam_len, n_tiles, tile_cnt, cand, st);
     }
-    d_members = overlap ? (Member *)c->pinned_members : b_members.as<Member>();
+    d_members = b_members.as<Member>();
+    h_members = overlap ? (const Member *)c->pinned_members : nullptr;
     from_members = overlap ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
     if (!overlap) chain(UINT64_MAX);
     if (bai_thread.joinable()) bai_thread.join();

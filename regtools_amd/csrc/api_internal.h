@@ -348,7 +348,8 @@ struct rgx_ctx {
     DevBuf bufs[(size_t)Buf::count];
     void *pinned = nullptr; size_t pinned_cap = 0;     // small pinned staging for scalar readbacks
     std::vector<Member> hm_scratch;
-    void *pinned_members = nullptr; size_t pinned_members_cap = 0;      // the host scan's member list: kernels read it in place (grow-only)
+    // the host scan's member list, page-locked (grow-only): the host reads it here, the device fetches it into the "members" block once per call
+    void *pinned_members = nullptr; size_t pinned_members_cap = 0;
     void *pinned_rows = nullptr; size_t pinned_rows_cap = 0;
     // rows of the last rgx_extract* call, still in the "rows_out" block in HBM   // grow-only pinned staging for whole result tables (device merge)
     uint64_t last_rows = 0, last_records = 0, last_events = 0, last_bytes = 0; bool last_rows_valid = false;
@@ -462,6 +463,9 @@ struct EventsRun {
     uint64_t *cand = nullptr;
     uint32_t *nx[2] = {nullptr, nullptr}, *c_isize = nullptr, *c_reach = nullptr, *c_rank = nullptr, *c_isz2 = nullptr, *c_tmp = nullptr;
     Member *d_members = nullptr; hipMemcpyKind from_members = hipMemcpyDeviceToHost;
+    // the host scan's list has two copies: the page-locked one the host reads (h_members) and the one in HBM the kernels read (d_members)
+    const Member *h_members = nullptr;
+    const Member *members_src() const { return h_members ? h_members : d_members; }      // what a copy of kind from_members to the host reads
     // the members = the candidates that chain up from offset 0 (and, second try below, from the offset a seek lands on)
     void chain(uint64_t root2) {
         launch_member_link(d_bam, bam_len, cand, n_cand, nx[0], c_isize, c_reach, root2, st);
@@ -484,7 +488,7 @@ struct EventsRun {
     // one member of the list (the host scan's list is host memory; the device's is read on the pipeline's stream -- never through the null stream, which
     // would wait for whatever any other stream of the process has in flight)
     hipError_t member_at(uint32_t k, Member &m) {
-        if (from_members == hipMemcpyHostToHost) { memcpy(&m, d_members + k, sizeof m); return hipSuccess; }
+        if (h_members) { memcpy(&m, h_members + k, sizeof m); return hipSuccess; }
         hipError_t e = hipMemcpyAsync(&m, d_members + k, sizeof m, from_members, st);
         return e == hipSuccess ? hipStreamSynchronize(st) : e;
     }

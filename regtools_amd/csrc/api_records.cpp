@@ -61,7 +61,7 @@ int EventsRun::stage_footers_and_header() {
             const uint8_t *src; uint64_t have;
             uint32_t bad_h = 0xffffffffu;
             std::vector<Member> hmem(n_h);
-            HIP_TRY(hipMemcpyAsync(hmem.data(), d_members, (size_t)n_h * sizeof(Member), from_members, st));
+            HIP_TRY(hipMemcpyAsync(hmem.data(), members_src(), (size_t)n_h * sizeof(Member), from_members, st));
             HIP_TRY(hipStreamSynchronize(st));
             uint32_t used = 0;
             for (; used < n_h; ++used) if (hmem[used].isize == 0 || hmem[used].isize > kBgzfMaxBlock) break;   // the header read stops there
@@ -199,7 +199,7 @@ int EventsRun::stage_bounds_and_chains() {
         std::vector<Member> rm(n_range);
         std::vector<uint8_t> bad(n_range, 0);
         if (n_range) {
-            HIP_TRY(hipMemcpyAsync(rm.data(), d_members + m_lo, (size_t)n_range * sizeof(Member), from_members, st));
+            HIP_TRY(hipMemcpyAsync(rm.data(), members_src() + m_lo, (size_t)n_range * sizeof(Member), from_members, st));
             HIP_TRY(hipMemcpyAsync(bad.data(), d_bad, n_range, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }

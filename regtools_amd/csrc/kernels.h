@@ -49,6 +49,8 @@ void launch_inflate(const uint8_t *comp, const Member *members, uint32_t n_membe
                     InflateGate gate = InflateGate() /* k_inflate_coop only: waves wait for their upload chunk */);
 // whether launch_inflate would pick k_inflate_coop for a range of this size (the gate needs it)
 bool inflate_takes_coop(uint32_t n_members);
+// the host scan's member list (page-locked host memory, n_members + 1 members long) into a device block of the same length
+void launch_members_fetch(const Member *host_members, Member *dst, uint32_t n_members, hipStream_t stream);
 void launch_gate_set(uint32_t *flag, uint32_t epoch, hipStream_t stream);      // flags[k] = epoch, in stream order behind chunk k's copy
 // Which options suit a payload, from how well the file compresses (round 4, 50 M-read files / 10 M long reads on one box, ms, all byte-equal to zlib;
 // tools/lab/forms_r4.sh, profiles/r04_inflate_forms.txt):

@@ -537,6 +537,17 @@ static void inflate_attrs() {
 // write does not reach; measured: 604 ms per step); a store from a wave is coherent with them.
 __global__ void k_gate_set(uint32_t *flag, uint32_t epoch) { __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 void launch_gate_set(uint32_t *flag, uint32_t epoch, hipStream_t stream) { hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(1), 0, stream, flag, epoch); }
+// The host scan's member list, from page-locked host memory into HBM: 16 bytes a lane, every byte over the link once.  (Both blocks are a member
+// longer than the list: the last lane's 16 bytes may end 8 behind it.)
+__global__ __launch_bounds__(256) void k_members_fetch(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
+}
+void launch_members_fetch(const Member *host_members, Member *dst, uint32_t n_members, hipStream_t stream) {
+    static_assert(sizeof(Member) == 24, "two members are three 16-byte words");
+    const uint32_t n16 = (uint32_t)(((uint64_t)n_members * sizeof(Member) + 15) / 16);
+    if (!n16) return;
+    hipLaunchKernelGGL(k_members_fetch, dim3(std::min<uint32_t>((n16 + 255) / 256, 256)), dim3(256), 0, stream, (const uint4 *)host_members, (uint4 *)dst, n16);
+}
 bool inflate_takes_coop(uint32_t n_members) {
     const int f = inflate_form_env();
     return f ? f == 4 : n_members > kWaveFormMaxMembers && kDefaultLaneForm == 4;
