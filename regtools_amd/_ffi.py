@@ -58,7 +58,9 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host",
            "rgx_pheno_params_default", "rgx_cohort_phenotypes", "rgx_cohort_phenotypes_host", "rgx_cohort_phenotypes_free", "rgx_pheno_quantile",
            "rgx_cohort_format_phenotypes",
-           "rgx_cohort_pheno_pcs", "rgx_cohort_pheno_pcs_host", "rgx_cohort_pheno_pcs_free", "rgx_cohort_format_pheno_pcs"]
+           "rgx_cohort_pheno_pcs", "rgx_cohort_pheno_pcs_host", "rgx_cohort_pheno_pcs_free", "rgx_cohort_format_pheno_pcs",
+           "rgx_cohort_pheno_regions", "rgx_cohort_qtl_nominal", "rgx_cohort_qtl_nominal_host", "rgx_cohort_qtl_free", "rgx_qtl_tstat",
+           "rgx_qtl_pvalue", "rgx_cohort_format_qtl", "rgx_genotypes_load", "rgx_genotypes_free"]
 
 
 class CohortParams(C.Structure):
@@ -106,6 +108,25 @@ class PhenoPCs(C.Structure):
     _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_pcs", C.c_uint32), ("col_sum", C.POINTER(C.c_double)),
                 ("gram", C.POINTER(C.c_double)), ("variance", C.POINTER(C.c_double)), ("component", C.POINTER(C.c_double)),
                 ("ms_pcs", C.c_double), ("ms_gram", C.c_double), ("ms_eigen", C.c_double)]
+
+
+class Genotypes(C.Structure):
+    _fields_ = [("n_variants", C.c_uint32), ("n_samples", C.c_uint32), ("tid", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
+                ("dosage", C.POINTER(C.c_int8)), ("id", C.POINTER(C.c_char_p)),
+                ("n_records", C.c_uint64), ("n_multiallelic", C.c_uint64), ("n_no_gt", C.c_uint64), ("n_unknown_contig", C.c_uint64)]
+
+
+class QtlRegion(C.Structure):
+    _fields_ = [("tid", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32)]
+
+
+class QtlResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("dof", C.c_uint32),
+                ("n_pairs", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)), ("yy", C.POINTER(C.c_double)), ("gg", C.POINTER(C.c_double)),
+                ("pair_begin", C.POINTER(C.c_uint32)), ("pair_variant", C.POINTER(C.c_uint32)), ("r", C.POINTER(C.c_double)),
+                ("slope", C.POINTER(C.c_double)), ("best", C.POINTER(C.c_uint32)),
+                ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("ms_qtl", C.c_double), ("ms_residual", C.c_double), ("ms_pairs", C.c_double)]
 
 
 class IdentifyParams(C.Structure):
@@ -268,6 +289,21 @@ def lib():
         L.rgx_cohort_pheno_pcs_free.argtypes = [P(PhenoPCs)]
         L.rgx_cohort_format_pheno_pcs.argtypes = [P(CohortMatrix), P(PhenoPCs), C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_pheno_pcs.restype = C.c_size_t
+        qtl_in = [P(PhenoTable), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(P(QtlResult)),
+                  C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_nominal.argtypes = [C.c_void_p] + qtl_in
+        L.rgx_cohort_qtl_nominal_host.argtypes = qtl_in
+        L.rgx_cohort_qtl_free.argtypes = [P(QtlResult)]
+        L.rgx_cohort_pheno_regions.argtypes = [P(CohortMatrix), P(PhenoTable), C.c_void_p, C.c_char_p, C.c_size_t]
+        L.rgx_genotypes_load.argtypes = [C.c_char_p, P(CohortMatrix), P(P(Genotypes)), C.c_char_p, C.c_size_t]
+        L.rgx_genotypes_free.argtypes = [P(Genotypes)]
+        L.rgx_qtl_tstat.argtypes = [C.c_double, C.c_uint32]
+        L.rgx_qtl_tstat.restype = C.c_double
+        L.rgx_qtl_pvalue.argtypes = [C.c_double, C.c_uint32]
+        L.rgx_qtl_pvalue.restype = C.c_double
+        L.rgx_cohort_format_qtl.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlResult), C.c_void_p, P(C.c_char_p), C.c_char_p,
+                                            C.c_size_t]
+        L.rgx_cohort_format_qtl.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -263,6 +263,133 @@ class CohortPCs(object):
             pass
 
 
+class CohortQTL(object):
+    """rgx_qtl_result: the nominal cis-sQTL scan of a phenotype table -- per variant its verdict (0 usable, 1 constant, 2 explained by the
+    covariates) and gg, per row yy, the pairs as a CSR (pair_begin, pair_variant) with r and slope, and per row its best pair (NO_PAIR: none).
+    The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+    NO_PAIR = 0xffffffff
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.dof, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_pairs)
+        self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
+        self.n_tiles = int(p.n_tiles)
+        self.ms_qtl, self.ms_residual, self.ms_pairs = p.ms_qtl, p.ms_residual, p.ms_pairs
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        K, V, n = self.n_rows, self.n_variants, self.n_pairs
+        self.variant_verdict = view(p.variant_verdict, V, np.uint8)
+        self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
+        self.pair_begin, self.pair_variant = view(p.pair_begin, K + 1, np.uint32), view(p.pair_variant, n, np.uint32)
+        self.r, self.slope, self.best = view(p.r, n, np.float64), view(p.slope, n, np.float64), view(p.best, K, np.uint32)
+
+    def text(self, matrix, clusters, ph, var_pos, variant_ids):
+        """The pairs as text: phenotype_id, variant_id, distance, r, slope, slope_se, tstat, pval_nominal, is_best; one line per pair.  matrix,
+        clusters and ph are what the scan came from; var_pos and variant_ids (str or bytes) are per input variant."""
+        import numpy as np
+        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
+        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
+            raise ValueError("one position and one id per variant")
+        fn = self._lib.rgx_cohort_format_qtl
+        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_qtl_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Genotypes(object):
+    """rgx_genotypes: the dosages of a matrix's samples from a VCF or BCF -- tid, pos (V), dosage (V x S int8), ids (V, bytes), sorted by (tid, pos),
+    and the counts of the records left out.  Copies: nothing here refers to the library's memory."""
+
+    def __init__(self, path, matrix):
+        import numpy as np
+        lib = _ffi.lib()
+        out = C.POINTER(_ffi.Genotypes)()
+        err = C.create_string_buffer(1024)
+        rc = lib.rgx_genotypes_load(os.fsencode(path), matrix._h, C.byref(out), err, len(err))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        g = out.contents
+        V, S = int(g.n_variants), int(g.n_samples)
+        self.n_variants, self.n_samples = V, S
+        self.n_records, self.n_multiallelic, self.n_no_gt, self.n_unknown_contig = (int(g.n_records), int(g.n_multiallelic), int(g.n_no_gt),
+                                                                                   int(g.n_unknown_contig))
+        self.tid = np.ctypeslib.as_array(g.tid, shape=(V,)).copy() if V else np.zeros(0, np.uint32)
+        self.pos = np.ctypeslib.as_array(g.pos, shape=(V,)).copy() if V else np.zeros(0, np.uint32)
+        self.dosage = np.ctypeslib.as_array(g.dosage, shape=(V * S,)).copy().reshape(V, S) if V * S else np.zeros((V, S), np.int8)
+        self.ids = [g.id[v] for v in range(V)]
+        lib.rgx_genotypes_free(out)
+
+
+def genotypes(path, matrix):
+    """rgx_genotypes_load: the genotypes of `matrix`'s samples, matched by name, from the VCF or BCF at `path`."""
+    return Genotypes(path, matrix)
+
+
+def qtl_tstat(r, dof):
+    """rgx_qtl_tstat: r * sqrt(dof / (1 - r * r)), an infinity of r's sign when 1 - r * r <= 0."""
+    return _ffi.lib().rgx_qtl_tstat(r, dof)
+
+
+def qtl_pvalue(t, dof):
+    """rgx_qtl_pvalue: the two-sided p of Student's t with dof degrees of freedom, on the host."""
+    return _ffi.lib().rgx_qtl_pvalue(t, dof)
+
+
+def pheno_regions(matrix, ph):
+    """rgx_cohort_pheno_regions: K x 3 uint32 (tid, start, end) of the matrix rows the phenotype table kept."""
+    import numpy as np
+    out = np.zeros((ph.n_rows, 3), np.uint32)
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_pheno_regions(matrix._h, ph._h, out.ctypes.data, err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return out
+
+
+def _qtl_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window):
+    import numpy as np
+    S = ph.n_samples
+    reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1, 3)
+    tid, pos = np.ascontiguousarray(var_tid, dtype=np.uint32), np.ascontiguousarray(var_pos, dtype=np.uint32)
+    dos = np.ascontiguousarray(dosage, dtype=np.int8).reshape(-1, S) if S else np.zeros((0, 0), np.int8)
+    cov = np.ascontiguousarray(covariates, dtype=np.float64).reshape(-1, S) if covariates is not None and len(covariates) else np.zeros((0, S))
+    if len(reg) != ph.n_rows or len(pos) != len(tid) or len(dos) != len(tid):
+        raise ValueError("one region per table row, one position and one row of dosages per variant")
+    if not 0 <= int(window) <= 0xffffffff:
+        raise ValueError("window must fit 32 bits")
+    out = C.POINTER(_ffi.QtlResult)()
+    err = C.create_string_buffer(512)
+    rc = fn(*(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
+                       C.byref(out), err, len(err))))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortQTL(out)
+
+
+def qtl_nominal_host(ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000):
+    """rgx_cohort_qtl_nominal_host: the nominal cis-sQTL scan by the library's plain C++ twin, no device involved.  regions: K x 3 (tid, start,
+    end); var_tid, var_pos: V, ascending; dosage: V x S int8 in {0, 1, 2, -1}; covariates: n_cov x S or None."""
+    return _qtl_call(_ffi.lib().rgx_cohort_qtl_nominal_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window)
+
+
 class PlantedPhenotypes(object):
     """A K x S uint32 array as the rgx_pheno_table the principal component calls read (n_rows, n_samples and rank2 alone are set).  The memory is
     the array's own (a C-contiguous copy when it is not one already), kept alive by this object."""
@@ -404,6 +531,12 @@ class Cohort(object):
         if rc != 0:
             raise RegtoolsError(rc, err.value.decode())
         return CohortPCs(out)
+
+    def qtl_nominal(self, ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000):
+        """The nominal cis-sQTL scan of the phenotype table `ph` on this cohort's device (rgx_cohort_qtl_nominal): residuals of rows and variants
+        against intercept + covariates, then r and slope of every (row, variant within `window` of its intron) pair.  Arguments as
+        qtl_nominal_host."""
+        return _qtl_call(self._lib.rgx_cohort_qtl_nominal, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

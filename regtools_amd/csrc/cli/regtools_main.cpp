@@ -269,6 +269,12 @@ void cohort_usage(std::ostream &out) {
         << "\t\t-P FILE\tThe principal components of the -q table, the covariates of an sQTL run, laid out as LeafCutter's .PCs file: one line\n"
         << "\t\t\t per component, one column per sample. The table is computed as for -q, whether or not -q is given.\n"
         << "\t\t-C INT\tThe number of components -P writes, at most the table's rows and the samples. [10]\n"
+        << "\t\t-g FILE\tThe samples' genotypes for -Q: a VCF (plain, gzip, bgzip) or a BCF whose sample names are the cohort's. The dosage is the\n"
+        << "\t\t\t number of non-reference alleles of a diploid GT call of a biallelic record.\n"
+        << "\t\t-Q FILE\tThe nominal cis-sQTL scan: every row of the -q table against every variant of -g within the window around its intron,\n"
+        << "\t\t\t with an intercept and the first -C components (at most the samples less three) in the model: one line per pair with\n"
+        << "\t\t\t r, slope, its standard error, t and the two-sided p. The table and the components are computed as for -q and -P.\n"
+        << "\t\t-w INT\tThe cis window of -Q on either side of the intron. [100000]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -334,8 +340,8 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA";
-        uint32_t n_components = 10;
+        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA";
+        uint32_t n_components = 10, window = 100000;
         rgx_pheno_params qp;
         rgx_pheno_params_default(&qp);
         rgx_cohort_params cp;
@@ -348,7 +354,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -371,6 +377,17 @@ int junctions_cohort(int argc, char **argv) {
                     refine = true; break;
                 case 'q': phenotypes = optarg; break;
                 case 'P': components = optarg; break;
+                case 'g': genotypes = optarg; break;
+                case 'Q': qtl = optarg; break;
+                case 'w': {
+                    char *end = nullptr;
+                    errno = 0;
+                    const long long v = strtoll(optarg, &end, 10);
+                    if (end == optarg || *end || errno || v < 0 || v > 0xffffffffll || optarg[0] == ' ' || optarg[0] == '+' || optarg[0] == '-')
+                        throw std::runtime_error("Unrecognized window argument!\n\n");
+                    window = (uint32_t)v;
+                    break;
+                }
                 case 'C': {
                     char *end = nullptr;
                     errno = 0;
@@ -417,6 +434,7 @@ int junctions_cohort(int argc, char **argv) {
         for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
         if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
         if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
+        if (qtl != "NA" && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
         for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
         for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
             throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
@@ -463,16 +481,33 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        const bool want_pheno = phenotypes != "NA" || components != "NA";
+        const bool want_qtl = qtl != "NA", want_pheno = phenotypes != "NA" || components != "NA" || want_qtl;
         if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
         rgx_pheno_table *ph = nullptr;
         if (ok && want_pheno && rgx_cohort_phenotypes(co, m, cl, &qp, &ph, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         // -C clipped to the table; a table of fewer than two rows (or of no samples) has no components: the file is its header line
         rgx_pheno_pcs *pcs = nullptr;
-        const uint32_t n_pcs = ph && components != "NA" && ph->n_rows >= 2 ? (uint32_t)std::min<uint64_t>({n_components, ph->n_rows, ph->n_samples}) : 0;
-        if (ok && n_pcs && rgx_cohort_pheno_pcs(co, ph, n_pcs, &pcs, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        const uint32_t n_clip = ph && ph->n_rows >= 2 ? (uint32_t)std::min<uint64_t>({n_components, ph->n_rows, ph->n_samples}) : 0;
+        const uint32_t n_pcs = components != "NA" ? n_clip : 0;
+        // -Q: the first n_cov components are the covariates -- those of -C further clipped to the samples less three -- of the same decomposition
+        const uint32_t n_cov = want_qtl && ph && ph->n_samples >= 3 ? std::min<uint32_t>(n_clip, ph->n_samples - 3) : 0;
+        if (ok && std::max(n_pcs, n_cov) && rgx_cohort_pheno_pcs(co, ph, std::max(n_pcs, n_cov), &pcs, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        rgx_genotypes *gt = nullptr;
+        if (ok && want_qtl && rgx_genotypes_load(genotypes.c_str(), m, &gt, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        // a table without rows has no pairs: the file is its header line
+        rgx_qtl_result *qr = nullptr;
+        if (ok && want_qtl && ph->n_rows) {
+            std::vector<rgx_qtl_region> regions((size_t)ph->n_rows);
+            int rc = rgx_cohort_pheno_regions(m, ph, regions.data(), err, sizeof err);
+            if (rc == RGX_OK) rc = rgx_cohort_qtl_nominal(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov, pcs ? pcs->component : nullptr,
+                                                          window, &qr, err, sizeof err);
+            if (rc != RGX_OK) { failure = err; ok = false; }
+        }
         if (!ok) {
+            rgx_cohort_qtl_free(qr);
+            rgx_genotypes_free(gt);
+            rgx_cohort_pheno_pcs_free(pcs);
             if (ph) rgx_cohort_phenotypes_free(ph);
             if (cl) rgx_cohort_clusters_free(cl);
             if (m) rgx_cohort_matrix_free(m);
@@ -493,7 +528,13 @@ int junctions_cohort(int argc, char **argv) {
         size_t nq = 0; std::unique_ptr<char[]> qtx;
         if (ph && phenotypes != "NA") { nq = rgx_cohort_format_phenotypes(m, cl, ph, nullptr, 0); qtx.reset(new char[nq + 1]); rgx_cohort_format_phenotypes(m, cl, ph, qtx.get(), nq); }
         size_t np = 0; std::unique_ptr<char[]> ptx;
-        if (components != "NA") { np = rgx_cohort_format_pheno_pcs(m, pcs, nullptr, 0); ptx.reset(new char[np + 1]); rgx_cohort_format_pheno_pcs(m, pcs, ptx.get(), np); }
+        if (components != "NA") {
+            // (beside -Q with more covariates than -P has components this cannot be: n_cov <= n_clip = n_pcs)
+            np = rgx_cohort_format_pheno_pcs(m, pcs, nullptr, 0); ptx.reset(new char[np + 1]); rgx_cohort_format_pheno_pcs(m, pcs, ptx.get(), np); }
+        size_t nt = 0; std::unique_ptr<char[]> ttx;
+        if (want_qtl) {
+            nt = rgx_cohort_format_qtl(m, cl, ph, qr, gt->pos, gt->id, nullptr, 0); ttx.reset(new char[nt + 1]);
+            rgx_cohort_format_qtl(m, cl, ph, qr, gt->pos, gt->id, ttx.get(), nt); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -518,6 +559,11 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + components + "\n\n");
             short_write |= fwrite(ptx.get(), 1, np, g) != np; short_write |= fclose(g) != 0;
         }
+        if (want_qtl) {
+            FILE *g = fopen(qtl.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + qtl + "\n\n");
+            short_write |= fwrite(ttx.get(), 1, nt, g) != nt; short_write |= fclose(g) != 0;
+        }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
             fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
@@ -533,6 +579,15 @@ int junctions_cohort(int argc, char **argv) {
         if (components != "NA" && ph && getenv("REGTOOLS_AMD_STATS"))
             fprintf(stderr, "[regtools_amd] pcs: %llu rows, %u samples, %u components written, %.3f ms (gram %.3f ms, eigen %.3f ms)\n",
                     (unsigned long long)ph->n_rows, ph->n_samples, n_pcs, pcs ? pcs->ms_pcs : 0.0, pcs ? pcs->ms_gram : 0.0, pcs ? pcs->ms_eigen : 0.0);
+        if (want_qtl && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] qtl: %u variants of %llu records (%llu multi-allelic, %llu without GT, %llu on contigs the cohort does not know), "
+                    "%u covariates, %llu pairs written, %llu constant variants, %llu explained, %llu flat rows, %.3f ms (residuals %.3f ms, pairs %.3f ms)\n",
+                    gt->n_variants, (unsigned long long)gt->n_records, (unsigned long long)gt->n_multiallelic, (unsigned long long)gt->n_no_gt,
+                    (unsigned long long)gt->n_unknown_contig, n_cov, (unsigned long long)(qr ? qr->n_pairs : 0), (unsigned long long)(qr ? qr->n_constant : 0),
+                    (unsigned long long)(qr ? qr->n_explained : 0), (unsigned long long)(qr ? qr->n_flat_rows : 0), qr ? qr->ms_qtl : 0.0,
+                    qr ? qr->ms_residual : 0.0, qr ? qr->ms_pairs : 0.0);
+        rgx_cohort_qtl_free(qr);
+        rgx_genotypes_free(gt);
         rgx_cohort_pheno_pcs_free(pcs);
         rgx_cohort_phenotypes_free(ph);
         rgx_cohort_clusters_free(cl);

@@ -86,8 +86,14 @@ struct rgx_cohort {
     DevBuf ph_in, ph_rows, ph_entries;
     // rgx_cohort_pheno_pcs (cohort_pcs.cpp): rank2 and the quantile table, the chunk partials, the Gram matrix with the column sums
     DevBuf pc_in, pc_part, pc_out;
+    // rgx_cohort_qtl_nominal (cohort_qtl.cpp): the uploaded inputs, the row-major residuals with the per-row and per-variant arrays, the
+    // sample-major panels, the pairs
+    DevBuf qt_in, qt_rows, qt_t, qt_out;
 };
 
 // cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the
 // columns the cluster and phenotype kernels need, uploaded on st into co->cl_in
 int cohort_matrix_image(rgx_cohort *co, const rgx_cohort_matrix *m, hipStream_t st, CohortImage *in, char *err, size_t errlen);
+
+// cohort_pcs.cpp: T[r - 2] = rgx_pheno_quantile(r, K) for r = 2 .. 2 K, the table the principal components and the sQTL scan look rank2 up in
+void pheno_quantile_table(uint64_t K, std::vector<double> &T);

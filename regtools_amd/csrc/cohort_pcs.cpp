@@ -257,6 +257,8 @@ bool twin_rows_plain(const uint32_t *rank2, const double *T, uint64_t K, uint32_
 
 }  // namespace
 
+void pheno_quantile_table(uint64_t K, std::vector<double> &T) { quantile_table(K, T); }
+
 extern "C" void rgx_cohort_pheno_pcs_free(rgx_pheno_pcs *pcs) {
     if (!pcs) return;
     PcsBox *box = (PcsBox *)pcs;                                      // pcs is the first member

@@ -398,4 +398,28 @@ void launch_pca_gram(const uint32_t *rank2, const double *T, uint64_t K, uint32_
 // gram (S x S, both triangles) and col_sum (S): the chunk partials in ascending chunk order
 void launch_pca_reduce(const double *part, const double *col_part, uint64_t K, uint32_t S, double *gram, double *col_sum, hipStream_t st);
 
+// ---- the cohort's nominal cis-sQTL scan (qtl_kernels.hip; host side in cohort_qtl.cpp; arithmetic in qtl_core.h) ------------------------------------
+// Residuals against the C unit vectors of Q (C x S), row-major: Y (K x S) with yy, G (V x S) with gg, the verdicts and the usable flags.  flag: two
+// words (qtl_core.h), zeroed by the caller
+void launch_qtl_residual_pheno(const uint32_t *rank2, const double *T, uint32_t K, uint32_t S, const double *Q, uint32_t C, double *Y, double *yy,
+                               uint32_t *flag, hipStream_t st);
+void launch_qtl_residual_geno(const int8_t *dosage, uint32_t V, uint32_t S, const double *Q, uint32_t C, double *G, double *gg, uint8_t *verdict,
+                              uint32_t *usable, uint32_t *flag, hipStream_t st);
+// place = exclusive scan of usable: the usable variants side by side
+void launch_qtl_compact(const uint32_t *usable, const uint32_t *place, uint32_t V, const uint32_t *var_tid, const uint32_t *var_pos, const double *gg,
+                        uint32_t *u_var, uint64_t *u_key, double *u_gg, hipStream_t st);
+// dst[s * ld + i] = src[(idx ? idx[i] : i) * S + s] for i < (n ? *n : n_fixed), +0.0 behind that up to ld
+void launch_qtl_transpose(const double *src, const uint32_t *idx, const uint32_t *n, uint32_t n_fixed, uint32_t S, size_t ld, double *dst,
+                          hipStream_t st);
+// lo and count (K + 1 words, the last 0) per row, blk_lo and tile_count (ceil(K / 64) + 1 words, the last 0) per block of 64 rows, and
+// totals = {the sum of count, the sum of tile_count}
+void launch_qtl_plan(const uint32_t *regions, uint32_t K, uint32_t S, const double *yy, const uint64_t *u_key, const uint32_t *n_usable,
+                     uint32_t window, uint32_t *lo, uint32_t *count, uint32_t *blk_lo, uint32_t *tile_count, unsigned long long *totals,
+                     hipStream_t st);
+// Yt: ldy a multiple of 64 at or above K; Gt: ldg at or above the usable variants + 63; both zero behind their last column
+void launch_qtl_pairs(const double *Yt, size_t ldy, const double *Gt, size_t ldg, uint32_t S, uint32_t K, uint32_t n_tiles, const uint32_t *tile_begin,
+                      const uint32_t *blk_lo, const uint32_t *lo, const uint32_t *count, const uint32_t *pair_begin, const double *yy,
+                      const double *u_gg, const uint32_t *u_var, double *r, double *slope, uint32_t *pair_variant, hipStream_t st);
+void launch_qtl_best(const double *r, const uint32_t *pair_begin, uint32_t K, uint32_t *best, hipStream_t st);
+
 }  // namespace rgx

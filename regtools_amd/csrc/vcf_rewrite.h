@@ -41,6 +41,7 @@ class VcfDictionary {
     void note(const std::string &line);
 
     size_t n_samples() const { return samples_.size(); }
+    const std::vector<std::string> &sample_names() const { return samples_; }
     bool knows_contig(const std::string &name) const { return contig_number_.count(name) != 0; }
     // "" for a number nothing was registered under
     const std::string &contig_name(int number) const { return name_in(contig_names_, number); }

@@ -29,6 +29,12 @@
                     (default 10, clipped to the table), rgx_cohort_pheno_pcs_host's times, whether every array was identical to the twin's as bit
                     patterns, and K S (S + 1) / 2 fused multiply-adds over ms_gram as GFMA/s
 
+  --qtl             rgx_cohort_qtl_nominal (ms_qtl, ms_residual, ms_pairs) on planted tables --planted "SAMPLESxROWSxVARIANTS,..."
+                    (planted_rank2's table; rows and variants spread evenly over one contig of 500 bases per row; binomial dosages, 2 % missing):
+                    first and warm calls with --n-cov principal components of the table as covariates (default 10, clipped) and --window (default
+                    100000), beside rgx_cohort_qtl_nominal_host; the pairs P, P S fused multiply-adds over ms_pairs as GFMA/s (and the 4,096 S per tile that were issued), and whether every
+                    device run was identical to the others and to the twin in every array as bit patterns
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -435,6 +441,59 @@ def part_pcs(a):
     co.close()
 
 
+QTL_ARRAYS = ("variant_verdict", "yy", "gg", "pair_begin", "pair_variant", "r", "slope", "best")
+
+
+def same_qtl(a, b):
+    def bits(x):
+        x = np.ascontiguousarray(x)
+        return x.view(np.uint64) if x.dtype == np.float64 else x
+    return a.n_pairs == b.n_pairs and all(np.array_equal(bits(getattr(a, k)), bits(getattr(b, k))) for k in QTL_ARRAYS)
+
+
+def part_qtl(a):
+    import regtools_amd
+    from regtools_amd import cohort
+    co = regtools_amd.Cohort(ctx=regtools_amd.Context(0))
+    for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
+        S, K, V = [int(x) for x in size.lower().split("x")]
+        t0 = time.time()
+        rng = np.random.default_rng(11)
+        ph = cohort.pheno_table_from_rank2(planted_rank2(S, K))
+        span = 500 * K
+        start = np.sort(rng.integers(1, span, K)).astype(np.uint32)
+        regions = np.stack([np.zeros(K, np.uint32), start, start + rng.integers(50, 5000, K).astype(np.uint32)], axis=1)
+        pos = np.sort(rng.integers(1, span, V)).astype(np.uint32)
+        dosage = rng.binomial(2, rng.uniform(0.05, 0.5, V)[:, None], (V, S)).astype(np.int8)
+        dosage[rng.random((V, S)) < 0.02] = -1
+        n_cov = max(0, min(a.n_cov, K, S - 3))
+        pcs = co.pheno_pcs(ph, n_cov) if n_cov else None
+        args = (ph, regions, np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None, a.window)
+        line = {"part": "qtl", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "window": a.window, "s_generate": round(time.time() - t0, 1)}
+        runs = [co.qtl_nominal(*args) for _ in range(a.reps)]
+        warm = runs[1:] or runs
+        best = min(warm, key=lambda q: q.ms_pairs)
+        P = runs[0].n_pairs
+        line.update({"pairs": P, "usable_variants": int((runs[0].variant_verdict == 0).sum()), "flat_rows": runs[0].n_flat_rows,
+                     "ms_qtl": [round(q.ms_qtl, 3) for q in runs], "ms_residual": [round(q.ms_residual, 3) for q in runs],
+                     "ms_pairs": [round(q.ms_pairs, 3) for q in runs], "ms_pairs_best_warm": round(best.ms_pairs, 3), "fmas": P * S,
+                     "tiles": runs[0].n_tiles, "tile_fill": round(P / (4096.0 * runs[0].n_tiles), 3) if runs[0].n_tiles else None,
+                     "GFMA_per_s_issued_over_ms_pairs": round(4096.0 * runs[0].n_tiles * S / best.ms_pairs / 1e6, 1) if best.ms_pairs > 0 else None,
+                     "GFMA_per_s_over_ms_pairs": round(P * S / best.ms_pairs / 1e6, 1) if best.ms_pairs > 0 else None,
+                     "identical_every_time": bool(all(same_qtl(runs[0], q) for q in runs[1:]))})
+        assert line["identical_every_time"], "two device runs differ"
+        if not a.no_host:
+            h = cohort.qtl_nominal_host(*args)
+            line.update({"ms_qtl_host": round(h.ms_qtl, 1), "ms_residual_host": round(h.ms_residual, 1), "ms_pairs_host": round(h.ms_pairs, 1),
+                         "identical_to_host": bool(same_qtl(runs[0], h))})
+            assert line["identical_to_host"], "the device's scan differs from the host twin's"
+            h.close()
+        for q in runs:
+            q.close()
+        print(json.dumps(line), flush=True)
+    co.close()
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -492,7 +551,10 @@ def main():
     ap.add_argument("--refine", action="store_true", help="the refine part, alone")
     ap.add_argument("--pheno", action="store_true", help="the phenotype part, alone")
     ap.add_argument("--pcs", action="store_true", help="the principal component part, alone")
-    ap.add_argument("--planted", default="", help="--pcs: planted tables, SAMPLESxROWS, comma separated")
+    ap.add_argument("--qtl", action="store_true", help="the sQTL scan part, alone")
+    ap.add_argument("--n-cov", type=int, default=10, help="--qtl: principal components taken as covariates (clipped to the samples less three)")
+    ap.add_argument("--window", type=int, default=100000, help="--qtl: the cis window")
+    ap.add_argument("--planted", default="", help="--pcs: planted tables, SAMPLESxROWS; --qtl: SAMPLESxROWSxVARIANTS; comma separated")
     ap.add_argument("--n-pcs", type=int, default=10, help="--pcs: components asked for (clipped to the table)")
     ap.add_argument("--pheno-params", default="4/10,0.005", help="num/den of the missing share, min_sd")
     ap.add_argument("--refine-params", default="100000,5,1/1000,2,30", help="max_intron,min_reads,num/den,min_rows,min_total")
@@ -510,6 +572,8 @@ def main():
         return part_pheno(a)
     if a.pcs:
         return part_pcs(a)
+    if a.qtl:
+        return part_qtl(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
