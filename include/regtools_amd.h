@@ -567,6 +567,94 @@ double rgx_qtl_pvalue(double t, uint32_t dof);
 size_t rgx_cohort_format_qtl(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, const rgx_qtl_result *q,
                              const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
 
+/* -----------------------------------------------------------------------------------------------------
+ * The permutation pass of the cis-sQTL scan: per table row the largest |r| over its cis variants, for the row as it is and for B permutations of
+ * its samples, the empirical p of the row's best variant and its beta approximation -- FastQTL's --permute and tensorQTL's map_cis, neither of
+ * which is available to this project: checked against a restatement in exact rationals, scipy and mpmath.  DELIBERATE DEVIATIONS: the degrees of
+ * freedom are not re-estimated from the permutations, and the number of permutations is not adaptive.
+ *   input                 everything rgx_cohort_qtl_nominal takes; n_perm = B; perm: (B + 1) x S uint16, row-major, row 0 the identity, every
+ *                         row a permutation of 0 .. S - 1 (rgx_qtl_permutations fills one)
+ *   errors                RGX_ERR_ARG, before any launch: the nominal scan's; B == 0 or B > 65535; row 0 not the identity; a row that is no
+ *                         permutation; K (B + 1) > 2^32 - 2^16.  The flag words as in the nominal scan
+ *   steps                 basis, dot64, residuals Y[k] with yy, G[v] with gg, verdicts, flat rows and cis ranges: the nominal contract's, unchanged.
+ *                         No pair array is produced and P has no limit: n_cis[k] = the row's number of pairs, n_pairs their 64-bit sum
+ *   per (k, b, cis v)     dot = ONE chain acc = fma(Y[k][perm[b][s]], G[v][s], acc) in ascending s from +0.0; r = dot / sqrt(yy[k] * gg[v]) with
+ *                         the yy of the UNPERMUTED row, every operation rounded on its own
+ *   perm_r[k][b]          the largest |r| over the row's cis variants, compared and stored as bit patterns (no order to fix), b = 0 .. B; +0.0
+ *                         throughout for a row without pairs
+ *   best                  of b = 0: best_variant[k] = the input variant with the largest |r|, the earliest on ties, RGX_NO_PAIR without pairs;
+ *                         best_r[k] (signed) and best_slope[k] = dot / gg: bit for bit the nominal scan's r and slope at best[k]; +0.0 without
+ *   n_ge, p_perm          n_ge[k] = #{b in 1 .. B: bits(perm_r[k][b]) >= bits(perm_r[k][0])}; p_perm[k] = (n_ge + 1) / (B + 1)
+ *   beta approximation    on the HOST, by one function for the device path and the twin (rgx_qtl_beta_fit below), rows shared among threads,
+ *                         each row's sums in ascending b: p_b = rgx_qtl_pvalue(rgx_qtl_tstat(perm_r[k][b], dof), dof) clipped to
+ *                         [DBL_MIN, 1 - 2^-53] for b = 1 .. B; p_beta[k] = I_x(shape1, shape2) at x = rgx_qtl_pvalue(rgx_qtl_tstat(best_r[k],
+ *                         dof), dof).  beta_status[k]: 0 converged, 1 the moment estimates kept, 2 no fit (no pairs, B < 2, zero variance or
+ *                         moment estimates outside (0, inf)): shapes and p_beta NaN
+ * ----------------------------------------------------------------------------------------------------- */
+/* Owned by the library (rgx_cohort_qtl_perm_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_variants;      /* V */
+    uint32_t   n_cov;
+    uint32_t   dof;             /* S - n_cov - 2 */
+    uint32_t   n_perm;          /* B */
+    uint64_t   n_pairs;         /* the sum of n_cis */
+    uint8_t   *variant_verdict; /* V: 0 usable, 1 constant, 2 explained by the covariates */
+    double    *yy;              /* K */
+    double    *gg;              /* V */
+    uint32_t  *n_cis;           /* K: the row's pairs */
+    double    *perm_r;          /* K x (B + 1), row-major */
+    uint32_t  *best_variant;    /* K: an input variant, or RGX_NO_PAIR */
+    double    *best_r, *best_slope;   /* K */
+    uint32_t  *n_ge;            /* K */
+    double    *p_perm;          /* K */
+    double    *beta_shape1, *beta_shape2, *p_beta;   /* K */
+    uint8_t   *beta_status;     /* K */
+    /* statistics */
+    uint64_t   n_constant, n_explained, n_flat_rows;
+    uint64_t   n_tiles;         /* the device's products of 64 permutations x 64 usable variants: per row ceil((B + 1) / 64) * ceil(n_cis / 64)
+                                   (the twin: 0) */
+    double     ms_perm;         /* this call, wall */
+    double     ms_residual;     /* device time from the first upload to the sample-major residuals (the twin: its residual loops, wall) */
+    double     ms_products;     /* device time of the permuted products and the best pairs (the twin: its loops, wall) */
+    double     ms_beta;         /* the beta approximation, host wall */
+} rgx_qtl_perm_result;
+/* out[(B + 1) x S]: row 0 the identity, rows 1 .. B Fisher-Yates shuffles drawn in order from ONE splitmix64 stream: z starts at the seed; next():
+ * z += 0x9E3779B97F4A7C15, x = z, x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9, x = (x ^ x >> 27) * 0x94D049BB133111EB, x ^ x >> 31.  A row starts
+ * from the identity; for i = S - 1 down to 1: j = (next() * (i + 1)) >> 64 (the 128-bit product), swap p[i] and p[j].  RGX_ERR_ARG for S == 0,
+ * S > 65536 or B > 65535. */
+int  rgx_qtl_permutations(uint32_t n_samples, uint32_t n_perm, uint64_t seed, uint16_t *out, char *err, size_t errlen);
+/* On the cohort's device and stream: the nominal scan's residuals, compaction, G transpose and plan, then one workgroup per (row, 64 permutations)
+ * over all the row's tiles of 64 usable variants, a thread per row for the best pair, ONE host wait in front of the copies back, the beta
+ * approximation on the host. */
+int  rgx_cohort_qtl_permute(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants,
+                            const uint32_t *var_tid, const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates,
+                            uint32_t window, uint32_t n_perm, const uint16_t *perm, rgx_qtl_perm_result **out, char *err, size_t errlen);
+/* Host twin: the same chains in plain C++ (std::fma), the same beta function, no device.  NOT a fallback. */
+int  rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                                 const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, uint32_t window,
+                                 uint32_t n_perm, const uint16_t *perm, rgx_qtl_perm_result **out, char *err, size_t errlen);
+void rgx_cohort_qtl_perm_free(rgx_qtl_perm_result *q);
+/* psi(x) and psi'(x) for x > 0 (NaN otherwise), in long double: the recurrence up to x >= 32, then the asymptotic series. */
+double rgx_qtl_digamma(double x);
+double rgx_qtl_trigamma(double x);
+/* The regularised incomplete beta function I_x(a, b), a, b > 0, 0 <= x <= 1 (NaN otherwise): rgx_qtl_pvalue's Lentz fraction with the prefactor
+ * exp(a log x + b log1p(-x) - lgammal(a) - lgammal(b) + lgammal(a + b)), in long double; the fraction of (b, a, 1 - x) when x is beyond
+ * (a + 1) / (a + b + 2). */
+double rgx_qtl_betainc(double x, double a, double b);
+/* The beta distribution fitted to p[0 .. n) (each inside (0, 1)) by maximum likelihood, sums in ascending order, long double: mean m and variance
+ * v (divisor n); the moment start a = m (m (1 - m) / v - 1), b = a (1 / m - 1); Newton on psi(a) - psi(a + b) = mean log p, psi(b) - psi(a + b) =
+ * mean log(1 - p) with the trigamma Jacobian, the step halved while a or b would leave (0, inf), at most 100 steps, done when both relative
+ * changes are below 1e-12.  Returns the status of beta_status above (2: n < 2, v == 0 or a moment estimate outside (0, inf); shapes NaN). */
+int  rgx_qtl_beta_fit(const double *p, uint32_t n, double *shape1, double *shape2);
+/* "phenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\tpval_perm\tpval_beta" and
+ * one line per table row that has pairs, in row order: the ID and distance of rgx_cohort_format_qtl for best_variant, num_var = n_cis, doubles as
+ * %.17g, NaN as "nan".  q == NULL writes the header line alone; 0 when the arguments do not fit together.  Buffer protocol of
+ * rgx_cohort_format_counts. */
+size_t rgx_cohort_format_qtl_perm(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, const rgx_qtl_perm_result *q,
+                                  const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
+
 /* The genotypes of a cohort's samples from a VCF (plain, gzip, bgzip) or a BCF, as rgx_cohort_qtl_nominal takes them.  Samples are matched to
  * m->sample_name BY NAME; a cohort sample the file does not have is RGX_ERR_ARG, "Sample <name> has no genotypes in <file>".  A record is
  * skipped, and counted, when it is multi-allelic (anything but one ALT), carries no GT, or lies on a contig m does not know.  The dosage is the

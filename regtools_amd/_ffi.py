@@ -60,7 +60,9 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_cohort_format_phenotypes",
            "rgx_cohort_pheno_pcs", "rgx_cohort_pheno_pcs_host", "rgx_cohort_pheno_pcs_free", "rgx_cohort_format_pheno_pcs",
            "rgx_cohort_pheno_regions", "rgx_cohort_qtl_nominal", "rgx_cohort_qtl_nominal_host", "rgx_cohort_qtl_free", "rgx_qtl_tstat",
-           "rgx_qtl_pvalue", "rgx_cohort_format_qtl", "rgx_genotypes_load", "rgx_genotypes_free"]
+           "rgx_qtl_pvalue", "rgx_cohort_format_qtl", "rgx_genotypes_load", "rgx_genotypes_free",
+           "rgx_qtl_permutations", "rgx_cohort_qtl_permute", "rgx_cohort_qtl_permute_host", "rgx_cohort_qtl_perm_free", "rgx_qtl_digamma",
+           "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm"]
 
 
 class CohortParams(C.Structure):
@@ -127,6 +129,17 @@ class QtlResult(C.Structure):
                 ("slope", C.POINTER(C.c_double)), ("best", C.POINTER(C.c_uint32)),
                 ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
                 ("ms_qtl", C.c_double), ("ms_residual", C.c_double), ("ms_pairs", C.c_double)]
+
+
+class QtlPermResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("dof", C.c_uint32),
+                ("n_perm", C.c_uint32), ("n_pairs", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)), ("yy", C.POINTER(C.c_double)),
+                ("gg", C.POINTER(C.c_double)), ("n_cis", C.POINTER(C.c_uint32)), ("perm_r", C.POINTER(C.c_double)),
+                ("best_variant", C.POINTER(C.c_uint32)), ("best_r", C.POINTER(C.c_double)), ("best_slope", C.POINTER(C.c_double)),
+                ("n_ge", C.POINTER(C.c_uint32)), ("p_perm", C.POINTER(C.c_double)), ("beta_shape1", C.POINTER(C.c_double)),
+                ("beta_shape2", C.POINTER(C.c_double)), ("p_beta", C.POINTER(C.c_double)), ("beta_status", C.POINTER(C.c_uint8)),
+                ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("ms_perm", C.c_double), ("ms_residual", C.c_double), ("ms_products", C.c_double), ("ms_beta", C.c_double)]
 
 
 class IdentifyParams(C.Structure):
@@ -304,6 +317,21 @@ def lib():
         L.rgx_cohort_format_qtl.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlResult), C.c_void_p, P(C.c_char_p), C.c_char_p,
                                             C.c_size_t]
         L.rgx_cohort_format_qtl.restype = C.c_size_t
+        perm_in = [P(PhenoTable), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                   C.c_void_p, P(P(QtlPermResult)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_permute.argtypes = [C.c_void_p] + perm_in
+        L.rgx_cohort_qtl_permute_host.argtypes = perm_in
+        L.rgx_cohort_qtl_perm_free.argtypes = [P(QtlPermResult)]
+        L.rgx_qtl_permutations.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]
+        for fn in (L.rgx_qtl_digamma, L.rgx_qtl_trigamma):
+            fn.argtypes = [C.c_double]
+            fn.restype = C.c_double
+        L.rgx_qtl_betainc.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.rgx_qtl_betainc.restype = C.c_double
+        L.rgx_qtl_beta_fit.argtypes = [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_double)]
+        L.rgx_cohort_format_qtl_perm.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlPermResult), C.c_void_p, P(C.c_char_p),
+                                                 C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_qtl_perm.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -390,6 +390,134 @@ def qtl_nominal_host(ph, regions, var_tid, var_pos, dosage, covariates=None, win
     return _qtl_call(_ffi.lib().rgx_cohort_qtl_nominal_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window)
 
 
+class CohortQTLPerm(object):
+    """rgx_qtl_perm_result: the permutation pass of the cis-sQTL scan -- per variant its verdict and gg, per row yy, n_cis (its pairs), perm_r
+    (K x (B + 1): the largest |r| over its cis variants under the identity and the B permutations), the best pair of the identity (best_variant, an
+    input variant or NO_PAIR; best_r, best_slope), n_ge, p_perm, and the beta approximation (beta_shape1, beta_shape2, p_beta, beta_status: 0
+    converged, 1 moment estimates, 2 no fit).  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+    NO_PAIR = 0xffffffff
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.dof, self.n_perm, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_perm), int(p.n_pairs)
+        self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
+        self.n_tiles = int(p.n_tiles)
+        self.ms_perm, self.ms_residual, self.ms_products, self.ms_beta = p.ms_perm, p.ms_residual, p.ms_products, p.ms_beta
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        K, V, B1 = self.n_rows, self.n_variants, self.n_perm + 1
+        self.variant_verdict = view(p.variant_verdict, V, np.uint8)
+        self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
+        self.n_cis, self.perm_r = view(p.n_cis, K, np.uint32), view(p.perm_r, K * B1, np.float64).reshape(K, B1)
+        self.best_variant, self.best_r, self.best_slope = (view(p.best_variant, K, np.uint32), view(p.best_r, K, np.float64),
+                                                           view(p.best_slope, K, np.float64))
+        self.n_ge, self.p_perm = view(p.n_ge, K, np.uint32), view(p.p_perm, K, np.float64)
+        self.beta_shape1, self.beta_shape2 = view(p.beta_shape1, K, np.float64), view(p.beta_shape2, K, np.float64)
+        self.p_beta, self.beta_status = view(p.p_beta, K, np.float64), view(p.beta_status, K, np.uint8)
+
+    def text(self, matrix, clusters, ph, var_pos, variant_ids):
+        """One line per row that has pairs: phenotype_id, num_var, beta_shape1, beta_shape2, dof, variant_id, distance, r, slope, slope_se, tstat,
+        pval_nominal, pval_perm, pval_beta.  The arguments are CohortQTL.text's."""
+        import numpy as np
+        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
+        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
+            raise ValueError("one position and one id per variant")
+        fn = self._lib.rgx_cohort_format_qtl_perm
+        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_qtl_perm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def qtl_permutations(n_samples, n_perm, seed=0):
+    """rgx_qtl_permutations: (n_perm + 1) x n_samples uint16, row 0 the identity, rows 1 .. n_perm Fisher-Yates shuffles from one splitmix64
+    stream that starts at `seed`."""
+    import numpy as np
+    out = np.zeros((int(n_perm) + 1, int(n_samples)), np.uint16)
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_qtl_permutations(int(n_samples), int(n_perm), int(seed) & 0xffffffffffffffff, out.ctypes.data, err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return out
+
+
+def qtl_digamma(x):
+    """rgx_qtl_digamma: psi(x) for x > 0, on the host in long double."""
+    return _ffi.lib().rgx_qtl_digamma(x)
+
+
+def qtl_trigamma(x):
+    """rgx_qtl_trigamma: psi'(x) for x > 0, on the host in long double."""
+    return _ffi.lib().rgx_qtl_trigamma(x)
+
+
+def qtl_betainc(x, a, b):
+    """rgx_qtl_betainc: the regularised incomplete beta function I_x(a, b), on the host in long double."""
+    return _ffi.lib().rgx_qtl_betainc(x, a, b)
+
+
+def qtl_beta_fit(p):
+    """rgx_qtl_beta_fit: (status, shape1, shape2) of the beta distribution fitted to the values p, each inside (0, 1), by maximum likelihood."""
+    import numpy as np
+    a = np.ascontiguousarray(p, dtype=np.float64)
+    s1, s2 = C.c_double(), C.c_double()
+    status = _ffi.lib().rgx_qtl_beta_fit(a.ctypes.data, len(a), C.byref(s1), C.byref(s2))
+    return status, s1.value, s2.value
+
+
+def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms):
+    import numpy as np
+    S = ph.n_samples
+    reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1, 3)
+    tid, pos = np.ascontiguousarray(var_tid, dtype=np.uint32), np.ascontiguousarray(var_pos, dtype=np.uint32)
+    dos = np.ascontiguousarray(dosage, dtype=np.int8).reshape(-1, S) if S else np.zeros((0, 0), np.int8)
+    cov = np.ascontiguousarray(covariates, dtype=np.float64).reshape(-1, S) if covariates is not None and len(covariates) else np.zeros((0, S))
+    if len(reg) != ph.n_rows or len(pos) != len(tid) or len(dos) != len(tid):
+        raise ValueError("one region per table row, one position and one row of dosages per variant")
+    if not 0 <= int(window) <= 0xffffffff:
+        raise ValueError("window must fit 32 bits")
+    if perms is None:
+        if not 0 <= int(n_perm) <= 0xffffffff:
+            raise ValueError("n_perm must fit 32 bits")
+        n_perm = int(n_perm)
+        pm = qtl_permutations(S, n_perm, seed) if 1 <= n_perm <= 65535 else np.zeros((1, S), np.uint16)     # (the library refuses the count)
+    else:
+        pm = np.ascontiguousarray(perms, dtype=np.uint16).reshape(-1, S)
+        n_perm = len(pm) - 1
+        if n_perm < 0:
+            raise ValueError("perms needs the identity as its row 0")
+    out = C.POINTER(_ffi.QtlPermResult)()
+    err = C.create_string_buffer(512)
+    rc = fn(*(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
+                       n_perm, pm.ctypes.data, C.byref(out), err, len(err))))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return CohortQTLPerm(out)
+
+
+def qtl_permute_host(ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0, perms=None):
+    """rgx_cohort_qtl_permute_host: the permutation pass by the library's plain C++ twin, no device involved.  The arguments are
+    qtl_nominal_host's; perms: (B + 1) x S uint16 with the identity as row 0, or None for qtl_permutations(S, n_perm, seed)."""
+    return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms)
+
+
 class PlantedPhenotypes(object):
     """A K x S uint32 array as the rgx_pheno_table the principal component calls read (n_rows, n_samples and rank2 alone are set).  The memory is
     the array's own (a C-contiguous copy when it is not one already), kept alive by this object."""
@@ -537,6 +665,13 @@ class Cohort(object):
         against intercept + covariates, then r and slope of every (row, variant within `window` of its intron) pair.  Arguments as
         qtl_nominal_host."""
         return _qtl_call(self._lib.rgx_cohort_qtl_nominal, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window)
+
+    def qtl_permute(self, ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0, perms=None):
+        """The permutation pass of the cis-sQTL scan on this cohort's device (rgx_cohort_qtl_permute): per row the largest |r| over its cis variants
+        under the identity and n_perm permutations of the samples, the empirical p and its beta approximation.  Returns a CohortQTLPerm; the
+        arguments are qtl_permute_host's."""
+        return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
+                              seed, perms)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

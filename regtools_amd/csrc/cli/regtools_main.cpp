@@ -274,7 +274,12 @@ void cohort_usage(std::ostream &out) {
         << "\t\t-Q FILE\tThe nominal cis-sQTL scan: every row of the -q table against every variant of -g within the window around its intron,\n"
         << "\t\t\t with an intercept and the first -C components (at most the samples less three) in the model: one line per pair with\n"
         << "\t\t\t r, slope, its standard error, t and the two-sided p. The table and the components are computed as for -q and -P.\n"
-        << "\t\t-w INT\tThe cis window of -Q on either side of the intron. [100000]\n"
+        << "\t\t-w INT\tThe cis window of -Q and -R on either side of the intron. [100000]\n"
+        << "\t\t-R FILE\tThe permutation pass of the cis-sQTL scan: one line per row of the -q table that has variants of -g in its window, with its\n"
+        << "\t\t\t best variant, the empirical p of that variant's |r| among -B permutations of the samples and its beta approximation.\n"
+        << "\t\t\t Needs -g; the table, the components and the window are those of -Q, beside which it may stand.\n"
+        << "\t\t-B INT\tThe permutations of -R, 1 to 65535. [1000]\n"
+        << "\t\t-e INT\tThe seed of -R's permutations. [0]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -340,8 +345,9 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA";
-        uint32_t n_components = 10, window = 100000;
+        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA", perm = "NA";
+        uint32_t n_components = 10, window = 100000, n_perm = 1000;
+        uint64_t seed = 0;
         rgx_pheno_params qp;
         rgx_pheno_params_default(&qp);
         rgx_cohort_params cp;
@@ -354,7 +360,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -386,6 +392,25 @@ int junctions_cohort(int argc, char **argv) {
                     if (end == optarg || *end || errno || v < 0 || v > 0xffffffffll || optarg[0] == ' ' || optarg[0] == '+' || optarg[0] == '-')
                         throw std::runtime_error("Unrecognized window argument!\n\n");
                     window = (uint32_t)v;
+                    break;
+                }
+                case 'R': perm = optarg; break;
+                case 'B': {
+                    char *end = nullptr;
+                    errno = 0;
+                    const long long v = strtoll(optarg, &end, 10);
+                    if (end == optarg || *end || errno || v < 1 || v > 65535 || optarg[0] == ' ' || optarg[0] == '+')
+                        throw std::runtime_error("Unrecognized permutations argument!\n\n");
+                    n_perm = (uint32_t)v;
+                    break;
+                }
+                case 'e': {
+                    char *end = nullptr;
+                    errno = 0;
+                    const unsigned long long v = strtoull(optarg, &end, 10);
+                    if (end == optarg || *end || errno || optarg[0] == ' ' || optarg[0] == '+' || optarg[0] == '-')
+                        throw std::runtime_error("Unrecognized seed argument!\n\n");
+                    seed = v;
                     break;
                 }
                 case 'C': {
@@ -434,7 +459,7 @@ int junctions_cohort(int argc, char **argv) {
         for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
         if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
         if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
-        if (qtl != "NA" && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
+        if ((qtl != "NA" || perm != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
         for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
         for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
             throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
@@ -481,7 +506,8 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        const bool want_qtl = qtl != "NA", want_pheno = phenotypes != "NA" || components != "NA" || want_qtl;
+        const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_scan = want_qtl || want_perm;
+        const bool want_pheno = phenotypes != "NA" || components != "NA" || want_scan;
         if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
         rgx_pheno_table *ph = nullptr;
@@ -490,21 +516,29 @@ int junctions_cohort(int argc, char **argv) {
         rgx_pheno_pcs *pcs = nullptr;
         const uint32_t n_clip = ph && ph->n_rows >= 2 ? (uint32_t)std::min<uint64_t>({n_components, ph->n_rows, ph->n_samples}) : 0;
         const uint32_t n_pcs = components != "NA" ? n_clip : 0;
-        // -Q: the first n_cov components are the covariates -- those of -C further clipped to the samples less three -- of the same decomposition
-        const uint32_t n_cov = want_qtl && ph && ph->n_samples >= 3 ? std::min<uint32_t>(n_clip, ph->n_samples - 3) : 0;
+        // -Q and -R: the first n_cov components are the covariates -- those of -C further clipped to the samples less three -- of the same decomposition
+        const uint32_t n_cov = want_scan && ph && ph->n_samples >= 3 ? std::min<uint32_t>(n_clip, ph->n_samples - 3) : 0;
         if (ok && std::max(n_pcs, n_cov) && rgx_cohort_pheno_pcs(co, ph, std::max(n_pcs, n_cov), &pcs, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_genotypes *gt = nullptr;
-        if (ok && want_qtl && rgx_genotypes_load(genotypes.c_str(), m, &gt, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
+        if (ok && want_scan && rgx_genotypes_load(genotypes.c_str(), m, &gt, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         // a table without rows has no pairs: the file is its header line
         rgx_qtl_result *qr = nullptr;
-        if (ok && want_qtl && ph->n_rows) {
+        rgx_qtl_perm_result *pr = nullptr;
+        if (ok && want_scan && ph->n_rows) {
             std::vector<rgx_qtl_region> regions((size_t)ph->n_rows);
             int rc = rgx_cohort_pheno_regions(m, ph, regions.data(), err, sizeof err);
-            if (rc == RGX_OK) rc = rgx_cohort_qtl_nominal(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov, pcs ? pcs->component : nullptr,
-                                                          window, &qr, err, sizeof err);
+            if (rc == RGX_OK && want_qtl) rc = rgx_cohort_qtl_nominal(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
+                                                                      pcs ? pcs->component : nullptr, window, &qr, err, sizeof err);
+            if (rc == RGX_OK && want_perm) {
+                std::vector<uint16_t> perms(((size_t)n_perm + 1) * ph->n_samples);
+                rc = rgx_qtl_permutations(ph->n_samples, n_perm, seed, perms.data(), err, sizeof err);
+                if (rc == RGX_OK) rc = rgx_cohort_qtl_permute(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
+                                                              pcs ? pcs->component : nullptr, window, n_perm, perms.data(), &pr, err, sizeof err);
+            }
             if (rc != RGX_OK) { failure = err; ok = false; }
         }
         if (!ok) {
+            rgx_cohort_qtl_perm_free(pr);
             rgx_cohort_qtl_free(qr);
             rgx_genotypes_free(gt);
             rgx_cohort_pheno_pcs_free(pcs);
@@ -535,6 +569,10 @@ int junctions_cohort(int argc, char **argv) {
         if (want_qtl) {
             nt = rgx_cohort_format_qtl(m, cl, ph, qr, gt->pos, gt->id, nullptr, 0); ttx.reset(new char[nt + 1]);
             rgx_cohort_format_qtl(m, cl, ph, qr, gt->pos, gt->id, ttx.get(), nt); }
+        size_t nr = 0; std::unique_ptr<char[]> rtx;
+        if (want_perm) {
+            nr = rgx_cohort_format_qtl_perm(m, cl, ph, pr, gt->pos, gt->id, nullptr, 0); rtx.reset(new char[nr + 1]);
+            rgx_cohort_format_qtl_perm(m, cl, ph, pr, gt->pos, gt->id, rtx.get(), nr); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -564,6 +602,11 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + qtl + "\n\n");
             short_write |= fwrite(ttx.get(), 1, nt, g) != nt; short_write |= fclose(g) != 0;
         }
+        if (want_perm) {
+            FILE *g = fopen(perm.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + perm + "\n\n");
+            short_write |= fwrite(rtx.get(), 1, nr, g) != nr; short_write |= fclose(g) != 0;
+        }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
             fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
@@ -586,6 +629,15 @@ int junctions_cohort(int argc, char **argv) {
                     (unsigned long long)gt->n_unknown_contig, n_cov, (unsigned long long)(qr ? qr->n_pairs : 0), (unsigned long long)(qr ? qr->n_constant : 0),
                     (unsigned long long)(qr ? qr->n_explained : 0), (unsigned long long)(qr ? qr->n_flat_rows : 0), qr ? qr->ms_qtl : 0.0,
                     qr ? qr->ms_residual : 0.0, qr ? qr->ms_pairs : 0.0);
+        if (want_perm && getenv("REGTOOLS_AMD_STATS")) {
+            uint64_t n_lines = 0;
+            for (uint64_t k = 0; pr && k < pr->n_rows; ++k) n_lines += pr->n_cis[k] != 0;
+            fprintf(stderr, "[regtools_amd] perm: %u permutations from seed %llu, %u variants, %u covariates, %llu pairs, %llu rows written, %llu tiles, "
+                    "%.3f ms (residuals %.3f ms, products %.3f ms, beta %.3f ms)\n", n_perm, (unsigned long long)seed, gt->n_variants, n_cov,
+                    (unsigned long long)(pr ? pr->n_pairs : 0), (unsigned long long)n_lines, (unsigned long long)(pr ? pr->n_tiles : 0),
+                    pr ? pr->ms_perm : 0.0, pr ? pr->ms_residual : 0.0, pr ? pr->ms_products : 0.0, pr ? pr->ms_beta : 0.0);
+        }
+        rgx_cohort_qtl_perm_free(pr);
         rgx_cohort_qtl_free(qr);
         rgx_genotypes_free(gt);
         rgx_cohort_pheno_pcs_free(pcs);

@@ -89,6 +89,8 @@ struct rgx_cohort {
     // rgx_cohort_qtl_nominal (cohort_qtl.cpp): the uploaded inputs, the row-major residuals with the per-row and per-variant arrays, the
     // sample-major panels, the pairs
     DevBuf qt_in, qt_rows, qt_t, qt_out;
+    // rgx_cohort_qtl_permute (cohort_qtl_perm.cpp; the four above are shared with it): the sample-major permutations, perm_r with the best pairs
+    DevBuf qp_in, qp_out;
 };
 
 // cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the

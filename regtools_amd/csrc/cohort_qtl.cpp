@@ -2,12 +2,12 @@
 // rgx_cohort_qtl_nominal_host, the t and p functions, the text, and rgx_genotypes_load, which reads the dosages from a VCF or BCF (contract in
 // include/regtools_amd.h; the nominal pass of FastQTL and tensorQTL, which the reference does not contain).  Device side: qtl_kernels.hip;
 // arithmetic: qtl_core.h.
+//   QtlRun, the device stages, is declared in qtl_run.h, which the permutation pass (cohort_qtl_perm.cpp) shares.
 //   on the host, for the device path and the twin alike: the quantile table T and the orthonormal basis Q of intercept + covariates
 //   rank2, T, Q, regions, variants and dosages in HBM -> residuals Y, G row-major with yy, gg and the verdicts -> the usable variants compacted
 //   -> Yt, Gt sample-major -> per row its range of usable variants, per 64 rows the tiles -> ONE wait for P and the tile count
 //   -> one workgroup per tile: r, slope, pair_variant -> per row the best pair -> the copies back
-#include "cohort_internal.h"
-#include "qtl_core.h"
+#include "qtl_run.h"
 
 #include <cmath>
 
@@ -42,10 +42,16 @@ rgx_qtl_result *qtl_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, ui
     return q;
 }
 
-struct QtlArgs {
-    const rgx_pheno_table *ph; const rgx_qtl_region *regions; uint32_t V; const uint32_t *var_tid, *var_pos; const int8_t *dosage;
-    uint32_t n_cov; const double *cov; uint32_t window;
-};
+int too_many_pairs(uint64_t P, char *err, size_t errlen) {
+    return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: %llu pairs of a row and a variant; the sQTL scan takes at most 2^32 - 2^16\n", (unsigned long long)P);
+}
+
+void count_verdicts(rgx_qtl_result *q) {
+    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
+    for (uint64_t k = 0; k < q->n_rows; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], q->n_samples);
+}
+
+}  // namespace
 
 // the arguments the host can judge, the same for the device and the twin
 int check_qtl(const QtlArgs &a, char *err, size_t errlen) {
@@ -69,9 +75,6 @@ int bad_flags(const uint32_t *flag, uint64_t K, char *err, size_t errlen) {
     if (flag[kQtlFlagRank]) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the phenotype table holds a rank2 outside 2 .. %llu\n",
         (unsigned long long)(2 * K));
     return RGX_OK;
-}
-int too_many_pairs(uint64_t P, char *err, size_t errlen) {
-    return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: %llu pairs of a row and a variant; the sQTL scan takes at most 2^32 - 2^16\n", (unsigned long long)P);
 }
 
 // ---- the host part, shared by the device path and the twin ------------------------------------------------------------------------------------
@@ -117,171 +120,118 @@ double host_residual(double *x, uint32_t S, const double *Q, uint32_t C) {
     return host_dot64(x, x, S);
 }
 
-void count_verdicts(rgx_qtl_result *q) {
-    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
-    for (uint64_t k = 0; k < q->n_rows; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], q->n_samples);
+// steps (1)-(6) of the contract on the host (qtl_run.h)
+int qtl_host_prepare(const QtlArgs &a, QtlHost &h, char *err, size_t errlen) {
+    const rgx_pheno_table *ph = a.ph; const rgx_qtl_region *regions = a.regions; const uint32_t *var_tid = a.var_tid, *var_pos = a.var_pos;
+    const int8_t *dosage = a.dosage; const uint32_t window = a.window;
+    const uint64_t K = ph->n_rows; const uint32_t S = ph->n_samples, V = a.V, C = a.n_cov + 1;
+    std::vector<double> &T = h.T, &Q = h.Q, &Y = h.Y, &G = h.G, &yy = h.yy, &gg = h.gg; std::vector<uint8_t> &verdict = h.verdict;
+    std::vector<uint32_t> &u_var = h.u_var, &lo = h.lo, &cnt = h.cnt; std::vector<uint64_t> &u_key = h.u_key;
+    try {
+        pheno_quantile_table(K, T);
+        Y.resize((size_t)K * S); G.resize((size_t)V * S); yy.resize(K); gg.resize(V); verdict.resize(V); lo.resize(K); cnt.resize(K);
+    } catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the residuals of %llu rows and %u variants\n",
+        (unsigned long long)K, V); }
+    const int rc = qtl_basis(S, a.n_cov, a.cov, Q, err, errlen);
+    if (rc != RGX_OK) return rc;
+    h.t_res = now_ms();
+    uint32_t flag[2] = {0, 0};
+    for (uint64_t k = 0; k < K; ++k) {
+        double *x = Y.data() + k * S;
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint32_t r = ph->rank2[k * S + s];
+            if (!pca_rank_ok(r, K)) { flag[kQtlFlagRank] = 1; return bad_flags(flag, K, err, errlen); }
+            x[s] = T[r - 2];
+        }
+        yy[k] = host_residual(x, S, Q.data(), C);
+    }
+    for (uint32_t v = 0; v < V; ++v) {
+        const int8_t *row = dosage + (size_t)v * S; double *x = G.data() + (size_t)v * S;
+        uint32_t n = 0, sum = 0; int mn = 3, mx = -1;
+        for (uint32_t s = 0; s < S; ++s) {
+            const int8_t d = row[s];
+            if (!qtl_dosage_ok(d)) { flag[kQtlFlagDosage] = 1; return bad_flags(flag, K, err, errlen); }
+            if (d < 0) continue;
+            ++n; sum += (uint32_t)d; mn = std::min<int>(mn, d); mx = std::max<int>(mx, d);
+        }
+        if (!n || mn == mx) { gg[v] = 0.0; verdict[v] = 1; continue; }
+        const double mean = qtl_mean(sum, n);
+        for (uint32_t s = 0; s < S; ++s) x[s] = row[s] >= 0 ? (double)row[s] : mean;
+        gg[v] = host_residual(x, S, Q.data(), C);
+        verdict[v] = qtl_enough(gg[v], S) ? 0 : 2;
+        if (!verdict[v]) { u_var.push_back(v); u_key.push_back(qtl_key(var_tid[v], var_pos[v])); }
+    }
+    h.t_pairs = now_ms();
+    uint64_t &P = h.P; P = 0;
+    for (uint64_t k = 0; k < K; ++k) {
+        lo[k] = cnt[k] = 0;
+        if (!qtl_enough(yy[k], S)) continue;
+        const auto first = std::lower_bound(u_key.begin(), u_key.end(), qtl_key_first(regions[k].tid, regions[k].start, window));
+        const auto last = std::upper_bound(u_key.begin(), u_key.end(), qtl_key_last(regions[k].tid, regions[k].end, window));
+        if (last <= first) continue;
+        lo[k] = (uint32_t)(first - u_key.begin()); cnt[k] = (uint32_t)(last - first); P += cnt[k];
+    }
+    return RGX_OK;
 }
 
-// One device run, as the stages rgx_cohort_qtl_nominal is made of.  The caller holds the cohort's lock and has checked the arguments; every stage
-// enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
-struct QtlRun {
-    rgx_cohort *co; QtlArgs a; char *err; size_t errlen;
-    double t0, t_last; bool trace = false; hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // uploads begin, residuals done, products begin, best done
-    uint32_t K, S, V, C, n_blocks; size_t ldy, ldg;
-    uint64_t P = 0, n_tiles = 0;
-    std::vector<double> T, Q;
-    // uploads
-    const double *d_T = nullptr, *d_Q = nullptr; const uint32_t *rank2 = nullptr, *regions = nullptr, *var_tid = nullptr, *var_pos = nullptr;
-    const int8_t *dosage = nullptr;
-    // per row and per variant
-    double *Y = nullptr, *G = nullptr, *yy = nullptr, *gg = nullptr, *u_gg = nullptr; uint64_t *u_key = nullptr, *head = nullptr;
-    uint32_t *usable = nullptr, *place = nullptr, *u_var = nullptr, *lo = nullptr, *count = nullptr, *pair_begin = nullptr, *blk_lo = nullptr,
-             *tile_count = nullptr, *tile_begin = nullptr, *tmp = nullptr; uint8_t *verdict = nullptr;
-    double *Yt = nullptr, *Gt = nullptr;
-    double *r = nullptr, *slope = nullptr; uint32_t *pair_variant = nullptr, *best = nullptr;
-
-    QtlRun(rgx_cohort *co_, const QtlArgs &a_, char *err_, size_t errlen_)
-        : co(co_), a(a_), err(err_), errlen(errlen_), t0(now_ms()), t_last(t0), K((uint32_t)a_.ph->n_rows), S(a_.ph->n_samples), V(a_.V),
-          C(a_.n_cov + 1), n_blocks((K + kQtlTile - 1) / kQtlTile), ldy((size_t)n_blocks * kQtlTile),
-          ldg(((size_t)a_.V + kQtlTile - 1) / kQtlTile * kQtlTile + kQtlTile) {}
-    ~QtlRun() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    void mark(const char *what) {
-        if (!trace) return;
-        (void)hipStreamSynchronize(st);
-        const double t = now_ms();
-        fprintf(stderr, "[rgx trace] qtl nominal: %-28s +%8.3f ms\n", what, t - t_last); t_last = t;
-    }
-    uint32_t *flag() const { return (uint32_t *)(head + 2); }                 // head: P, the tile count, the two flag words, the usable variants
-    uint32_t *n_usable() const { return (uint32_t *)(head + 3); }
-
-    // 1. the quantile table and the basis (host), then the inputs in HBM and the workspaces
-    int open() {
-        HIP_ENTER(co->device);
-        st = co->stream;
-        trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
-        try { pheno_quantile_table(K, T); }
-        catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the %llu quantiles\n", (unsigned long long)(2ull * K - 1)); }
-        int rc = qtl_basis(S, a.n_cov, a.cov, Q, err, errlen);
-        if (rc != RGX_OK) return rc;
-        mark("quantile table + basis");
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        const size_t n_T = 2 * (size_t)K - 1, n_Q = (size_t)C * S, n_ks = (size_t)K * S, n_vs = (size_t)V * S;
-        if (co->qt_in.ensure((n_T + n_Q) * 8 + (n_ks + 3 * (size_t)K + 2 * (size_t)V) * 4 + n_vs + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for a table of %u rows, %u variants and %u samples\n", K, V, S); }
-        Carve u(co->qt_in);
-        double *t_up = u.take<double>(n_T), *q_up = u.take<double>(n_Q);
-        uint32_t *r_up = u.u32(n_ks), *g_up = u.u32(3 * (size_t)K), *vt_up = u.u32(V), *vp_up = u.u32(V); int8_t *d_up = u.take<int8_t>(n_vs);
-        CARVE_TRY(u, "sQTL input");
-        const size_t n_scan = std::max<size_t>(std::max<size_t>((size_t)K + 1, V), (size_t)n_blocks + 1);
-        if (co->qt_rows.ensure((n_ks + n_vs + K + 2 * (size_t)V) * 8 + (size_t)V * 8 + 32 +
-                               (3 * (size_t)V + 3 * (size_t)K + 2 + 3 * (size_t)n_blocks + 2 + scan_tmp_words((uint32_t)n_scan)) * 4 + V + 256) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for the residuals of %u rows and %u variants\n", K, V); }
-        Carve w(co->qt_rows);
-        Y = w.take<double>(n_ks); G = w.take<double>(n_vs); yy = w.take<double>(K); gg = w.take<double>(V); u_gg = w.take<double>(V);
-        u_key = w.u64(V); head = w.u64(4);
-        usable = w.u32(V); place = w.u32(V); u_var = w.u32(V); lo = w.u32(K); count = w.u32((size_t)K + 1); pair_begin = w.u32((size_t)K + 1);
-        blk_lo = w.u32(n_blocks); tile_count = w.u32((size_t)n_blocks + 1); tile_begin = w.u32((size_t)n_blocks + 1);
-        tmp = w.u32(scan_tmp_words((uint32_t)n_scan)); verdict = w.u8(V);
-        CARVE_TRY(w, "sQTL row");
-        if (co->qt_t.ensure((size_t)S * (ldy + ldg) * 8 + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for the sample-major residuals of %u rows and %u variants\n", K, V); }
-        Carve t(co->qt_t);
-        Yt = t.take<double>((size_t)S * ldy); Gt = t.take<double>((size_t)S * ldg);
-        CARVE_TRY(t, "sQTL panel");
-        HIP_TRY(hipEventRecord(ev[0], st));
-        HIP_TRY(hipMemcpyAsync(r_up, a.ph->rank2, n_ks * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t_up, T.data(), n_T * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(q_up, Q.data(), n_Q * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(g_up, a.regions, (size_t)K * 12, hipMemcpyHostToDevice, st));
-        if (V) {
-            HIP_TRY(hipMemcpyAsync(vt_up, a.var_tid, (size_t)V * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(vp_up, a.var_pos, (size_t)V * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_up, a.dosage, n_vs, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipMemsetAsync(head, 0, 32, st));
-        d_T = t_up; d_Q = q_up; rank2 = r_up; regions = g_up; var_tid = vt_up; var_pos = vp_up; dosage = d_up;
-        mark("inputs in HBM");
-        return RGX_OK;
-    }
-    // 2. a wave per row and per variant
-    int residuals() {
-        launch_qtl_residual_pheno(rank2, d_T, K, S, d_Q, C, Y, yy, flag(), st);
-        launch_qtl_residual_geno(dosage, V, S, d_Q, C, G, gg, verdict, usable, flag(), st);
-        mark("residuals");
-        return RGX_OK;
-    }
-    // 3. the usable variants side by side; both sides sample-major
-    int compact() {
-        launch_scan_u32(usable, place, V, n_usable(), tmp, st);
-        launch_qtl_compact(usable, place, V, var_tid, var_pos, gg, u_var, u_key, u_gg, st);
-        launch_qtl_transpose(Y, nullptr, nullptr, K, S, ldy, Yt, st);
-        launch_qtl_transpose(G, u_var, n_usable(), 0, S, ldg, Gt, st);
-        HIP_TRY(hipEventRecord(ev[1], st));
-        mark("compaction + transposes");
-        return RGX_OK;
-    }
-    // 4. the rows' ranges and the tiles; the call's one wait in front of its results: P, the tile count, the flags
-    int plan() {
-        launch_qtl_plan(regions, K, S, yy, u_key, n_usable(), a.window, lo, count, blk_lo, tile_count, (unsigned long long *)head, st);
-        launch_scan_u32(count, pair_begin, K + 1, nullptr, tmp, st);
-        launch_scan_u32(tile_count, tile_begin, n_blocks + 1, nullptr, tmp, st);
-        uint64_t h[4];
-        HIP_TRY(hipMemcpyAsync(h, head, 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        mark("plan");
-        const uint32_t *f = (const uint32_t *)(h + 2);
-        const int rc = bad_flags(f, K, err, errlen);
-        if (rc != RGX_OK) return rc;
-        P = h[0]; n_tiles = h[1];
-        if (P > kQtlMaxPairs) return too_many_pairs(P, err, errlen);
-        if (n_tiles > kQtlMaxTiles) return fail(err, errlen, RGX_ERR_ARG,
-            "regtools_amd: %llu tiles of 64 rows and 64 variants; the sQTL scan takes at most 2^31 - 1 (rows far out of position order)\n",
-            (unsigned long long)n_tiles);
-        if (co->qt_out.ensure((size_t)P * 20 + (size_t)K * 4 + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %llu pairs\n", (unsigned long long)P); }
-        Carve o(co->qt_out);
-        r = o.take<double>(P); slope = o.take<double>(P); pair_variant = o.u32(P); best = o.u32(K);
-        CARVE_TRY(o, "sQTL pair");
-        return RGX_OK;
-    }
-    // 5. one workgroup per tile, then a wave per row
-    int pairs() {
-        HIP_TRY(hipEventRecord(ev[2], st));
-        launch_qtl_pairs(Yt, ldy, Gt, ldg, S, K, (uint32_t)n_tiles, tile_begin, blk_lo, lo, count, pair_begin, yy, u_gg, u_var, r, slope, pair_variant, st);
-        mark("pair products");
-        launch_qtl_best(r, pair_begin, K, best, st);
-        HIP_TRY(hipEventRecord(ev[3], st));
-        mark("best pairs");
-        return RGX_OK;
-    }
-    // 6. the copies back, one wait
-    int finish(rgx_qtl_result **out) {
-        rgx_qtl_result *q = qtl_alloc(K, S, V, a.n_cov, P, /*pinned=*/true);
-        if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result of %llu pairs\n",
-            (unsigned long long)P); }
-        hipError_t e_ = hipMemcpyAsync(q->yy, yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-        auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
-        copy(q->gg, gg, (size_t)V * 8); copy(q->variant_verdict, verdict, V); copy(q->pair_begin, pair_begin, ((size_t)K + 1) * 4);
-        copy(q->r, r, (size_t)P * 8); copy(q->slope, slope, (size_t)P * 8); copy(q->pair_variant, pair_variant, (size_t)P * 4);
-        copy(q->best, best, (size_t)K * 4);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
-        float ms_res = 0, ms_pr = 0;
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, ev[0], ev[1]);
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, ev[2], ev[3]);
-        if (e_ != hipSuccess) { rgx_cohort_qtl_free(q); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the sQTL scan\n", hipGetErrorString(e_)); }
-        mark("copies");
-        count_verdicts(q);
-        q->n_tiles = n_tiles;
-        q->ms_residual = ms_res; q->ms_pairs = ms_pr; q->ms_qtl = now_ms() - t0;
-        *out = q;
-        return RGX_OK;
-    }
-};
-
-}  // namespace
+// ---- the nominal scan's own stages of QtlRun (the shared ones: qtl_run.h) ---------------------------------------------------------------------
+// 4. the rows' ranges and the tiles; the call's one wait in front of its results: P, the tile count, the flags
+int QtlRun::plan() {
+    plan_launch();
+    launch_scan_u32(count, pair_begin, K + 1, nullptr, tmp, st);
+    launch_scan_u32(tile_count, tile_begin, n_blocks + 1, nullptr, tmp, st);
+    uint64_t h[4];
+    HIP_TRY(hipMemcpyAsync(h, head, 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    mark("plan");
+    const uint32_t *f = (const uint32_t *)(h + 2);
+    const int rc = bad_flags(f, K, err, errlen);
+    if (rc != RGX_OK) return rc;
+    P = h[0]; n_tiles = h[1];
+    if (P > kQtlMaxPairs) return too_many_pairs(P, err, errlen);
+    if (n_tiles > kQtlMaxTiles) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: %llu tiles of 64 rows and 64 variants; the sQTL scan takes at most 2^31 - 1 (rows far out of position order)\n",
+        (unsigned long long)n_tiles);
+    if (co->qt_out.ensure((size_t)P * 20 + (size_t)K * 4 + 256) != hipSuccess) { (void)hipGetLastError();
+        return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %llu pairs\n", (unsigned long long)P); }
+    Carve o(co->qt_out);
+    r = o.take<double>(P); slope = o.take<double>(P); pair_variant = o.u32(P); best = o.u32(K);
+    CARVE_TRY(o, "sQTL pair");
+    return RGX_OK;
+}
+// 5. one workgroup per tile, then a wave per row
+int QtlRun::pairs() {
+    HIP_TRY(hipEventRecord(ev[2], st));
+    launch_qtl_pairs(Yt, ldy, Gt, ldg, S, K, (uint32_t)n_tiles, tile_begin, blk_lo, lo, count, pair_begin, yy, u_gg, u_var, r, slope, pair_variant, st);
+    mark("pair products");
+    launch_qtl_best(r, pair_begin, K, best, st);
+    HIP_TRY(hipEventRecord(ev[3], st));
+    mark("best pairs");
+    return RGX_OK;
+}
+// 6. the copies back, one wait
+int QtlRun::finish(rgx_qtl_result **out) {
+    rgx_qtl_result *q = qtl_alloc(K, S, V, a.n_cov, P, /*pinned=*/true);
+    if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result of %llu pairs\n",
+        (unsigned long long)P); }
+    hipError_t e_ = hipMemcpyAsync(q->yy, yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
+    auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+    copy(q->gg, gg, (size_t)V * 8); copy(q->variant_verdict, verdict, V); copy(q->pair_begin, pair_begin, ((size_t)K + 1) * 4);
+    copy(q->r, r, (size_t)P * 8); copy(q->slope, slope, (size_t)P * 8); copy(q->pair_variant, pair_variant, (size_t)P * 4);
+    copy(q->best, best, (size_t)K * 4);
+    if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
+    if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+    float ms_res = 0, ms_pr = 0;
+    if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, ev[0], ev[1]);
+    if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, ev[2], ev[3]);
+    if (e_ != hipSuccess) { rgx_cohort_qtl_free(q); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the sQTL scan\n", hipGetErrorString(e_)); }
+    mark("copies");
+    count_verdicts(q);
+    q->n_tiles = n_tiles;
+    q->ms_residual = ms_res; q->ms_pairs = ms_pr; q->ms_qtl = now_ms() - t0;
+    *out = q;
+    return RGX_OK;
+}
 
 extern "C" void rgx_cohort_qtl_free(rgx_qtl_result *q) {
     if (!q) return;
@@ -330,52 +280,12 @@ extern "C" int rgx_cohort_qtl_nominal_host(const rgx_pheno_table *ph, const rgx_
     const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
     int rc = check_qtl(a, err, errlen);
     if (rc != RGX_OK) return rc;
-    const uint64_t K = ph->n_rows; const uint32_t S = ph->n_samples, V = n_variants, C = n_cov + 1;
-    std::vector<double> T, Q, Y, G, yy, gg; std::vector<uint8_t> verdict; std::vector<uint32_t> u_var, lo, cnt; std::vector<uint64_t> u_key;
-    try {
-        pheno_quantile_table(K, T);
-        Y.resize((size_t)K * S); G.resize((size_t)V * S); yy.resize(K); gg.resize(V); verdict.resize(V); lo.resize(K); cnt.resize(K);
-    } catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the residuals of %llu rows and %u variants\n",
-        (unsigned long long)K, V); }
-    rc = qtl_basis(S, n_cov, covariates, Q, err, errlen);
+    QtlHost h;
+    rc = qtl_host_prepare(a, h, err, errlen);
     if (rc != RGX_OK) return rc;
-    const double t_res = now_ms();
-    uint32_t flag[2] = {0, 0};
-    for (uint64_t k = 0; k < K; ++k) {
-        double *x = Y.data() + k * S;
-        for (uint32_t s = 0; s < S; ++s) {
-            const uint32_t r = ph->rank2[k * S + s];
-            if (!pca_rank_ok(r, K)) { flag[kQtlFlagRank] = 1; return bad_flags(flag, K, err, errlen); }
-            x[s] = T[r - 2];
-        }
-        yy[k] = host_residual(x, S, Q.data(), C);
-    }
-    for (uint32_t v = 0; v < V; ++v) {
-        const int8_t *row = dosage + (size_t)v * S; double *x = G.data() + (size_t)v * S;
-        uint32_t n = 0, sum = 0; int mn = 3, mx = -1;
-        for (uint32_t s = 0; s < S; ++s) {
-            const int8_t d = row[s];
-            if (!qtl_dosage_ok(d)) { flag[kQtlFlagDosage] = 1; return bad_flags(flag, K, err, errlen); }
-            if (d < 0) continue;
-            ++n; sum += (uint32_t)d; mn = std::min<int>(mn, d); mx = std::max<int>(mx, d);
-        }
-        if (!n || mn == mx) { gg[v] = 0.0; verdict[v] = 1; continue; }
-        const double mean = qtl_mean(sum, n);
-        for (uint32_t s = 0; s < S; ++s) x[s] = row[s] >= 0 ? (double)row[s] : mean;
-        gg[v] = host_residual(x, S, Q.data(), C);
-        verdict[v] = qtl_enough(gg[v], S) ? 0 : 2;
-        if (!verdict[v]) { u_var.push_back(v); u_key.push_back(qtl_key(var_tid[v], var_pos[v])); }
-    }
-    const double t_pairs = now_ms();
-    uint64_t P = 0;
-    for (uint64_t k = 0; k < K; ++k) {
-        lo[k] = cnt[k] = 0;
-        if (!qtl_enough(yy[k], S)) continue;
-        const auto first = std::lower_bound(u_key.begin(), u_key.end(), qtl_key_first(regions[k].tid, regions[k].start, window));
-        const auto last = std::upper_bound(u_key.begin(), u_key.end(), qtl_key_last(regions[k].tid, regions[k].end, window));
-        if (last <= first) continue;
-        lo[k] = (uint32_t)(first - u_key.begin()); cnt[k] = (uint32_t)(last - first); P += cnt[k];
-    }
+    const uint64_t K = ph->n_rows, P = h.P; const uint32_t S = ph->n_samples, V = n_variants;
+    const std::vector<double> &Y = h.Y, &G = h.G, &yy = h.yy, &gg = h.gg; const std::vector<uint8_t> &verdict = h.verdict;
+    const std::vector<uint32_t> &u_var = h.u_var, &lo = h.lo, &cnt = h.cnt;
     if (P > kQtlMaxPairs) return too_many_pairs(P, err, errlen);
     rgx_qtl_result *q = qtl_alloc(K, S, V, n_cov, P, false);
     if (!q) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the result of %llu pairs\n", (unsigned long long)P);
@@ -398,7 +308,7 @@ extern "C" int rgx_cohort_qtl_nominal_host(const rgx_pheno_table *ph, const rgx_
     q->pair_begin[K] = p;
     count_verdicts(q);
     const double t1 = now_ms();
-    q->ms_residual = t_pairs - t_res; q->ms_pairs = t1 - t_pairs; q->ms_qtl = t1 - t0;
+    q->ms_residual = h.t_pairs - h.t_res; q->ms_pairs = t1 - h.t_pairs; q->ms_qtl = t1 - t0;
     *out = q;
     return RGX_OK;
 }
@@ -411,9 +321,8 @@ extern "C" double rgx_qtl_tstat(double r, uint32_t dof) {
     return r * sqrt((double)dof / u);
 }
 
-namespace {
 // the continued fraction of the incomplete beta function (Lentz's method, modified: Thompson and Barnett 1986), in the widest type the host has
-long double beta_cf(long double a, long double b, long double x) {
+long double qtl_beta_cf(long double a, long double b, long double x) {
     const long double tiny = 1e-300L, eps = 1e-19L;
     long double c = 1.0L, d = 1.0L - (a + b) * x / (a + 1.0L);
     if (fabsl(d) < tiny) d = tiny;
@@ -435,6 +344,7 @@ long double beta_cf(long double a, long double b, long double x) {
     }
     return h;
 }
+namespace {
 // Gamma(n / 2 + 1 / 2) / (Gamma(n / 2) Gamma(1 / 2)) = 1 / B(n / 2, 1 / 2), by the recurrence over n - 2 from n = 1 (1 / pi) or n = 2 (1 / 2)
 long double inv_beta_half(uint32_t n) {
     long double v = n % 2 ? 1.0L / 3.14159265358979323846264338327950288L : 0.5L;
@@ -452,8 +362,8 @@ extern "C" double rgx_qtl_pvalue(double t, uint32_t dof) {
     // x^a y^b / B(a, b), with log x = -log1p(t^2 / n)
     const long double front = expl(-a * log1pl(t2 / n)) * sqrtl(y) * inv_beta_half(dof);
     long double p;
-    if (x < (a + 1.0L) / (a + b + 2.0L)) p = front * beta_cf(a, b, x) / a;
-    else p = 1.0L - front * beta_cf(b, a, y) / b;
+    if (x < (a + 1.0L) / (a + b + 2.0L)) p = front * qtl_beta_cf(a, b, x) / a;
+    else p = 1.0L - front * qtl_beta_cf(b, a, y) / b;
     return (double)(p < 0.0L ? 0.0L : p > 1.0L ? 1.0L : p);
 }
 

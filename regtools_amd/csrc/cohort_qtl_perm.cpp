@@ -1,0 +1,403 @@
+// cohort_qtl_perm.cpp -- the permutation pass of the cohort's cis-sQTL scan: rgx_cohort_qtl_permute (device), its host twin
+// rgx_cohort_qtl_permute_host, rgx_qtl_permutations, the digamma, trigamma and incomplete beta functions, the beta fit and the text (contract in
+// include/regtools_amd.h; FastQTL's --permute and tensorQTL's map_cis, which the reference does not contain).  Device side: qtl_perm_kernels.hip
+// behind QtlRun's shared stages (qtl_run.h); arithmetic: qtl_core.h.
+//   QtlRun: inputs in HBM -> residuals Y, G with yy, gg and the verdicts -> the usable variants compacted -> Gt sample-major -> per row its range
+//   -> the permutations sample-major in HBM -> one workgroup per (row, 64 permutations): perm_r -> a thread per row: the best pair of permutation 0
+//   -> ONE wait, the copies back -> on the host: n_ge, p_perm, the beta approximation
+#include "qtl_run.h"
+
+#include <cfloat>
+#include <cmath>
+
+namespace {
+
+// One block, every array 16-byte aligned.
+struct PermLayout { size_t yy, gg, perm_r, best_r, best_slope, p_perm, shape1, shape2, p_beta, n_cis, best_variant, n_ge, verdict, status, bytes; };
+PermLayout perm_layout(uint64_t K, uint32_t V, uint32_t B) {
+    PermLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    L.yy = take((size_t)K * 8); L.gg = take((size_t)V * 8); L.perm_r = take((size_t)K * ((size_t)B + 1) * 8);
+    L.best_r = take((size_t)K * 8); L.best_slope = take((size_t)K * 8); L.p_perm = take((size_t)K * 8); L.shape1 = take((size_t)K * 8);
+    L.shape2 = take((size_t)K * 8); L.p_beta = take((size_t)K * 8);
+    L.n_cis = take((size_t)K * 4); L.best_variant = take((size_t)K * 4); L.n_ge = take((size_t)K * 4); L.verdict = take((size_t)V);
+    L.status = take((size_t)K);
+    L.bytes = o + 16;
+    return L;
+}
+struct PermBox { rgx_qtl_perm_result q; void *block; size_t block_cap; bool pinned; };
+
+rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, uint32_t B, bool pinned) {
+    PermBox *box = (PermBox *)calloc(1, sizeof *box);
+    if (!box) return nullptr;
+    const PermLayout L = perm_layout(K, V, B);
+    box->pinned = pinned;
+    box->block = block_take(L.bytes, box->block_cap, pinned);
+    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
+    if (!box->block) { free(box); return nullptr; }
+    uint8_t *b = (uint8_t *)box->block;
+    rgx_qtl_perm_result *q = &box->q;
+    q->n_rows = K; q->n_samples = S; q->n_variants = V; q->n_cov = n_cov; q->dof = S - n_cov - 2; q->n_perm = B;
+    q->yy = (double *)(b + L.yy); q->gg = (double *)(b + L.gg); q->perm_r = (double *)(b + L.perm_r); q->best_r = (double *)(b + L.best_r);
+    q->best_slope = (double *)(b + L.best_slope); q->p_perm = (double *)(b + L.p_perm); q->beta_shape1 = (double *)(b + L.shape1);
+    q->beta_shape2 = (double *)(b + L.shape2); q->p_beta = (double *)(b + L.p_beta);
+    q->n_cis = (uint32_t *)(b + L.n_cis); q->best_variant = (uint32_t *)(b + L.best_variant); q->n_ge = (uint32_t *)(b + L.n_ge);
+    q->variant_verdict = b + L.verdict; q->beta_status = b + L.status;
+    return q;
+}
+
+// what the host can judge of the permutations, the same for the device and the twin
+int check_perm(uint64_t K, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen) {
+    if (!B || B > 65535u) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the permutation pass takes 1 to 65535 permutations; %u were asked for\n", B);
+    if (!perm) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the permutation pass needs its permutations\n");
+    if (K * ((uint64_t)B + 1) > kQtlMaxPairs) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: %llu rows x %u permutations and the identity; the permutation pass takes at most 2^32 - 2^16 of them\n", (unsigned long long)K, B);
+    for (uint32_t s = 0; s < S; ++s) if (perm[s] != s) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: row 0 of the permutations is not the identity (sample %u stands at %u)\n", (uint32_t)perm[s], s);
+    std::vector<uint8_t> seen(S);
+    for (uint32_t b = 1; b <= B; ++b) {
+        std::fill(seen.begin(), seen.end(), 0);
+        const uint16_t *row = perm + (size_t)b * S;
+        for (uint32_t s = 0; s < S; ++s) {
+            if (row[s] >= S || seen[row[s]]) return fail(err, errlen, RGX_ERR_ARG,
+                "regtools_amd: row %u of the permutations is no permutation of 0 .. %u (index %u at %u)\n", b, S - 1, (uint32_t)row[s], s);
+            seen[row[s]] = 1;
+        }
+    }
+    return RGX_OK;
+}
+
+size_t host_threads() { return std::min<size_t>(16, std::max<size_t>(1, std::thread::hardware_concurrency())); }
+
+long double digamma_l(long double x) {
+    long double acc = 0.0L;
+    for (; x < 32.0L; x += 1.0L) acc -= 1.0L / x;
+    const long double i2 = 1.0L / (x * x);
+    // sum B_2n / (2n x^2n), n = 1 .. 8
+    const long double series = i2 * (1.0L / 12 - i2 * (1.0L / 120 - i2 * (1.0L / 252 - i2 * (1.0L / 240 - i2 * (1.0L / 132 - i2 * (691.0L / 32760 -
+                               i2 * (1.0L / 12 - i2 * (3617.0L / 8160))))))));
+    return acc + logl(x) - 0.5L / x - series;
+}
+long double trigamma_l(long double x) {
+    long double acc = 0.0L;
+    for (; x < 32.0L; x += 1.0L) acc += 1.0L / (x * x);
+    const long double i2 = 1.0L / (x * x);
+    // sum B_2n / x^(2n + 1), n = 1 .. 8
+    const long double series = i2 * (1.0L / 6 - i2 * (1.0L / 30 - i2 * (1.0L / 42 - i2 * (1.0L / 30 - i2 * (5.0L / 66 - i2 * (691.0L / 2730 -
+                               i2 * (7.0L / 6 - i2 * (3617.0L / 510))))))));
+    return acc + 1.0L / x + 0.5L * i2 + series / x;
+}
+long double betainc_l(long double x, long double a, long double b) {
+    if (x <= 0.0L) return 0.0L;
+    if (x >= 1.0L) return 1.0L;
+    const long double y = 1.0L - x;                                     // (exact: x is a double)
+    const long double front = expl(a * logl(x) + b * log1pl(-x) - lgammal(a) - lgammal(b) + lgammal(a + b));
+    long double p;
+    if (x < (a + 1.0L) / (a + b + 2.0L)) p = front * qtl_beta_cf(a, b, x) / a;
+    else p = 1.0L - front * qtl_beta_cf(b, a, y) / b;
+    return p < 0.0L ? 0.0L : p > 1.0L ? 1.0L : p;
+}
+
+int beta_fit_l(const double *p, uint32_t n, long double &a, long double &b) {
+    a = b = NAN;
+    if (n < 2) return 2;
+    long double sum = 0.0L, l1 = 0.0L, l2 = 0.0L;
+    for (uint32_t i = 0; i < n; ++i) { sum += p[i]; l1 += logl((long double)p[i]); l2 += log1pl(-(long double)p[i]); }
+    const long double m = sum / n;
+    long double ss = 0.0L;
+    for (uint32_t i = 0; i < n; ++i) { const long double d = (long double)p[i] - m; ss += d * d; }
+    const long double v = ss / n;
+    if (!(v > 0.0L)) return 2;
+    const long double a0 = m * (m * (1.0L - m) / v - 1.0L), b0 = a0 * (1.0L / m - 1.0L);
+    if (!(a0 > 0.0L) || !(b0 > 0.0L) || std::isinf(a0) || std::isinf(b0)) return 2;
+    l1 /= n; l2 /= n;
+    a = a0; b = b0;
+    for (int step = 0; step < 100; ++step) {
+        const long double pab = digamma_l(a + b), tab = trigamma_l(a + b);
+        const long double g1 = digamma_l(a) - pab - l1, g2 = digamma_l(b) - pab - l2;
+        const long double j11 = trigamma_l(a) - tab, j22 = trigamma_l(b) - tab, j12 = -tab;
+        const long double det = j11 * j22 - j12 * j12;
+        long double da = -(j22 * g1 - j12 * g2) / det, db = -(j11 * g2 - j12 * g1) / det;
+        if (da != da || db != db || std::isinf(da) || std::isinf(db)) break;
+        for (int h = 0; h < 200 && (!(a + da > 0.0L) || !(b + db > 0.0L)); ++h) { da *= 0.5L; db *= 0.5L; }
+        if (!(a + da > 0.0L) || !(b + db > 0.0L)) break;
+        const bool done = fabsl(da) < 1e-12L * a && fabsl(db) < 1e-12L * b;
+        a += da; b += db;
+        if (done) return 0;
+    }
+    a = a0; b = b0;
+    return 1;
+}
+
+// n_ge, p_perm, the verdict counts and the tile count of a result whose arrays from steps (1)-(6) and perm_r, best_* are in place; then the beta
+// approximation, rows shared among the host's threads (a row is one task: its sums do not depend on who runs it)
+int perm_finish(rgx_qtl_perm_result *q, bool device, char *err, size_t errlen) {
+    const uint64_t K = q->n_rows; const uint32_t B = q->n_perm, S = q->n_samples, dof = q->dof;
+    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
+    const uint64_t p_tiles = ((uint64_t)B + 1 + kQtlTile - 1) / kQtlTile;
+    for (uint64_t k = 0; k < K; ++k) {
+        q->n_flat_rows += !qtl_enough(q->yy[k], S);
+        if (device) q->n_tiles += p_tiles * (((uint64_t)q->n_cis[k] + kQtlTile - 1) / kQtlTile);
+    }
+    const double t0 = now_ms();
+    try {
+        WorkerPool pool(K * B < 4096 ? 1 : host_threads());
+        const uint64_t chunk = 16, n_tasks = (K + chunk - 1) / chunk;
+        pool.run((size_t)n_tasks, [&](size_t task) {
+            std::vector<double> p(B);
+            for (uint64_t k = task * chunk; k < K && k < (task + 1) * chunk; ++k) {
+                const double *row = q->perm_r + k * ((size_t)B + 1);
+                const uint64_t top = qtl_abs_bits(row[0]);
+                uint32_t n_ge = 0;
+                for (uint32_t b = 1; b <= B; ++b) n_ge += qtl_abs_bits(row[b]) >= top;
+                q->n_ge[k] = n_ge;
+                q->p_perm[k] = (double)(n_ge + 1) / (double)(B + 1);
+                q->beta_shape1[k] = q->beta_shape2[k] = q->p_beta[k] = NAN; q->beta_status[k] = 2;
+                if (!q->n_cis[k]) continue;
+                for (uint32_t b = 1; b <= B; ++b) {
+                    const double pb = rgx_qtl_pvalue(rgx_qtl_tstat(row[b], dof), dof);
+                    p[b - 1] = pb < DBL_MIN ? DBL_MIN : pb > 1.0 - 0x1p-53 ? 1.0 - 0x1p-53 : pb;
+                }
+                long double a, b2;
+                q->beta_status[k] = (uint8_t)beta_fit_l(p.data(), B, a, b2);
+                if (q->beta_status[k] == 2) continue;
+                q->beta_shape1[k] = (double)a; q->beta_shape2[k] = (double)b2;
+                const double x = rgx_qtl_pvalue(rgx_qtl_tstat(q->best_r[k], dof), dof);
+                q->p_beta[k] = (double)betainc_l(x, q->beta_shape1[k], q->beta_shape2[k]);
+            }
+        });
+    } catch (const std::exception &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory or threads for the beta approximation\n"); }
+    q->ms_beta = now_ms() - t0;
+    return RGX_OK;
+}
+
+// The device run: QtlRun's shared stages with the permutation stage behind them.
+struct PermRun {
+    QtlRun run; uint32_t B; const uint16_t *perm; size_t ldp;
+    std::vector<uint16_t> permT;
+    uint16_t *d_permT = nullptr; double *perm_r = nullptr, *best_r = nullptr, *best_slope = nullptr; uint32_t *best_u = nullptr, *best_variant = nullptr;
+
+    PermRun(rgx_cohort *co, const QtlArgs &a, uint32_t B_, const uint16_t *perm_, char *err, size_t errlen)
+        : run(co, a, err, errlen), B(B_), perm(perm_), ldp(((size_t)B_ + 1 + kQtlTile - 1) / kQtlTile * kQtlTile) { run.best_only = true; }
+
+    // 5. the permutations sample-major in HBM, the products, the best pairs
+    int products() {
+        rgx_cohort *co = run.co; char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
+        const uint32_t K = run.K, S = run.S;
+        if ((uint64_t)K * (ldp / kQtlTile) > 0x7fffffffull) return fail(err, errlen, RGX_ERR_ARG,
+            "regtools_amd: %u rows x %zu blocks of 64 permutations are more than 2^31 - 1 workgroups\n", K, ldp / kQtlTile);
+        try { permT.assign((size_t)S * ldp, 0); }
+        catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for %u permutations of %u samples\n", B, S); }
+        for (uint32_t b = 0; b <= B; ++b) for (uint32_t s = 0; s < S; ++s) permT[(size_t)s * ldp + b] = perm[(size_t)b * S + s];
+        const size_t n_out = (size_t)K * ((size_t)B + 1);
+        if (co->qp_in.ensure(permT.size() * 2 + 256) != hipSuccess || co->qp_out.ensure(n_out * 8 + (size_t)K * 24 + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %u permutations of %u rows\n", B, K); }
+        Carve in(co->qp_in);
+        d_permT = in.take<uint16_t>(permT.size());
+        CARVE_TRY(in, "sQTL permutation");
+        Carve o(co->qp_out);
+        perm_r = o.take<double>(n_out); best_r = o.take<double>(K); best_slope = o.take<double>(K); best_u = o.u32(K); best_variant = o.u32(K);
+        CARVE_TRY(o, "sQTL permutation result");
+        HIP_TRY(hipMemcpyAsync(d_permT, permT.data(), permT.size() * 2, hipMemcpyHostToDevice, st));
+        run.mark("permutations in HBM");
+        HIP_TRY(hipEventRecord(run.ev[2], st));
+        launch_qtl_perm(run.Y, K, S, d_permT, ldp, B + 1, run.Gt, run.ldg, run.lo, run.count, run.yy, run.u_gg, perm_r, best_u, st);
+        run.mark("permuted products");
+        launch_qtl_perm_best(run.Y, run.G, K, S, best_u, run.u_var, run.yy, run.gg, best_variant, best_r, best_slope, st);
+        HIP_TRY(hipEventRecord(run.ev[3], st));
+        run.mark("best pairs");
+        return RGX_OK;
+    }
+    // 6. the copies back behind the call's one wait, then the host's part
+    int finish(rgx_qtl_perm_result **out) {
+        char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
+        const uint32_t K = run.K, V = run.V;
+        rgx_qtl_perm_result *q = perm_alloc(K, run.S, V, run.a.n_cov, B, /*pinned=*/true);
+        if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE,
+            "regtools_amd: no memory for the result of %u rows and %u permutations\n", K, B); }
+        uint64_t h[4] = {0, 0, 0, 0};
+        hipError_t e_ = hipMemcpyAsync(q->yy, run.yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
+        auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+        copy(q->gg, run.gg, (size_t)V * 8); copy(q->variant_verdict, run.verdict, V); copy(q->n_cis, run.count, (size_t)K * 4);
+        copy(q->perm_r, perm_r, (size_t)K * ((size_t)B + 1) * 8); copy(q->best_r, best_r, (size_t)K * 8); copy(q->best_slope, best_slope, (size_t)K * 8);
+        copy(q->best_variant, best_variant, (size_t)K * 4); copy(h, run.head, 32);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
+        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+        float ms_res = 0, ms_pr = 0;
+        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, run.ev[0], run.ev[1]);
+        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, run.ev[2], run.ev[3]);
+        if (e_ != hipSuccess) { rgx_cohort_qtl_perm_free(q); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the sQTL permutation pass\n",
+            hipGetErrorString(e_)); }
+        run.mark("copies");
+        int rc = bad_flags((const uint32_t *)(h + 2), K, err, errlen);
+        if (rc == RGX_OK) { q->n_pairs = h[0]; rc = perm_finish(q, /*device=*/true, err, errlen); }
+        if (rc != RGX_OK) { rgx_cohort_qtl_perm_free(q); return rc; }
+        q->ms_residual = ms_res; q->ms_products = ms_pr; q->ms_perm = now_ms() - run.t0;
+        *out = q;
+        return RGX_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" void rgx_cohort_qtl_perm_free(rgx_qtl_perm_result *q) {
+    if (!q) return;
+    PermBox *box = (PermBox *)q;                                       // q is the first member
+    block_give(box->block, box->block_cap, box->pinned);
+    free(box);
+}
+
+extern "C" int rgx_qtl_permutations(uint32_t n_samples, uint32_t n_perm, uint64_t seed, uint16_t *out, char *err, size_t errlen) {
+    const uint32_t S = n_samples;
+    if (!S || S > 65536u || n_perm > 65535u || !out) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: rgx_qtl_permutations takes 1 to 65536 samples, at most 65535 permutations and room for them\n");
+    uint64_t z = seed;
+    auto next = [&]() {
+        z += 0x9E3779B97F4A7C15ull;
+        uint64_t x = z;
+        x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ x >> 27) * 0x94D049BB133111EBull;
+        return x ^ x >> 31;
+    };
+    for (uint32_t b = 0; b <= n_perm; ++b) {
+        uint16_t *p = out + (size_t)b * S;
+        for (uint32_t s = 0; s < S; ++s) p[s] = (uint16_t)s;
+        if (!b) continue;
+        for (uint32_t i = S - 1; i >= 1; --i) {
+            const uint32_t j = (uint32_t)(((unsigned __int128)next() * (i + 1)) >> 64);
+            std::swap(p[i], p[j]);
+        }
+    }
+    return RGX_OK;
+}
+
+extern "C" double rgx_qtl_digamma(double x) { return x > 0.0 ? (double)digamma_l(x) : NAN; }
+extern "C" double rgx_qtl_trigamma(double x) { return x > 0.0 ? (double)trigamma_l(x) : NAN; }
+extern "C" double rgx_qtl_betainc(double x, double a, double b) {
+    if (!(a > 0.0) || !(b > 0.0) || !(x >= 0.0) || !(x <= 1.0) || std::isinf(a) || std::isinf(b)) return NAN;
+    return (double)betainc_l(x, a, b);
+}
+extern "C" int rgx_qtl_beta_fit(const double *p, uint32_t n, double *shape1, double *shape2) {
+    long double a = NAN, b = NAN;
+    int status = 2;
+    if (p) {
+        bool inside = true;
+        for (uint32_t i = 0; i < n; ++i) inside = inside && p[i] > 0.0 && p[i] < 1.0;
+        if (inside) status = beta_fit_l(p, n, a, b);
+    }
+    if (shape1) *shape1 = (double)a;
+    if (shape2) *shape2 = (double)b;
+    return status;
+}
+
+extern "C" int rgx_cohort_qtl_permute(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants,
+                                      const uint32_t *var_tid, const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates,
+                                      uint32_t window, uint32_t n_perm, const uint16_t *perm, rgx_qtl_perm_result **out, char *err, size_t errlen) {
+    if (!co || !ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_permute needs a cohort and a phenotype table\n");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(co->mu);
+    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
+    int rc = check_qtl(a, err, errlen);
+    if (rc == RGX_OK) rc = check_perm(ph->n_rows, ph->n_samples, n_perm, perm, err, errlen);
+    if (rc != RGX_OK) return rc;
+    PermRun p(co, a, n_perm, perm, err, errlen);
+    rc = p.run.open();
+    if (rc == RGX_OK) rc = p.run.residuals();
+    if (rc == RGX_OK) rc = p.run.compact();
+    if (rc == RGX_OK) rc = p.run.plan_launch();
+    if (rc == RGX_OK) rc = p.products();
+    if (rc == RGX_OK) rc = p.finish(out);
+    if (rc != RGX_OK && p.run.st) (void)hipStreamSynchronize(p.run.st);   // (the uploads read the caller's arrays and this run's T, Q and permT)
+    return rc;
+}
+
+extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                                           const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, uint32_t window,
+                                           uint32_t n_perm, const uint16_t *perm, rgx_qtl_perm_result **out, char *err, size_t errlen) {
+    if (!ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_permute_host needs a phenotype table\n");
+    *out = nullptr;
+    const double t0 = now_ms();
+    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
+    int rc = check_qtl(a, err, errlen);
+    if (rc == RGX_OK) rc = check_perm(ph->n_rows, ph->n_samples, n_perm, perm, err, errlen);
+    if (rc != RGX_OK) return rc;
+    QtlHost h;
+    rc = qtl_host_prepare(a, h, err, errlen);
+    if (rc != RGX_OK) return rc;
+    const uint64_t K = ph->n_rows; const uint32_t S = ph->n_samples, V = n_variants, B = n_perm;
+    rgx_qtl_perm_result *q = perm_alloc(K, S, V, n_cov, B, false);
+    if (!q) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the result of %llu rows and %u permutations\n", (unsigned long long)K, B);
+    memcpy(q->yy, h.yy.data(), K * 8);
+    if (V) { memcpy(q->gg, h.gg.data(), (size_t)V * 8); memcpy(q->variant_verdict, h.verdict.data(), V); }
+    q->n_pairs = h.P;
+    try {
+        WorkerPool pool(h.P * ((uint64_t)B + 1) * S < (1u << 20) ? 1 : host_threads());
+        pool.run((size_t)K, [&](size_t k) {
+            std::vector<double> yp(S);
+            const double *y = h.Y.data() + k * S;
+            double *row = q->perm_r + k * ((size_t)B + 1);
+            q->n_cis[k] = h.cnt[k]; q->best_variant[k] = RGX_NO_PAIR; q->best_r[k] = 0.0; q->best_slope[k] = 0.0;
+            for (uint32_t b = 0; b <= B; ++b) {
+                const uint16_t *pb = perm + (size_t)b * S;
+                for (uint32_t s = 0; s < S; ++s) yp[s] = y[pb[s]];
+                uint64_t top = 0;
+                for (uint32_t i = 0; i < h.cnt[k]; ++i) {
+                    const uint32_t v = h.u_var[h.lo[k] + i]; const double *g = h.G.data() + (size_t)v * S;
+                    double acc = 0.0;
+                    for (uint32_t s = 0; s < S; ++s) acc = qtl_fma(yp[s], g[s], acc);
+                    const double r = qtl_r(acc, h.yy[k], h.gg[v]);
+                    const uint64_t bits = qtl_abs_bits(r);
+                    if (!b && (q->best_variant[k] == RGX_NO_PAIR || bits > top)) {
+                        q->best_variant[k] = v; q->best_r[k] = r; q->best_slope[k] = qtl_slope(acc, h.gg[v]);
+                    }
+                    if (bits > top) top = bits;
+                }
+                memcpy(&row[b], &top, 8);
+            }
+        });
+    } catch (const std::exception &) { rgx_cohort_qtl_perm_free(q); return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory or threads for the permutation pass\n"); }
+    const double t1 = now_ms();
+    rc = perm_finish(q, /*device=*/false, err, errlen);
+    if (rc != RGX_OK) { rgx_cohort_qtl_perm_free(q); return rc; }
+    q->ms_residual = h.t_pairs - h.t_res; q->ms_products = t1 - h.t_pairs; q->ms_perm = now_ms() - t0;
+    *out = q;
+    return RGX_OK;
+}
+
+// ---- text ---------------------------------------------------------------------------------------------------------------------------------------------
+extern "C" size_t rgx_cohort_format_qtl_perm(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
+                                             const rgx_qtl_perm_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap) {
+    if (!m || !cl || !ph || cl->n_rows != m->n || (q && (q->n_rows != ph->n_rows || (q->n_variants && (!var_pos || !variant_id))))) return 0;
+    for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return 0;
+    auto run = [&](char *dst) {
+        size_t need = 0;
+        auto put = [&](const char *s, size_t n) { if (dst) memcpy(dst + need, s, n); need += n; };
+        char num[256];
+        auto put_g = [&](double x, char end) {
+            if (x != x) put(num, (size_t)snprintf(num, sizeof num, "nan%c", end)); else put(num, (size_t)snprintf(num, sizeof num, "%.17g%c", x, end));
+        };
+        static const char head[] = "phenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\t"
+                                   "pval_perm\tpval_beta\n";
+        put(head, sizeof head - 1);
+        for (uint64_t k = 0; q && k < q->n_rows; ++k) {
+            if (!q->n_cis[k]) continue;
+            const uint32_t i = ph->row[k], c = cl->cluster[i], cls = rgx::strand_class(m->strand[i]), v = q->best_variant[k];
+            const char *contig = m->ref_name[m->tid[i]];
+            const double t = rgx_qtl_tstat(q->best_r[k], q->dof);
+            put(contig, strlen(contig));
+            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s\t%u\t", m->start[i], m->end[i], (unsigned long long)c + 1,
+                                      cls == 0 ? "+" : cls == 1 ? "-" : "NA", q->n_cis[k]));
+            put_g(q->beta_shape1[k], '\t'); put_g(q->beta_shape2[k], '\t');
+            put(num, (size_t)snprintf(num, sizeof num, "%u\t", q->dof));
+            put(variant_id[v], strlen(variant_id[v]));
+            put(num, (size_t)snprintf(num, sizeof num, "\t%lld\t", (long long)var_pos[v] - (long long)m->start[i]));
+            put_g(q->best_r[k], '\t'); put_g(q->best_slope[k], '\t'); put_g(q->best_slope[k] / t, '\t'); put_g(t, '\t');
+            put_g(rgx_qtl_pvalue(t, q->dof), '\t'); put_g(q->p_perm[k], '\t'); put_g(q->p_beta[k], '\n');
+        }
+        return need;
+    };
+    const size_t need = run(nullptr);
+    if (buf && need <= cap) run(buf);
+    return need;
+}

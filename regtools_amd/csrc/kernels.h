@@ -422,4 +422,15 @@ void launch_qtl_pairs(const double *Yt, size_t ldy, const double *Gt, size_t ldg
                       const double *u_gg, const uint32_t *u_var, double *r, double *slope, uint32_t *pair_variant, hipStream_t st);
 void launch_qtl_best(const double *r, const uint32_t *pair_begin, uint32_t K, uint32_t *best, hipStream_t st);
 
+// ---- the cis-sQTL permutation pass (qtl_perm_kernels.hip; host side in cohort_qtl_perm.cpp) --------------------------------------------------------
+// perm_r (K x n_perm1) = per row and permutation the largest |r| over the row's cis variants, best_u (K) = permutation 0's usable variant (all ones:
+// none).  Y: the row-major residuals; permT: S rows of ldp uint16, ldp a multiple of 64 at or above n_perm1, index 0 behind it; Gt as for the
+// pairs.  K * (ldp / 64) workgroups: the caller keeps that inside 2^31 - 1
+void launch_qtl_perm(const double *Y, uint32_t K, uint32_t S, const uint16_t *permT, size_t ldp, uint32_t n_perm1, const double *Gt, size_t ldg,
+                     const uint32_t *lo, const uint32_t *count, const double *yy, const double *u_gg, double *perm_r, uint32_t *best_u,
+                     hipStream_t st);
+// the winning pair's chain again, a thread per row: the input variant (RGX_NO_PAIR: none), r and slope
+void launch_qtl_perm_best(const double *Y, const double *G, uint32_t K, uint32_t S, const uint32_t *best_u, const uint32_t *u_var, const double *yy,
+                          const double *gg, uint32_t *best_variant, double *best_r, double *best_slope, hipStream_t st);
+
 }  // namespace rgx

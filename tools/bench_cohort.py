@@ -35,6 +35,11 @@
                     100000), beside rgx_cohort_qtl_nominal_host; the pairs P, P S fused multiply-adds over ms_pairs as GFMA/s (and the 4,096 S per tile that were issued), and whether every
                     device run was identical to the others and to the twin in every array as bit patterns
 
+  --perm            rgx_cohort_qtl_permute (ms_perm, ms_residual, ms_products, ms_beta) on --qtl's planted tables with --perms B
+                    permutations (default 1000, seed 0): first and warm calls; P (B + 1) S fused multiply-adds of the contract over ms_products as
+                    GFMA/s, the 4,096 S per tile that were issued, the tile fill; rgx_cohort_qtl_permute_host where its P (B + 1) S stay below
+                    --host-fmas (default 2e11), identical as bit patterns; and ms_pairs of rgx_cohort_qtl_nominal on the same inputs beside it
+
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
 import ctypes as C
@@ -451,6 +456,21 @@ def same_qtl(a, b):
     return a.n_pairs == b.n_pairs and all(np.array_equal(bits(getattr(a, k)), bits(getattr(b, k))) for k in QTL_ARRAYS)
 
 
+def planted_qtl_inputs(a, co, S, K, V):
+    """--qtl's and --perm's table: (the phenotype table, regions, positions, dosages, the components taken as covariates or None, their number)."""
+    from regtools_amd import cohort
+    rng = np.random.default_rng(11)
+    ph = cohort.pheno_table_from_rank2(planted_rank2(S, K))
+    span = 500 * K
+    start = np.sort(rng.integers(1, span, K)).astype(np.uint32)
+    regions = np.stack([np.zeros(K, np.uint32), start, start + rng.integers(50, 5000, K).astype(np.uint32)], axis=1)
+    pos = np.sort(rng.integers(1, span, V)).astype(np.uint32)
+    dosage = rng.binomial(2, rng.uniform(0.05, 0.5, V)[:, None], (V, S)).astype(np.int8)
+    dosage[rng.random((V, S)) < 0.02] = -1
+    n_cov = max(0, min(a.n_cov, K, S - 3))
+    return ph, regions, pos, dosage, co.pheno_pcs(ph, n_cov) if n_cov else None, n_cov
+
+
 def part_qtl(a):
     import regtools_amd
     from regtools_amd import cohort
@@ -458,16 +478,7 @@ def part_qtl(a):
     for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
         S, K, V = [int(x) for x in size.lower().split("x")]
         t0 = time.time()
-        rng = np.random.default_rng(11)
-        ph = cohort.pheno_table_from_rank2(planted_rank2(S, K))
-        span = 500 * K
-        start = np.sort(rng.integers(1, span, K)).astype(np.uint32)
-        regions = np.stack([np.zeros(K, np.uint32), start, start + rng.integers(50, 5000, K).astype(np.uint32)], axis=1)
-        pos = np.sort(rng.integers(1, span, V)).astype(np.uint32)
-        dosage = rng.binomial(2, rng.uniform(0.05, 0.5, V)[:, None], (V, S)).astype(np.int8)
-        dosage[rng.random((V, S)) < 0.02] = -1
-        n_cov = max(0, min(a.n_cov, K, S - 3))
-        pcs = co.pheno_pcs(ph, n_cov) if n_cov else None
+        ph, regions, pos, dosage, pcs, n_cov = planted_qtl_inputs(a, co, S, K, V)
         args = (ph, regions, np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None, a.window)
         line = {"part": "qtl", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "window": a.window, "s_generate": round(time.time() - t0, 1)}
         runs = [co.qtl_nominal(*args) for _ in range(a.reps)]
@@ -487,6 +498,62 @@ def part_qtl(a):
             line.update({"ms_qtl_host": round(h.ms_qtl, 1), "ms_residual_host": round(h.ms_residual, 1), "ms_pairs_host": round(h.ms_pairs, 1),
                          "identical_to_host": bool(same_qtl(runs[0], h))})
             assert line["identical_to_host"], "the device's scan differs from the host twin's"
+            h.close()
+        for q in runs:
+            q.close()
+        print(json.dumps(line), flush=True)
+    co.close()
+
+
+PERM_ARRAYS = ("variant_verdict", "yy", "gg", "n_cis", "perm_r", "best_variant", "best_r", "best_slope", "n_ge", "p_perm", "beta_shape1", "beta_shape2",
+               "p_beta", "beta_status")
+
+
+def same_perm(a, b):
+    def bits(x):
+        x = np.ascontiguousarray(x)
+        return x.view(np.uint64) if x.dtype == np.float64 else x
+    return a.n_pairs == b.n_pairs and all(np.array_equal(bits(getattr(a, k)), bits(getattr(b, k))) for k in PERM_ARRAYS)
+
+
+def part_perm(a):
+    import regtools_amd
+    from regtools_amd import cohort
+    co = regtools_amd.Cohort(ctx=regtools_amd.Context(0))
+    for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
+        S, K, V = [int(x) for x in size.lower().split("x")]
+        t0 = time.time()
+        ph, regions, pos, dosage, pcs, n_cov = planted_qtl_inputs(a, co, S, K, V)
+        B = a.perms
+        perms = cohort.qtl_permutations(S, B, 0)
+        args = (ph, regions, np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None, a.window)
+        line = {"part": "perm", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "window": a.window, "perms": B,
+                "s_generate": round(time.time() - t0, 1)}
+        runs = [co.qtl_permute(*args, perms=perms) for _ in range(a.reps)]
+        warm = runs[1:] or runs
+        best = min(warm, key=lambda q: q.ms_products)
+        P, tiles = runs[0].n_pairs, runs[0].n_tiles
+        fmas = P * (B + 1) * S
+        line.update({"pairs": P, "rows_with_pairs": int((runs[0].n_cis > 0).sum()), "ms_perm": [round(q.ms_perm, 3) for q in runs],
+                     "ms_residual": [round(q.ms_residual, 3) for q in runs], "ms_products": [round(q.ms_products, 3) for q in runs],
+                     "ms_beta": [round(q.ms_beta, 1) for q in runs], "ms_products_best_warm": round(best.ms_products, 3), "fmas": fmas,
+                     "tiles": tiles, "tile_fill": round(P * (B + 1) / (4096.0 * tiles), 3) if tiles else None,
+                     "GFMA_per_s_issued_over_ms_products": round(4096.0 * tiles * S / best.ms_products / 1e6, 1) if best.ms_products > 0 else None,
+                     "GFMA_per_s_over_ms_products": round(fmas / best.ms_products / 1e6, 1) if best.ms_products > 0 else None,
+                     "beta_status_counts": np.bincount(runs[0].beta_status, minlength=3).tolist(),
+                     "identical_every_time": bool(all(same_perm(runs[0], q) for q in runs[1:]))})
+        assert line["identical_every_time"], "two device runs differ"
+        nominal = [co.qtl_nominal(*args) for _ in range(2)]
+        line.update({"nominal_ms_pairs": [round(q.ms_pairs, 3) for q in nominal], "nominal_ms_qtl": [round(q.ms_qtl, 3) for q in nominal]})
+        has = nominal[0].best != 0xffffffff
+        assert np.array_equal(runs[0].best_variant[has], nominal[0].pair_variant[nominal[0].best[has]]), "the best variants differ from the nominal scan's"
+        for q in nominal:
+            q.close()
+        if not a.no_host and fmas <= a.host_fmas:
+            h = cohort.qtl_permute_host(*args, perms=perms)
+            line.update({"ms_perm_host": round(h.ms_perm, 1), "ms_products_host": round(h.ms_products, 1), "ms_beta_host": round(h.ms_beta, 1),
+                         "identical_to_host": bool(same_perm(runs[0], h))})
+            assert line["identical_to_host"], "the device's permutation pass differs from the host twin's"
             h.close()
         for q in runs:
             q.close()
@@ -552,6 +619,9 @@ def main():
     ap.add_argument("--pheno", action="store_true", help="the phenotype part, alone")
     ap.add_argument("--pcs", action="store_true", help="the principal component part, alone")
     ap.add_argument("--qtl", action="store_true", help="the sQTL scan part, alone")
+    ap.add_argument("--perm", action="store_true", help="the sQTL permutation part, alone")
+    ap.add_argument("--perms", type=int, default=1000, help="--perm: permutations")
+    ap.add_argument("--host-fmas", type=float, default=2e11, help="--perm: the twin runs when its fused multiply-adds stay below this")
     ap.add_argument("--n-cov", type=int, default=10, help="--qtl: principal components taken as covariates (clipped to the samples less three)")
     ap.add_argument("--window", type=int, default=100000, help="--qtl: the cis window")
     ap.add_argument("--planted", default="", help="--pcs: planted tables, SAMPLESxROWS; --qtl: SAMPLESxROWSxVARIANTS; comma separated")
@@ -574,6 +644,8 @@ def main():
         return part_pcs(a)
     if a.qtl:
         return part_qtl(a)
+    if a.perm:
+        return part_perm(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
