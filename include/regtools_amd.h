@@ -655,6 +655,85 @@ int  rgx_qtl_beta_fit(const double *p, uint32_t n, double *shape1, double *shape
 size_t rgx_cohort_format_qtl_perm(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, const rgx_qtl_perm_result *q,
                                   const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
 
+/* -----------------------------------------------------------------------------------------------------
+ * The GROUPED permutation pass: one corrected p per group of table rows -- for a LeafCutter table per intron cluster, whose introns are ratios
+ * over one denominator tested against the same variants (FastQTL's --grp, tensorQTL's map_cis(..., group_s=...); neither is available to this
+ * project: checked against a restatement in exact rationals and against the ungrouped pass).  The deviations are the ungrouped pass's.
+ *   input                 everything rgx_cohort_qtl_permute takes; n_groups = G; group[K]: the row's group in [0, G), or RGX_NO_GROUP for a row
+ *                         that takes part in nothing.  A group's members are its rows in ascending table row; they need not be contiguous; a
+ *                         group may be empty
+ *   errors                RGX_ERR_ARG, before any launch: the ungrouped pass's, with G (B + 1) > 2^32 - 2^16 where it has K (B + 1); G == 0 or
+ *                         G > 2^31 - 1; a group[k] >= G that is not RGX_NO_GROUP.  The flag words as in the nominal scan
+ *   steps                 basis, dot64, residuals, yy, gg, verdicts, flat rows and cis ranges: the nominal contract's; n_cis[k] as in the ungrouped
+ *                         pass (also for a row without a group); group_n_cis[g] = the 64-bit sum of its members' n_cis, n_pairs their sum over
+ *                         the groups
+ *   per (member k, b, v)  the ungrouped pass's chain and r, with the unpermuted row's own yy[k]
+ *   perm_r[g][b]          the largest |r| over all members and their cis variants, compared and stored as bit patterns, b = 0 .. B; +0.0
+ *                         throughout for a group without pairs (empty, all members flat, or no member with a cis variant)
+ *   best                  of b = 0: best_row[g] (a table row) and best_variant[g] (an input variant) are the pair with the largest bits; on
+ *                         equal bits the lowest table row, then the earliest variant; both RGX_NO_PAIR without pairs.  best_r[g] and
+ *                         best_slope[g] are that pair's chain: bit for bit the nominal scan's r and slope there; +0.0 without pairs
+ *   n_ge .. beta_status   the ungrouped pass's definitions applied to the group's series, dof = S - n_cov - 2
+ * No K x (B + 1) array exists anywhere.
+ * ----------------------------------------------------------------------------------------------------- */
+#define RGX_NO_GROUP 0xffffffffu
+/* Owned by the library (rgx_cohort_qtl_group_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_variants;      /* V */
+    uint32_t   n_cov;
+    uint32_t   dof;             /* S - n_cov - 2 */
+    uint32_t   n_perm;          /* B */
+    uint32_t   n_groups;        /* G */
+    uint64_t   n_pairs;         /* the sum of group_n_cis */
+    uint8_t   *variant_verdict; /* V: 0 usable, 1 constant, 2 explained by the covariates */
+    double    *yy;              /* K */
+    double    *gg;              /* V */
+    uint32_t  *n_cis;           /* K: the row's pairs */
+    uint32_t  *grp_begin;       /* G + 1: group g's members are grp_row[grp_begin[g] .. grp_begin[g + 1]) */
+    uint32_t  *grp_row;         /* grp_begin[G]: table rows, ascending inside a group */
+    uint64_t  *group_n_cis;     /* G */
+    double    *perm_r;          /* G x (B + 1), row-major */
+    uint32_t  *best_row;        /* G: a table row, or RGX_NO_PAIR */
+    uint32_t  *best_variant;    /* G: an input variant, or RGX_NO_PAIR */
+    double    *best_r, *best_slope;   /* G */
+    uint32_t  *n_ge;            /* G */
+    double    *p_perm;          /* G */
+    double    *beta_shape1, *beta_shape2, *p_beta;   /* G */
+    uint8_t   *beta_status;     /* G */
+    /* statistics */
+    uint64_t   n_constant, n_explained, n_flat_rows;
+    uint64_t   n_tiles;         /* the device's products of 64 permutations x 64 usable variants: per member ceil((B + 1) / 64) * ceil(n_cis / 64)
+                                   (the twin: 0) */
+    double     ms_perm;         /* this call, wall */
+    double     ms_residual;     /* device time from the first upload to the sample-major residuals (the twin: its residual loops, wall) */
+    double     ms_products;     /* device time of the permuted products and the best pairs (the twin: its loops, wall) */
+    double     ms_beta;         /* the beta approximation, host wall */
+} rgx_qtl_group_result;
+/* group_out[k] = the cluster of ph->row[k] in cl, renumbered 0 .. G - 1 in ascending order of each cluster's first table row; *n_groups = G.
+ * RGX_ERR_ARG when a row of ph is no row of cl or is not clustered there. */
+int  rgx_cohort_pheno_groups(const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, uint32_t *group_out, uint32_t *n_groups, char *err,
+                             size_t errlen);
+/* On the cohort's device and stream: the ungrouped pass's stages with one workgroup per (group, 64 permutations) that walks the group's members,
+ * a thread per group for the best pair, ONE host wait in front of the copies back, the beta approximation on the host. */
+int  rgx_cohort_qtl_permute_grouped(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants,
+                                    const uint32_t *var_tid, const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov,
+                                    const double *covariates, uint32_t window, uint32_t n_perm, const uint16_t *perm, uint32_t n_groups,
+                                    const uint32_t *group, rgx_qtl_group_result **out, char *err, size_t errlen);
+/* Host twin: the same chains in plain C++ (std::fma), a group a task, the same beta function, no device.  NOT a fallback. */
+int  rgx_cohort_qtl_permute_grouped_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                                         const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, uint32_t window,
+                                         uint32_t n_perm, const uint16_t *perm, uint32_t n_groups, const uint32_t *group,
+                                         rgx_qtl_group_result **out, char *err, size_t errlen);
+void rgx_cohort_qtl_group_free(rgx_qtl_group_result *q);
+/* "group_id\tgroup_size\tphenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\t
+ * pval_perm\tpval_beta" and one line per group that has pairs, in group order: group_id = clu_<k>_<s> as in the row IDs, of the group's first
+ * member; group_size = its member count; phenotype_id and distance those of best_row, num_var = group_n_cis, doubles as %.17g, NaN as "nan".
+ * q == NULL writes the header line alone; 0 when the arguments do not fit together.  Buffer protocol of rgx_cohort_format_counts. */
+size_t rgx_cohort_format_qtl_group(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
+                                   const rgx_qtl_group_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
+
 /* The genotypes of a cohort's samples from a VCF (plain, gzip, bgzip) or a BCF, as rgx_cohort_qtl_nominal takes them.  Samples are matched to
  * m->sample_name BY NAME; a cohort sample the file does not have is RGX_ERR_ARG, "Sample <name> has no genotypes in <file>".  A record is
  * skipped, and counted, when it is multi-allelic (anything but one ALT), carries no GT, or lies on a contig m does not know.  The dosage is the

@@ -62,7 +62,9 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_cohort_pheno_regions", "rgx_cohort_qtl_nominal", "rgx_cohort_qtl_nominal_host", "rgx_cohort_qtl_free", "rgx_qtl_tstat",
            "rgx_qtl_pvalue", "rgx_cohort_format_qtl", "rgx_genotypes_load", "rgx_genotypes_free",
            "rgx_qtl_permutations", "rgx_cohort_qtl_permute", "rgx_cohort_qtl_permute_host", "rgx_cohort_qtl_perm_free", "rgx_qtl_digamma",
-           "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm"]
+           "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm",
+           "rgx_cohort_pheno_groups", "rgx_cohort_qtl_permute_grouped", "rgx_cohort_qtl_permute_grouped_host", "rgx_cohort_qtl_group_free",
+           "rgx_cohort_format_qtl_group"]
 
 
 class CohortParams(C.Structure):
@@ -136,6 +138,19 @@ class QtlPermResult(C.Structure):
                 ("n_perm", C.c_uint32), ("n_pairs", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)), ("yy", C.POINTER(C.c_double)),
                 ("gg", C.POINTER(C.c_double)), ("n_cis", C.POINTER(C.c_uint32)), ("perm_r", C.POINTER(C.c_double)),
                 ("best_variant", C.POINTER(C.c_uint32)), ("best_r", C.POINTER(C.c_double)), ("best_slope", C.POINTER(C.c_double)),
+                ("n_ge", C.POINTER(C.c_uint32)), ("p_perm", C.POINTER(C.c_double)), ("beta_shape1", C.POINTER(C.c_double)),
+                ("beta_shape2", C.POINTER(C.c_double)), ("p_beta", C.POINTER(C.c_double)), ("beta_status", C.POINTER(C.c_uint8)),
+                ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("ms_perm", C.c_double), ("ms_residual", C.c_double), ("ms_products", C.c_double), ("ms_beta", C.c_double)]
+
+
+class QtlGroupResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("dof", C.c_uint32),
+                ("n_perm", C.c_uint32), ("n_groups", C.c_uint32), ("n_pairs", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)),
+                ("yy", C.POINTER(C.c_double)), ("gg", C.POINTER(C.c_double)), ("n_cis", C.POINTER(C.c_uint32)),
+                ("grp_begin", C.POINTER(C.c_uint32)), ("grp_row", C.POINTER(C.c_uint32)), ("group_n_cis", C.POINTER(C.c_uint64)),
+                ("perm_r", C.POINTER(C.c_double)), ("best_row", C.POINTER(C.c_uint32)), ("best_variant", C.POINTER(C.c_uint32)),
+                ("best_r", C.POINTER(C.c_double)), ("best_slope", C.POINTER(C.c_double)),
                 ("n_ge", C.POINTER(C.c_uint32)), ("p_perm", C.POINTER(C.c_double)), ("beta_shape1", C.POINTER(C.c_double)),
                 ("beta_shape2", C.POINTER(C.c_double)), ("p_beta", C.POINTER(C.c_double)), ("beta_status", C.POINTER(C.c_uint8)),
                 ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
@@ -332,6 +347,14 @@ def lib():
         L.rgx_cohort_format_qtl_perm.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlPermResult), C.c_void_p, P(C.c_char_p),
                                                  C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_qtl_perm.restype = C.c_size_t
+        group_in = perm_in[:11] + [C.c_uint32, C.c_void_p, P(P(QtlGroupResult)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_permute_grouped.argtypes = [C.c_void_p] + group_in
+        L.rgx_cohort_qtl_permute_grouped_host.argtypes = group_in
+        L.rgx_cohort_qtl_group_free.argtypes = [P(QtlGroupResult)]
+        L.rgx_cohort_pheno_groups.argtypes = [P(CohortClusters), P(PhenoTable), C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_qtl_group.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlGroupResult), C.c_void_p, P(C.c_char_p),
+                                                  C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_qtl_group.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

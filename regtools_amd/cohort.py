@@ -482,7 +482,7 @@ def qtl_beta_fit(p):
     return status, s1.value, s2.value
 
 
-def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms):
+def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms, groups=None, n_groups=None):
     import numpy as np
     S = ph.n_samples
     reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1, 3)
@@ -503,10 +503,22 @@ def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates,
         n_perm = len(pm) - 1
         if n_perm < 0:
             raise ValueError("perms needs the identity as its row 0")
-    out = C.POINTER(_ffi.QtlPermResult)()
     err = C.create_string_buffer(512)
-    rc = fn(*(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
-                       n_perm, pm.ctypes.data, C.byref(out), err, len(err))))
+    shared = front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
+                      n_perm, pm.ctypes.data)
+    if groups is not None:
+        grp = np.ascontiguousarray(groups, dtype=np.uint32)
+        if grp.shape != (ph.n_rows,):
+            raise ValueError("one group per table row")
+        if not 0 <= int(n_groups) <= 0xffffffff:
+            raise ValueError("n_groups must fit 32 bits")
+        out = C.POINTER(_ffi.QtlGroupResult)()
+        rc = fn(*(shared + (int(n_groups), grp.ctypes.data, C.byref(out), err, len(err))))
+        if rc != 0:
+            raise RegtoolsError(rc, err.value.decode())
+        return CohortQTLGroup(out)
+    out = C.POINTER(_ffi.QtlPermResult)()
+    rc = fn(*(shared + (C.byref(out), err, len(err))))
     if rc != 0:
         raise RegtoolsError(rc, err.value.decode())
     return CohortQTLPerm(out)
@@ -516,6 +528,87 @@ def qtl_permute_host(ph, regions, var_tid, var_pos, dosage, covariates=None, win
     """rgx_cohort_qtl_permute_host: the permutation pass by the library's plain C++ twin, no device involved.  The arguments are
     qtl_nominal_host's; perms: (B + 1) x S uint16 with the identity as row 0, or None for qtl_permutations(S, n_perm, seed)."""
     return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms)
+
+
+class CohortQTLGroup(object):
+    """rgx_qtl_group_result: the grouped permutation pass of the cis-sQTL scan -- per variant its verdict and gg, per row yy and n_cis, the
+    groups' member lists (grp_begin, grp_row), and per group group_n_cis, perm_r (G x (B + 1): the largest |r| over all members' cis variants
+    under the identity and the B permutations), the best pair of the identity (best_row, a table row, and best_variant, an input variant, or
+    NO_PAIR; best_r, best_slope), n_ge, p_perm, and the beta approximation (beta_shape1, beta_shape2, p_beta, beta_status).  The array attributes
+    are numpy VIEWS of memory this object owns: copy what must outlive it."""
+    NO_PAIR = 0xffffffff
+    NO_GROUP = 0xffffffff
+
+    def __init__(self, handle):
+        import numpy as np
+        self._lib = _ffi.lib()
+        self._h = handle
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.dof, self.n_perm, self.n_groups, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_perm), int(p.n_groups), int(p.n_pairs)
+        self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
+        self.n_tiles = int(p.n_tiles)
+        self.ms_perm, self.ms_residual, self.ms_products, self.ms_beta = p.ms_perm, p.ms_residual, p.ms_products, p.ms_beta
+
+        def view(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        K, V, G, B1 = self.n_rows, self.n_variants, self.n_groups, self.n_perm + 1
+        self.variant_verdict = view(p.variant_verdict, V, np.uint8)
+        self.yy, self.gg, self.n_cis = view(p.yy, K, np.float64), view(p.gg, V, np.float64), view(p.n_cis, K, np.uint32)
+        self.grp_begin = view(p.grp_begin, G + 1, np.uint32)
+        self.grp_row = view(p.grp_row, int(self.grp_begin[G]), np.uint32)
+        self.group_n_cis, self.perm_r = view(p.group_n_cis, G, np.uint64), view(p.perm_r, G * B1, np.float64).reshape(G, B1)
+        self.best_row, self.best_variant = view(p.best_row, G, np.uint32), view(p.best_variant, G, np.uint32)
+        self.best_r, self.best_slope = view(p.best_r, G, np.float64), view(p.best_slope, G, np.float64)
+        self.n_ge, self.p_perm = view(p.n_ge, G, np.uint32), view(p.p_perm, G, np.float64)
+        self.beta_shape1, self.beta_shape2 = view(p.beta_shape1, G, np.float64), view(p.beta_shape2, G, np.float64)
+        self.p_beta, self.beta_status = view(p.p_beta, G, np.float64), view(p.beta_status, G, np.uint8)
+
+    def text(self, matrix, clusters, ph, var_pos, variant_ids):
+        """One line per group that has pairs: group_id, group_size, then CohortQTLPerm.text's columns for the group's best pair with num_var =
+        group_n_cis.  The arguments are CohortQTL.text's."""
+        import numpy as np
+        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
+        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
+            raise ValueError("one position and one id per variant")
+        fn = self._lib.rgx_cohort_format_qtl_group
+        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
+        return buf.raw[:n]
+
+    def close(self):
+        if self._h:
+            self._lib.rgx_cohort_qtl_group_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pheno_groups(clusters, ph):
+    """rgx_cohort_pheno_groups: (groups, n_groups) -- per row of the phenotype table its cluster, renumbered 0 .. n_groups - 1 in ascending order
+    of each cluster's first table row."""
+    import numpy as np
+    out = np.zeros(ph.n_rows, np.uint32)
+    n = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    rc = _ffi.lib().rgx_cohort_pheno_groups(clusters._h, ph._h, out.ctypes.data, C.byref(n), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return out, int(n.value)
+
+
+def qtl_permute_grouped_host(ph, regions, groups, n_groups, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0,
+                             perms=None):
+    """rgx_cohort_qtl_permute_grouped_host: the grouped permutation pass by the library's plain C++ twin, no device involved.  groups: per table
+    row its group in [0, n_groups) or CohortQTLGroup.NO_GROUP; the other arguments are qtl_permute_host's."""
+    return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_grouped_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
+                          seed, perms, groups, n_groups)
 
 
 class PlantedPhenotypes(object):
@@ -672,6 +765,14 @@ class Cohort(object):
         arguments are qtl_permute_host's."""
         return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
                               seed, perms)
+
+    def qtl_permute_grouped(self, ph, regions, groups, n_groups, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0,
+                            perms=None):
+        """The grouped permutation pass on this cohort's device (rgx_cohort_qtl_permute_grouped): per group of rows -- per intron cluster with
+        pheno_groups -- the largest |r| over all its members' cis variants under the identity and n_perm permutations, the best (row, variant)
+        of the identity, and on the host the empirical p and its beta approximation.  The arguments are qtl_permute_grouped_host's."""
+        return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute_grouped, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window,
+                              n_perm, seed, perms, groups, n_groups)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

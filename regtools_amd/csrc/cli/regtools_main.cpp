@@ -278,8 +278,11 @@ void cohort_usage(std::ostream &out) {
         << "\t\t-R FILE\tThe permutation pass of the cis-sQTL scan: one line per row of the -q table that has variants of -g in its window, with its\n"
         << "\t\t\t best variant, the empirical p of that variant's |r| among -B permutations of the samples and its beta approximation.\n"
         << "\t\t\t Needs -g; the table, the components and the window are those of -Q, beside which it may stand.\n"
-        << "\t\t-B INT\tThe permutations of -R, 1 to 65535. [1000]\n"
-        << "\t\t-e INT\tThe seed of -R's permutations. [0]\n"
+        << "\t\t-G FILE\tThe grouped permutation pass: one line per cluster of the -q table whose introns have variants of -g in their windows, with\n"
+        << "\t\t\t the cluster's best (intron, variant) and the empirical p and beta approximation of the largest |r| over ALL its introns.\n"
+        << "\t\t\t Needs -g; everything else as for -R, beside which (and beside -Q) it may stand.\n"
+        << "\t\t-B INT\tThe permutations of -R and -G, 1 to 65535. [1000]\n"
+        << "\t\t-e INT\tThe seed of -R's and -G's permutations. [0]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -345,7 +348,7 @@ bool cohort_read_index(const std::string &bam, std::vector<char> &out) {
 int junctions_cohort(int argc, char **argv) {
     try {
         ExtractOptions o;
-        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA", perm = "NA";
+        std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA", perm = "NA", grouped = "NA";
         uint32_t n_components = 10, window = 100000, n_perm = 1000;
         uint64_t seed = 0;
         rgx_pheno_params qp;
@@ -360,7 +363,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:G:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -395,6 +398,7 @@ int junctions_cohort(int argc, char **argv) {
                     break;
                 }
                 case 'R': perm = optarg; break;
+                case 'G': grouped = optarg; break;
                 case 'B': {
                     char *end = nullptr;
                     errno = 0;
@@ -459,7 +463,7 @@ int junctions_cohort(int argc, char **argv) {
         for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
         if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
         if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
-        if ((qtl != "NA" || perm != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
+        if ((qtl != "NA" || perm != "NA" || grouped != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
         for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
         for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
             throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
@@ -506,7 +510,7 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_scan = want_qtl || want_perm;
+        const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_group = grouped != "NA", want_scan = want_qtl || want_perm || want_group;
         const bool want_pheno = phenotypes != "NA" || components != "NA" || want_scan;
         if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
@@ -524,20 +528,30 @@ int junctions_cohort(int argc, char **argv) {
         // a table without rows has no pairs: the file is its header line
         rgx_qtl_result *qr = nullptr;
         rgx_qtl_perm_result *pr = nullptr;
+        rgx_qtl_group_result *gr = nullptr;
         if (ok && want_scan && ph->n_rows) {
             std::vector<rgx_qtl_region> regions((size_t)ph->n_rows);
             int rc = rgx_cohort_pheno_regions(m, ph, regions.data(), err, sizeof err);
             if (rc == RGX_OK && want_qtl) rc = rgx_cohort_qtl_nominal(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
                                                                       pcs ? pcs->component : nullptr, window, &qr, err, sizeof err);
-            if (rc == RGX_OK && want_perm) {
+            if (rc == RGX_OK && (want_perm || want_group)) {
                 std::vector<uint16_t> perms(((size_t)n_perm + 1) * ph->n_samples);
                 rc = rgx_qtl_permutations(ph->n_samples, n_perm, seed, perms.data(), err, sizeof err);
-                if (rc == RGX_OK) rc = rgx_cohort_qtl_permute(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
+                if (rc == RGX_OK && want_perm) rc = rgx_cohort_qtl_permute(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
                                                               pcs ? pcs->component : nullptr, window, n_perm, perms.data(), &pr, err, sizeof err);
+                if (rc == RGX_OK && want_group) {
+                    std::vector<uint32_t> group((size_t)ph->n_rows);
+                    uint32_t n_groups = 0;
+                    rc = rgx_cohort_pheno_groups(cl, ph, group.data(), &n_groups, err, sizeof err);
+                    if (rc == RGX_OK) rc = rgx_cohort_qtl_permute_grouped(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
+                                                                          pcs ? pcs->component : nullptr, window, n_perm, perms.data(), n_groups,
+                                                                          group.data(), &gr, err, sizeof err);
+                }
             }
             if (rc != RGX_OK) { failure = err; ok = false; }
         }
         if (!ok) {
+            rgx_cohort_qtl_group_free(gr);
             rgx_cohort_qtl_perm_free(pr);
             rgx_cohort_qtl_free(qr);
             rgx_genotypes_free(gt);
@@ -573,6 +587,10 @@ int junctions_cohort(int argc, char **argv) {
         if (want_perm) {
             nr = rgx_cohort_format_qtl_perm(m, cl, ph, pr, gt->pos, gt->id, nullptr, 0); rtx.reset(new char[nr + 1]);
             rgx_cohort_format_qtl_perm(m, cl, ph, pr, gt->pos, gt->id, rtx.get(), nr); }
+        size_t ng = 0; std::unique_ptr<char[]> gtx;
+        if (want_group) {
+            ng = rgx_cohort_format_qtl_group(m, cl, ph, gr, gt->pos, gt->id, nullptr, 0); gtx.reset(new char[ng + 1]);
+            rgx_cohort_format_qtl_group(m, cl, ph, gr, gt->pos, gt->id, gtx.get(), ng); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -607,6 +625,11 @@ int junctions_cohort(int argc, char **argv) {
             if (!g) throw std::runtime_error("Unable to write " + perm + "\n\n");
             short_write |= fwrite(rtx.get(), 1, nr, g) != nr; short_write |= fclose(g) != 0;
         }
+        if (want_group) {
+            FILE *g = fopen(grouped.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + grouped + "\n\n");
+            short_write |= fwrite(gtx.get(), 1, ng, g) != ng; short_write |= fclose(g) != 0;
+        }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
             fprintf(stderr, "[regtools_amd] cohort: %u samples, %llu triples, %llu rows, adds %.3f ms, finish %.3f ms\n", m->n_samples,
@@ -637,6 +660,16 @@ int junctions_cohort(int argc, char **argv) {
                     (unsigned long long)(pr ? pr->n_pairs : 0), (unsigned long long)n_lines, (unsigned long long)(pr ? pr->n_tiles : 0),
                     pr ? pr->ms_perm : 0.0, pr ? pr->ms_residual : 0.0, pr ? pr->ms_products : 0.0, pr ? pr->ms_beta : 0.0);
         }
+        if (want_group && getenv("REGTOOLS_AMD_STATS")) {
+            uint64_t n_lines = 0;
+            for (uint64_t g = 0; gr && g < gr->n_groups; ++g) n_lines += gr->group_n_cis[g] != 0;
+            fprintf(stderr, "[regtools_amd] group: %u permutations from seed %llu, %u variants, %u covariates, %u groups, %llu pairs, %llu groups written, "
+                    "%llu tiles, %.3f ms (residuals %.3f ms, products %.3f ms, beta %.3f ms)\n", n_perm, (unsigned long long)seed, gt->n_variants, n_cov,
+                    gr ? gr->n_groups : 0u, (unsigned long long)(gr ? gr->n_pairs : 0), (unsigned long long)n_lines,
+                    (unsigned long long)(gr ? gr->n_tiles : 0), gr ? gr->ms_perm : 0.0, gr ? gr->ms_residual : 0.0, gr ? gr->ms_products : 0.0,
+                    gr ? gr->ms_beta : 0.0);
+        }
+        rgx_cohort_qtl_group_free(gr);
         rgx_cohort_qtl_perm_free(pr);
         rgx_cohort_qtl_free(qr);
         rgx_genotypes_free(gt);

@@ -46,12 +46,15 @@ rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_c
     return q;
 }
 
-// what the host can judge of the permutations, the same for the device and the twin
-int check_perm(uint64_t K, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen) {
+}  // namespace
+
+// what the host can judge of the permutations, the same for the device and the twin; n_series of `series` (rows, groups) get B + 1 values each
+int check_perm(uint64_t n_series, const char *series, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen) {
     if (!B || B > 65535u) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the permutation pass takes 1 to 65535 permutations; %u were asked for\n", B);
     if (!perm) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the permutation pass needs its permutations\n");
-    if (K * ((uint64_t)B + 1) > kQtlMaxPairs) return fail(err, errlen, RGX_ERR_ARG,
-        "regtools_amd: %llu rows x %u permutations and the identity; the permutation pass takes at most 2^32 - 2^16 of them\n", (unsigned long long)K, B);
+    if (n_series * ((uint64_t)B + 1) > kQtlMaxPairs) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: %llu %s x %u permutations and the identity; the permutation pass takes at most 2^32 - 2^16 of them\n",
+        (unsigned long long)n_series, series, B);
     for (uint32_t s = 0; s < S; ++s) if (perm[s] != s) return fail(err, errlen, RGX_ERR_ARG,
         "regtools_amd: row 0 of the permutations is not the identity (sample %u stands at %u)\n", (uint32_t)perm[s], s);
     std::vector<uint8_t> seen(S);
@@ -67,7 +70,9 @@ int check_perm(uint64_t K, uint32_t S, uint32_t B, const uint16_t *perm, char *e
     return RGX_OK;
 }
 
-size_t host_threads() { return std::min<size_t>(16, std::max<size_t>(1, std::thread::hardware_concurrency())); }
+size_t qtl_host_threads() { return std::min<size_t>(16, std::max<size_t>(1, std::thread::hardware_concurrency())); }
+
+namespace {
 
 long double digamma_l(long double x) {
     long double acc = 0.0L;
@@ -129,6 +134,33 @@ int beta_fit_l(const double *p, uint32_t n, long double &a, long double &b) {
     return 1;
 }
 
+}  // namespace
+
+// One series of B + 1 |r| values (a row's, a group's): n_ge and p_perm, then -- when the series has pairs -- the beta approximation of the p of
+// b = 1 .. B and p_beta at best_r.  p: room for B doubles.  The sums are in ascending b, so the result does not depend on who runs it.
+void qtl_series_finish(const double *row, uint32_t B, double best_r, uint32_t dof, bool has_pairs, double *p, uint32_t &n_ge_out, double &p_perm,
+                       double &shape1, double &shape2, double &p_beta, uint8_t &status) {
+    const uint64_t top = qtl_abs_bits(row[0]);
+    uint32_t n_ge = 0;
+    for (uint32_t b = 1; b <= B; ++b) n_ge += qtl_abs_bits(row[b]) >= top;
+    n_ge_out = n_ge;
+    p_perm = (double)(n_ge + 1) / (double)(B + 1);
+    shape1 = shape2 = p_beta = NAN; status = 2;
+    if (!has_pairs) return;
+    for (uint32_t b = 1; b <= B; ++b) {
+        const double pb = rgx_qtl_pvalue(rgx_qtl_tstat(row[b], dof), dof);
+        p[b - 1] = pb < DBL_MIN ? DBL_MIN : pb > 1.0 - 0x1p-53 ? 1.0 - 0x1p-53 : pb;
+    }
+    long double a, b2;
+    status = (uint8_t)beta_fit_l(p, B, a, b2);
+    if (status == 2) return;
+    shape1 = (double)a; shape2 = (double)b2;
+    const double x = rgx_qtl_pvalue(rgx_qtl_tstat(best_r, dof), dof);
+    p_beta = (double)betainc_l(x, shape1, shape2);
+}
+
+namespace {
+
 // n_ge, p_perm, the verdict counts and the tile count of a result whose arrays from steps (1)-(6) and perm_r, best_* are in place; then the beta
 // approximation, rows shared among the host's threads (a row is one task: its sums do not depend on who runs it)
 int perm_finish(rgx_qtl_perm_result *q, bool device, char *err, size_t errlen) {
@@ -141,30 +173,13 @@ int perm_finish(rgx_qtl_perm_result *q, bool device, char *err, size_t errlen) {
     }
     const double t0 = now_ms();
     try {
-        WorkerPool pool(K * B < 4096 ? 1 : host_threads());
+        WorkerPool pool(K * B < 4096 ? 1 : qtl_host_threads());
         const uint64_t chunk = 16, n_tasks = (K + chunk - 1) / chunk;
         pool.run((size_t)n_tasks, [&](size_t task) {
             std::vector<double> p(B);
-            for (uint64_t k = task * chunk; k < K && k < (task + 1) * chunk; ++k) {
-                const double *row = q->perm_r + k * ((size_t)B + 1);
-                const uint64_t top = qtl_abs_bits(row[0]);
-                uint32_t n_ge = 0;
-                for (uint32_t b = 1; b <= B; ++b) n_ge += qtl_abs_bits(row[b]) >= top;
-                q->n_ge[k] = n_ge;
-                q->p_perm[k] = (double)(n_ge + 1) / (double)(B + 1);
-                q->beta_shape1[k] = q->beta_shape2[k] = q->p_beta[k] = NAN; q->beta_status[k] = 2;
-                if (!q->n_cis[k]) continue;
-                for (uint32_t b = 1; b <= B; ++b) {
-                    const double pb = rgx_qtl_pvalue(rgx_qtl_tstat(row[b], dof), dof);
-                    p[b - 1] = pb < DBL_MIN ? DBL_MIN : pb > 1.0 - 0x1p-53 ? 1.0 - 0x1p-53 : pb;
-                }
-                long double a, b2;
-                q->beta_status[k] = (uint8_t)beta_fit_l(p.data(), B, a, b2);
-                if (q->beta_status[k] == 2) continue;
-                q->beta_shape1[k] = (double)a; q->beta_shape2[k] = (double)b2;
-                const double x = rgx_qtl_pvalue(rgx_qtl_tstat(q->best_r[k], dof), dof);
-                q->p_beta[k] = (double)betainc_l(x, q->beta_shape1[k], q->beta_shape2[k]);
-            }
+            for (uint64_t k = task * chunk; k < K && k < (task + 1) * chunk; ++k)
+                qtl_series_finish(q->perm_r + k * ((size_t)B + 1), B, q->best_r[k], dof, q->n_cis[k] != 0, p.data(), q->n_ge[k], q->p_perm[k],
+                                  q->beta_shape1[k], q->beta_shape2[k], q->p_beta[k], q->beta_status[k]);
         });
     } catch (const std::exception &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory or threads for the beta approximation\n"); }
     q->ms_beta = now_ms() - t0;
@@ -299,7 +314,7 @@ extern "C" int rgx_cohort_qtl_permute(rgx_cohort *co, const rgx_pheno_table *ph,
     std::lock_guard<std::mutex> lock(co->mu);
     const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
     int rc = check_qtl(a, err, errlen);
-    if (rc == RGX_OK) rc = check_perm(ph->n_rows, ph->n_samples, n_perm, perm, err, errlen);
+    if (rc == RGX_OK) rc = check_perm(ph->n_rows, "rows", ph->n_samples, n_perm, perm, err, errlen);
     if (rc != RGX_OK) return rc;
     PermRun p(co, a, n_perm, perm, err, errlen);
     rc = p.run.open();
@@ -320,7 +335,7 @@ extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_
     const double t0 = now_ms();
     const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
     int rc = check_qtl(a, err, errlen);
-    if (rc == RGX_OK) rc = check_perm(ph->n_rows, ph->n_samples, n_perm, perm, err, errlen);
+    if (rc == RGX_OK) rc = check_perm(ph->n_rows, "rows", ph->n_samples, n_perm, perm, err, errlen);
     if (rc != RGX_OK) return rc;
     QtlHost h;
     rc = qtl_host_prepare(a, h, err, errlen);
@@ -332,7 +347,7 @@ extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_
     if (V) { memcpy(q->gg, h.gg.data(), (size_t)V * 8); memcpy(q->variant_verdict, h.verdict.data(), V); }
     q->n_pairs = h.P;
     try {
-        WorkerPool pool(h.P * ((uint64_t)B + 1) * S < (1u << 20) ? 1 : host_threads());
+        WorkerPool pool(h.P * ((uint64_t)B + 1) * S < (1u << 20) ? 1 : qtl_host_threads());
         pool.run((size_t)K, [&](size_t k) {
             std::vector<double> yp(S);
             const double *y = h.Y.data() + k * S;

@@ -27,6 +27,15 @@ int qtl_host_prepare(const QtlArgs &a, QtlHost &h, char *err, size_t errlen);
 // the continued fraction of the incomplete beta function at (a, b, x), for rgx_qtl_pvalue and rgx_qtl_betainc
 long double qtl_beta_cf(long double a, long double b, long double x);
 
+
+// What the permutation pass (cohort_qtl_perm.cpp, where they are defined) shares with the grouped pass (cohort_qtl_group.cpp).
+// the permutations as the host can judge them; n_series of `series` ("rows", "groups") get B + 1 values each
+int check_perm(uint64_t n_series, const char *series, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen);
+size_t qtl_host_threads();
+// one series of B + 1 |r| values: n_ge, p_perm and, when the series has pairs, the beta approximation with p_beta at best_r; p: room for B doubles
+void qtl_series_finish(const double *row, uint32_t B, double best_r, uint32_t dof, bool has_pairs, double *p, uint32_t &n_ge, double &p_perm,
+                       double &shape1, double &shape2, double &p_beta, uint8_t &status);
+
 // One device run, as the stages rgx_cohort_qtl_nominal is made of.  The caller holds the cohort's lock and has checked the arguments; every stage
 // enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
 struct QtlRun {

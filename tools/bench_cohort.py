@@ -35,6 +35,10 @@
                     100000), beside rgx_cohort_qtl_nominal_host; the pairs P, P S fused multiply-adds over ms_pairs as GFMA/s (and the 4,096 S per tile that were issued), and whether every
                     device run was identical to the others and to the twin in every array as bit patterns
 
+  --group           rgx_cohort_qtl_permute_grouped on --qtl's planted tables with --perms B permutations, the rows grouped in runs of
+                    four (the planted table has no clusters), beside rgx_cohort_qtl_permute in the same process on the same inputs: --reps warm calls
+                    of each behind a first one; ms_products, ms_beta, ms_perm, tiles and fill, the bytes copied home, the ratio of the warm
+                    ms_products beside the spread of the ungrouped calls; every group checked as the maximum of its members
   --perm            rgx_cohort_qtl_permute (ms_perm, ms_residual, ms_products, ms_beta) on --qtl's planted tables with --perms B
                     permutations (default 1000, seed 0): first and warm calls; P (B + 1) S fused multiply-adds of the contract over ms_products as
                     GFMA/s, the 4,096 S per tile that were issued, the tile fill; rgx_cohort_qtl_permute_host where its P (B + 1) S stay below
@@ -561,6 +565,68 @@ def part_perm(a):
     co.close()
 
 
+GROUP_ARRAYS = ("variant_verdict", "yy", "gg", "n_cis", "grp_begin", "grp_row", "group_n_cis", "perm_r", "best_row", "best_variant", "best_r",
+                "best_slope", "n_ge", "p_perm", "beta_shape1", "beta_shape2", "p_beta", "beta_status")
+
+
+def same_group(a, b):
+    def bits(x):
+        x = np.ascontiguousarray(x)
+        return x.view(np.uint64) if x.dtype == np.float64 else x
+    return a.n_pairs == b.n_pairs and all(np.array_equal(bits(getattr(a, k)), bits(getattr(b, k))) for k in GROUP_ARRAYS)
+
+
+def part_group(a):
+    """rgx_cohort_qtl_permute_grouped beside rgx_cohort_qtl_permute in one process on the same inputs; the planted table has no clusters, so its
+    groups are runs of four rows."""
+    import regtools_amd
+    from regtools_amd import cohort
+    co = regtools_amd.Cohort(ctx=regtools_amd.Context(0))
+    for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
+        S, K, V = [int(x) for x in size.lower().split("x")]
+        ph, regions, pos, dosage, pcs, n_cov = planted_qtl_inputs(a, co, S, K, V)
+        B = a.perms
+        perms = cohort.qtl_permutations(S, B, 0)
+        groups, G = (np.arange(K) // 4).astype(np.uint32), (K + 3) // 4
+        tail = (np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None, a.window)
+        line = {"part": "group", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "window": a.window, "perms": B, "groups": G}
+        flat = [co.qtl_permute(ph, regions, *tail, perms=perms) for _ in range(a.reps + 1)]
+        runs = [co.qtl_permute_grouped(ph, regions, groups, G, *tail, perms=perms) for _ in range(a.reps + 1)]
+        warm_flat, warm = [q.ms_products for q in flat[1:]], [q.ms_products for q in runs[1:]]
+        P, tiles = runs[0].n_pairs, runs[0].n_tiles
+        fmas = P * (B + 1) * S
+        ub, gb = np.ascontiguousarray(flat[0].perm_r).view(np.uint64), np.ascontiguousarray(runs[0].perm_r).view(np.uint64)
+        pad = np.zeros(((-K) % 4, B + 1), np.uint64)
+        line.update({"pairs": P, "groups_with_pairs": int((runs[0].group_n_cis > 0).sum()), "ms_perm": [round(q.ms_perm, 3) for q in runs],
+                     "ms_residual": [round(q.ms_residual, 3) for q in runs], "ms_products": [round(q.ms_products, 3) for q in runs],
+                     "ms_beta": [round(q.ms_beta, 1) for q in runs], "ms_products_best_warm": round(min(warm), 3), "fmas": fmas,
+                     "tiles": tiles, "tile_fill": round(P * (B + 1) / (4096.0 * tiles), 3) if tiles else None,
+                     "GFMA_per_s_over_ms_products": round(fmas / min(warm) / 1e6, 1) if min(warm) > 0 else None,
+                     "bytes_home": int(G * (B + 1) * 8 + G * 24 + K * 12 + V * 9 + 32),
+                     "ungrouped_ms_products": [round(q.ms_products, 3) for q in flat], "ungrouped_ms_beta": [round(q.ms_beta, 1) for q in flat],
+                     "ungrouped_ms_perm": [round(q.ms_perm, 3) for q in flat], "ungrouped_tiles": flat[0].n_tiles,
+                     "ungrouped_bytes_home": int(K * (B + 1) * 8 + K * 32 + V * 9 + 32),
+                     "ungrouped_warm_spread": [round(min(warm_flat), 3), round(max(warm_flat), 3)],
+                     "ratio_products_best_warm": round(min(warm) / min(warm_flat), 4),
+                     "ratio_products_median_warm": round(float(np.median(warm)) / float(np.median(warm_flat)), 4),
+                     "ratio_beta_median_warm": round(float(np.median([q.ms_beta for q in runs[1:]])) / float(np.median([q.ms_beta for q in flat[1:]])), 4),
+                     "groups_over_rows": round(G / K, 4),
+                     "max_identity": bool(np.array_equal(gb, np.concatenate([ub, pad]).reshape(G, 4, B + 1).max(axis=1))),
+                     "identical_every_time": bool(all(same_group(runs[0], q) for q in runs[1:]))})
+        assert line["identical_every_time"], "two device runs differ"
+        assert line["max_identity"], "a group is not the maximum of its members"
+        if not a.no_host and fmas <= a.host_fmas:
+            h = cohort.qtl_permute_grouped_host(ph, regions, groups, G, *tail, perms=perms)
+            line.update({"ms_perm_host": round(h.ms_perm, 1), "ms_products_host": round(h.ms_products, 1), "ms_beta_host": round(h.ms_beta, 1),
+                         "identical_to_host": bool(same_group(runs[0], h))})
+            assert line["identical_to_host"], "the device's grouped pass differs from the host twin's"
+            h.close()
+        for q in runs + flat:
+            q.close()
+        print(json.dumps(line), flush=True)
+    co.close()
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -620,6 +686,7 @@ def main():
     ap.add_argument("--pcs", action="store_true", help="the principal component part, alone")
     ap.add_argument("--qtl", action="store_true", help="the sQTL scan part, alone")
     ap.add_argument("--perm", action="store_true", help="the sQTL permutation part, alone")
+    ap.add_argument("--group", action="store_true", help="the grouped sQTL permutation part beside the ungrouped one, alone")
     ap.add_argument("--perms", type=int, default=1000, help="--perm: permutations")
     ap.add_argument("--host-fmas", type=float, default=2e11, help="--perm: the twin runs when its fused multiply-adds stay below this")
     ap.add_argument("--n-cov", type=int, default=10, help="--qtl: principal components taken as covariates (clipped to the samples less three)")
@@ -646,6 +713,8 @@ def main():
         return part_qtl(a)
     if a.perm:
         return part_perm(a)
+    if a.group:
+        return part_group(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
