@@ -1,7 +1,8 @@
 // cohort_qtl_perm.cpp -- the permutation pass of the cohort's cis-sQTL scan: rgx_cohort_qtl_permute (device), its host twin
 // rgx_cohort_qtl_permute_host, rgx_qtl_permutations, the digamma, trigamma and incomplete beta functions, the beta fit and the text (contract in
 // include/regtools_amd.h; FastQTL's --permute and tensorQTL's map_cis, which the reference does not contain).  Device side: qtl_perm_kernels.hip
-// behind QtlRun's shared stages (qtl_run.h); arithmetic: qtl_core.h.
+// behind QtlRun's shared stages (qtl_run.h); arithmetic: qtl_core.h.  What is defined here over SERIES -- PermRun, perm_finish, the twin's
+// qtl_series_products -- is the grouped pass's too (cohort_qtl_group.cpp), where a series is a group; here it is table row k alone.
 //   QtlRun: inputs in HBM -> residuals Y, G with yy, gg and the verdicts -> the usable variants compacted -> Gt sample-major -> per row its range
 //   -> the permutations sample-major in HBM -> one workgroup per (row, 64 permutations): perm_r -> a thread per row: the best pair of permutation 0
 //   -> ONE wait, the copies back -> on the host: n_ge, p_perm, the beta approximation
@@ -12,37 +13,14 @@
 
 namespace {
 
-// One block, every array 16-byte aligned.
-struct PermLayout { size_t yy, gg, perm_r, best_r, best_slope, p_perm, shape1, shape2, p_beta, n_cis, best_variant, n_ge, verdict, status, bytes; };
-PermLayout perm_layout(uint64_t K, uint32_t V, uint32_t B) {
-    PermLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    L.yy = take((size_t)K * 8); L.gg = take((size_t)V * 8); L.perm_r = take((size_t)K * ((size_t)B + 1) * 8);
-    L.best_r = take((size_t)K * 8); L.best_slope = take((size_t)K * 8); L.p_perm = take((size_t)K * 8); L.shape1 = take((size_t)K * 8);
-    L.shape2 = take((size_t)K * 8); L.p_beta = take((size_t)K * 8);
-    L.n_cis = take((size_t)K * 4); L.best_variant = take((size_t)K * 4); L.n_ge = take((size_t)K * 4); L.verdict = take((size_t)V);
-    L.status = take((size_t)K);
-    L.bytes = o + 16;
-    return L;
-}
-struct PermBox { rgx_qtl_perm_result q; void *block; size_t block_cap; bool pinned; };
-
 rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, uint32_t B, bool pinned) {
-    PermBox *box = (PermBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    const PermLayout L = perm_layout(K, V, B);
-    box->pinned = pinned;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    uint8_t *b = (uint8_t *)box->block;
-    rgx_qtl_perm_result *q = &box->q;
+    rgx_qtl_perm_result *q = result_alloc<rgx_qtl_perm_result>(pinned, [&](rgx_qtl_perm_result &r, BlockTake &take) {
+        take(r.yy, K); take(r.gg, V); take(r.perm_r, K * ((size_t)B + 1)); take(r.best_r, K); take(r.best_slope, K); take(r.p_perm, K);
+        take(r.beta_shape1, K); take(r.beta_shape2, K); take(r.p_beta, K); take(r.n_cis, K); take(r.best_variant, K); take(r.n_ge, K);
+        take(r.variant_verdict, V); take(r.beta_status, K);
+    });
+    if (!q) return nullptr;
     q->n_rows = K; q->n_samples = S; q->n_variants = V; q->n_cov = n_cov; q->dof = S - n_cov - 2; q->n_perm = B;
-    q->yy = (double *)(b + L.yy); q->gg = (double *)(b + L.gg); q->perm_r = (double *)(b + L.perm_r); q->best_r = (double *)(b + L.best_r);
-    q->best_slope = (double *)(b + L.best_slope); q->p_perm = (double *)(b + L.p_perm); q->beta_shape1 = (double *)(b + L.shape1);
-    q->beta_shape2 = (double *)(b + L.shape2); q->p_beta = (double *)(b + L.p_beta);
-    q->n_cis = (uint32_t *)(b + L.n_cis); q->best_variant = (uint32_t *)(b + L.best_variant); q->n_ge = (uint32_t *)(b + L.n_ge);
-    q->variant_verdict = b + L.verdict; q->beta_status = b + L.status;
     return q;
 }
 
@@ -159,109 +137,148 @@ void qtl_series_finish(const double *row, uint32_t B, double best_r, uint32_t do
     p_beta = (double)betainc_l(x, shape1, shape2);
 }
 
-namespace {
+void qtl_series_products(const QtlHost &h, uint32_t S, uint32_t B, const uint16_t *perm, const uint32_t *rows, uint32_t n, double *series,
+                         uint32_t *best_row, uint32_t &best_variant, double &best_r, double &best_slope) {
+    std::vector<double> yp(S);
+    std::vector<uint64_t> top((size_t)B + 1, 0);
+    if (best_row) *best_row = RGX_NO_PAIR;
+    best_variant = RGX_NO_PAIR; best_r = 0.0; best_slope = 0.0;
+    // members in ascending row, variants in ascending order: a strictly larger |r| alone replaces, so the earliest of equals stays
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t k = rows[i];
+        const double *y = h.Y.data() + (size_t)k * S;
+        for (uint32_t b = 0; b <= B && h.cnt[k]; ++b) {
+            const uint16_t *pb = perm + (size_t)b * S;
+            for (uint32_t s = 0; s < S; ++s) yp[s] = y[pb[s]];
+            for (uint32_t j = 0; j < h.cnt[k]; ++j) {
+                const uint32_t v = h.u_var[h.lo[k] + j]; const double *x = h.G.data() + (size_t)v * S;
+                double acc = 0.0;
+                for (uint32_t s = 0; s < S; ++s) acc = qtl_fma(yp[s], x[s], acc);
+                const double r = qtl_r(acc, h.yy[k], h.gg[v]);
+                const uint64_t bits = qtl_abs_bits(r);
+                if (!b && (best_variant == RGX_NO_PAIR || bits > top[0])) {
+                    if (best_row) *best_row = k;
+                    best_variant = v; best_r = r; best_slope = qtl_slope(acc, h.gg[v]);
+                }
+                if (bits > top[b]) top[b] = bits;
+            }
+        }
+    }
+    memcpy(series, top.data(), ((size_t)B + 1) * 8);
+}
 
-// n_ge, p_perm, the verdict counts and the tile count of a result whose arrays from steps (1)-(6) and perm_r, best_* are in place; then the beta
-// approximation, rows shared among the host's threads (a row is one task: its sums do not depend on who runs it)
-int perm_finish(rgx_qtl_perm_result *q, bool device, char *err, size_t errlen) {
-    const uint64_t K = q->n_rows; const uint32_t B = q->n_perm, S = q->n_samples, dof = q->dof;
+template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen) {
+    const Series sr = series_of(q);
+    const uint64_t K = q->n_rows, N = sr.n; const uint32_t B = q->n_perm, S = q->n_samples, dof = q->dof;
     for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
+    for (uint64_t k = 0; k < K; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], S);
     const uint64_t p_tiles = ((uint64_t)B + 1 + kQtlTile - 1) / kQtlTile;
-    for (uint64_t k = 0; k < K; ++k) {
-        q->n_flat_rows += !qtl_enough(q->yy[k], S);
-        if (device) q->n_tiles += p_tiles * (((uint64_t)q->n_cis[k] + kQtlTile - 1) / kQtlTile);
+    for (uint64_t g = 0; g < N; ++g) {
+        const uint32_t m_end = sr.begin ? sr.begin[g + 1] : (uint32_t)g + 1;
+        uint64_t n = 0;
+        for (uint32_t m = sr.begin ? sr.begin[g] : (uint32_t)g; m < m_end; ++m) {
+            const uint32_t c = q->n_cis[sr.row ? sr.row[m] : m];
+            n += c;
+            if (device) q->n_tiles += p_tiles * (((uint64_t)c + kQtlTile - 1) / kQtlTile);
+        }
+        if (sr.pairs) { sr.pairs[g] = n; q->n_pairs += n; }
     }
     const double t0 = now_ms();
     try {
-        WorkerPool pool(K * B < 4096 ? 1 : qtl_host_threads());
-        const uint64_t chunk = 16, n_tasks = (K + chunk - 1) / chunk;
+        WorkerPool pool(N * B < 4096 ? 1 : qtl_host_threads());
+        const uint64_t chunk = 16, n_tasks = (N + chunk - 1) / chunk;
         pool.run((size_t)n_tasks, [&](size_t task) {
             std::vector<double> p(B);
-            for (uint64_t k = task * chunk; k < K && k < (task + 1) * chunk; ++k)
-                qtl_series_finish(q->perm_r + k * ((size_t)B + 1), B, q->best_r[k], dof, q->n_cis[k] != 0, p.data(), q->n_ge[k], q->p_perm[k],
-                                  q->beta_shape1[k], q->beta_shape2[k], q->p_beta[k], q->beta_status[k]);
+            for (uint64_t g = task * chunk; g < N && g < (task + 1) * chunk; ++g)
+                qtl_series_finish(q->perm_r + g * ((size_t)B + 1), B, q->best_r[g], dof, (sr.pairs ? sr.pairs[g] : q->n_cis[g]) != 0, p.data(),
+                                  q->n_ge[g], q->p_perm[g], q->beta_shape1[g], q->beta_shape2[g], q->p_beta[g], q->beta_status[g]);
         });
     } catch (const std::exception &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory or threads for the beta approximation\n"); }
     q->ms_beta = now_ms() - t0;
     return RGX_OK;
 }
+template int perm_finish(rgx_qtl_perm_result *, bool, char *, size_t);
+template int perm_finish(rgx_qtl_group_result *, bool, char *, size_t);
 
-// The device run: QtlRun's shared stages with the permutation stage behind them.
-struct PermRun {
-    QtlRun run; uint32_t B; const uint16_t *perm; size_t ldp;
-    std::vector<uint16_t> permT;
-    uint16_t *d_permT = nullptr; double *perm_r = nullptr, *best_r = nullptr, *best_slope = nullptr; uint32_t *best_u = nullptr, *best_variant = nullptr;
-
-    PermRun(rgx_cohort *co, const QtlArgs &a, uint32_t B_, const uint16_t *perm_, char *err, size_t errlen)
-        : run(co, a, err, errlen), B(B_), perm(perm_), ldp(((size_t)B_ + 1 + kQtlTile - 1) / kQtlTile * kQtlTile) { run.best_only = true; }
-
-    // 5. the permutations sample-major in HBM, the products, the best pairs
-    int products() {
-        rgx_cohort *co = run.co; char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
-        const uint32_t K = run.K, S = run.S;
-        if ((uint64_t)K * (ldp / kQtlTile) > 0x7fffffffull) return fail(err, errlen, RGX_ERR_ARG,
-            "regtools_amd: %u rows x %zu blocks of 64 permutations are more than 2^31 - 1 workgroups\n", K, ldp / kQtlTile);
-        try { permT.assign((size_t)S * ldp, 0); }
-        catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for %u permutations of %u samples\n", B, S); }
-        for (uint32_t b = 0; b <= B; ++b) for (uint32_t s = 0; s < S; ++s) permT[(size_t)s * ldp + b] = perm[(size_t)b * S + s];
-        const size_t n_out = (size_t)K * ((size_t)B + 1);
-        if (co->qp_in.ensure(permT.size() * 2 + 256) != hipSuccess || co->qp_out.ensure(n_out * 8 + (size_t)K * 24 + 256) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %u permutations of %u rows\n", B, K); }
-        Carve in(co->qp_in);
-        d_permT = in.take<uint16_t>(permT.size());
-        CARVE_TRY(in, "sQTL permutation");
-        Carve o(co->qp_out);
-        perm_r = o.take<double>(n_out); best_r = o.take<double>(K); best_slope = o.take<double>(K); best_u = o.u32(K); best_variant = o.u32(K);
-        CARVE_TRY(o, "sQTL permutation result");
-        HIP_TRY(hipMemcpyAsync(d_permT, permT.data(), permT.size() * 2, hipMemcpyHostToDevice, st));
-        run.mark("permutations in HBM");
-        HIP_TRY(hipEventRecord(run.ev[2], st));
-        launch_qtl_perm(run.Y, K, S, d_permT, ldp, B + 1, run.Gt, run.ldg, run.lo, run.count, run.yy, run.u_gg, perm_r, best_u, st);
-        run.mark("permuted products");
-        launch_qtl_perm_best(run.Y, run.G, K, S, best_u, run.u_var, run.yy, run.gg, best_variant, best_r, best_slope, st);
-        HIP_TRY(hipEventRecord(run.ev[3], st));
-        run.mark("best pairs");
-        return RGX_OK;
-    }
-    // 6. the copies back behind the call's one wait, then the host's part
-    int finish(rgx_qtl_perm_result **out) {
-        char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
-        const uint32_t K = run.K, V = run.V;
-        rgx_qtl_perm_result *q = perm_alloc(K, run.S, V, run.a.n_cov, B, /*pinned=*/true);
-        if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE,
-            "regtools_amd: no memory for the result of %u rows and %u permutations\n", K, B); }
-        uint64_t h[4] = {0, 0, 0, 0};
-        hipError_t e_ = hipMemcpyAsync(q->yy, run.yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-        auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
-        copy(q->gg, run.gg, (size_t)V * 8); copy(q->variant_verdict, run.verdict, V); copy(q->n_cis, run.count, (size_t)K * 4);
-        copy(q->perm_r, perm_r, (size_t)K * ((size_t)B + 1) * 8); copy(q->best_r, best_r, (size_t)K * 8); copy(q->best_slope, best_slope, (size_t)K * 8);
-        copy(q->best_variant, best_variant, (size_t)K * 4); copy(h, run.head, 32);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
-        float ms_res = 0, ms_pr = 0;
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, run.ev[0], run.ev[1]);
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, run.ev[2], run.ev[3]);
-        if (e_ != hipSuccess) { rgx_cohort_qtl_perm_free(q); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the sQTL permutation pass\n",
-            hipGetErrorString(e_)); }
-        run.mark("copies");
-        int rc = bad_flags((const uint32_t *)(h + 2), K, err, errlen);
-        if (rc == RGX_OK) { q->n_pairs = h[0]; rc = perm_finish(q, /*device=*/true, err, errlen); }
-        if (rc != RGX_OK) { rgx_cohort_qtl_perm_free(q); return rc; }
-        q->ms_residual = ms_res; q->ms_products = ms_pr; q->ms_perm = now_ms() - run.t0;
-        *out = q;
-        return RGX_OK;
-    }
-};
-
-}  // namespace
-
-extern "C" void rgx_cohort_qtl_perm_free(rgx_qtl_perm_result *q) {
-    if (!q) return;
-    PermBox *box = (PermBox *)q;                                       // q is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
+int PermRun::launch() {
+    int rc = run.open();
+    if (rc == RGX_OK) rc = run.residuals();
+    if (rc == RGX_OK) rc = run.compact();
+    if (rc == RGX_OK) rc = run.plan_launch();
+    if (rc == RGX_OK) rc = products();
+    return rc;
 }
+
+int PermRun::products() {
+    rgx_cohort *co = run.co; char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
+    const uint32_t S = run.S, N = n_series;
+    if ((uint64_t)N * (ldp / kQtlTile) > 0x7fffffffull) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: %u %s x %zu blocks of 64 permutations are more than 2^31 - 1 workgroups\n", N, series, ldp / kQtlTile);
+    try { permT.assign((size_t)S * ldp, 0); }
+    catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for %u permutations of %u samples\n", B, S); }
+    for (uint32_t b = 0; b <= B; ++b) for (uint32_t s = 0; s < S; ++s) permT[(size_t)s * ldp + b] = perm[(size_t)b * S + s];
+    const size_t n_out = (size_t)N * ((size_t)B + 1), n_begin = mem ? (size_t)N + 1 : 0, n_mem = mem ? mem->row.size() : 0;
+    if (co->qp_in.ensure(permT.size() * 2 + (n_begin + n_mem) * 4 + 256) != hipSuccess ||
+        co->qp_out.ensure(n_out * 8 + (size_t)N * (mem ? 28 : 24) + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %u permutations of %u %s\n", B, N, series); }
+    Carve in(co->qp_in);
+    d_permT = in.take<uint16_t>(permT.size());
+    if (mem) { d_begin = in.u32(n_begin); d_row = in.u32(n_mem); }
+    CARVE_TRY(in, mem ? "grouped sQTL permutation" : "sQTL permutation");
+    Carve o(co->qp_out);
+    perm_r = o.take<double>(n_out); best_r = o.take<double>(N); best_slope = o.take<double>(N); best_u = o.u32(N); best_variant = o.u32(N);
+    if (mem) best_row = o.u32(N);
+    CARVE_TRY(o, mem ? "grouped sQTL permutation result" : "sQTL permutation result");
+    HIP_TRY(hipMemcpyAsync(d_permT, permT.data(), permT.size() * 2, hipMemcpyHostToDevice, st));
+    if (mem) { HIP_TRY(hipMemcpyAsync(d_begin, mem->begin.data(), n_begin * 4, hipMemcpyHostToDevice, st)); }
+    if (n_mem) { HIP_TRY(hipMemcpyAsync(d_row, mem->row.data(), n_mem * 4, hipMemcpyHostToDevice, st)); }
+    run.mark(mem ? "members + permutations in HBM" : "permutations in HBM");
+    HIP_TRY(hipEventRecord(run.ev[2], st));
+    // (without lists all three of d_begin, d_row and best_row are null: series g is table row g alone)
+    launch_qtl_perm(run.Y, N, S, d_permT, ldp, B + 1, run.Gt, run.ldg, run.lo, run.count, run.yy, run.u_gg, d_begin, d_row, perm_r, best_row, best_u,
+                    st);
+    run.mark(mem ? "grouped permuted products" : "permuted products");
+    launch_qtl_perm_best(run.Y, run.G, N, S, best_row, best_u, run.u_var, run.yy, run.gg, best_variant, best_r, best_slope, st);
+    HIP_TRY(hipEventRecord(run.ev[3], st));
+    run.mark("best pairs");
+    return RGX_OK;
+}
+
+int PermRun::no_result() {
+    return fail(run.err, run.errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result of %u %s and %u permutations\n", n_series, series, B);
+}
+
+template <class R> int PermRun::finish(R *q) {
+    char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
+    const uint32_t K = run.K, V = run.V; const size_t N = n_series;
+    uint64_t h[4] = {0, 0, 0, 0};
+    hipError_t e_ = hipMemcpyAsync(q->yy, run.yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
+    auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+    copy(q->gg, run.gg, (size_t)V * 8); copy(q->variant_verdict, run.verdict, V); copy(q->n_cis, run.count, (size_t)K * 4);
+    copy(q->perm_r, perm_r, N * ((size_t)B + 1) * 8); copy(q->best_r, best_r, N * 8); copy(q->best_slope, best_slope, N * 8);
+    if (mem) copy(series_of(q).best_row, best_row, N * 4);
+    copy(q->best_variant, best_variant, N * 4); copy(h, run.head, 32);
+    if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
+    if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+    float ms_res = 0, ms_pr = 0;
+    if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, run.ev[0], run.ev[1]);
+    if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, run.ev[2], run.ev[3]);
+    if (e_ != hipSuccess) return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the %ssQTL permutation pass\n", hipGetErrorString(e_),
+                                      mem ? "grouped " : "");
+    run.mark("copies");
+    int rc = bad_flags((const uint32_t *)(h + 2), K, err, errlen);
+    if (rc != RGX_OK) return rc;
+    if (!mem) q->n_pairs = h[0];                                      // (the grouped result's is the sum over its groups: perm_finish)
+    rc = perm_finish(q, /*device=*/true, err, errlen);
+    if (rc != RGX_OK) return rc;
+    q->ms_residual = ms_res; q->ms_products = ms_pr; q->ms_perm = now_ms() - run.t0;
+    return RGX_OK;
+}
+template int PermRun::finish(rgx_qtl_perm_result *);
+template int PermRun::finish(rgx_qtl_group_result *);
+
+extern "C" void rgx_cohort_qtl_perm_free(rgx_qtl_perm_result *q) { result_free(q); }
 
 extern "C" int rgx_qtl_permutations(uint32_t n_samples, uint32_t n_perm, uint64_t seed, uint16_t *out, char *err, size_t errlen) {
     const uint32_t S = n_samples;
@@ -316,15 +333,18 @@ extern "C" int rgx_cohort_qtl_permute(rgx_cohort *co, const rgx_pheno_table *ph,
     int rc = check_qtl(a, err, errlen);
     if (rc == RGX_OK) rc = check_perm(ph->n_rows, "rows", ph->n_samples, n_perm, perm, err, errlen);
     if (rc != RGX_OK) return rc;
-    PermRun p(co, a, n_perm, perm, err, errlen);
-    rc = p.run.open();
-    if (rc == RGX_OK) rc = p.run.residuals();
-    if (rc == RGX_OK) rc = p.run.compact();
-    if (rc == RGX_OK) rc = p.run.plan_launch();
-    if (rc == RGX_OK) rc = p.products();
-    if (rc == RGX_OK) rc = p.finish(out);
-    if (rc != RGX_OK && p.run.st) (void)hipStreamSynchronize(p.run.st);   // (the uploads read the caller's arrays and this run's T, Q and permT)
-    return rc;
+    PermRun p(co, a, n_perm, perm, (uint32_t)ph->n_rows, "rows", nullptr, err, errlen);
+    rc = p.launch();
+    rgx_qtl_perm_result *q = nullptr;
+    if (rc == RGX_OK && !(q = perm_alloc(ph->n_rows, ph->n_samples, n_variants, n_cov, n_perm, /*pinned=*/true))) rc = p.no_result();
+    if (rc == RGX_OK) rc = p.finish(q);
+    if (rc != RGX_OK) {
+        if (p.run.st) (void)hipStreamSynchronize(p.run.st);            // (the copies read the caller's arrays and this run's T, Q and permT, and write q)
+        rgx_cohort_qtl_perm_free(q);
+        return rc;
+    }
+    *out = q;
+    return RGX_OK;
 }
 
 extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
@@ -344,32 +364,14 @@ extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_
     rgx_qtl_perm_result *q = perm_alloc(K, S, V, n_cov, B, false);
     if (!q) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the result of %llu rows and %u permutations\n", (unsigned long long)K, B);
     memcpy(q->yy, h.yy.data(), K * 8);
+    memcpy(q->n_cis, h.cnt.data(), K * 4);
     if (V) { memcpy(q->gg, h.gg.data(), (size_t)V * 8); memcpy(q->variant_verdict, h.verdict.data(), V); }
     q->n_pairs = h.P;
     try {
         WorkerPool pool(h.P * ((uint64_t)B + 1) * S < (1u << 20) ? 1 : qtl_host_threads());
         pool.run((size_t)K, [&](size_t k) {
-            std::vector<double> yp(S);
-            const double *y = h.Y.data() + k * S;
-            double *row = q->perm_r + k * ((size_t)B + 1);
-            q->n_cis[k] = h.cnt[k]; q->best_variant[k] = RGX_NO_PAIR; q->best_r[k] = 0.0; q->best_slope[k] = 0.0;
-            for (uint32_t b = 0; b <= B; ++b) {
-                const uint16_t *pb = perm + (size_t)b * S;
-                for (uint32_t s = 0; s < S; ++s) yp[s] = y[pb[s]];
-                uint64_t top = 0;
-                for (uint32_t i = 0; i < h.cnt[k]; ++i) {
-                    const uint32_t v = h.u_var[h.lo[k] + i]; const double *g = h.G.data() + (size_t)v * S;
-                    double acc = 0.0;
-                    for (uint32_t s = 0; s < S; ++s) acc = qtl_fma(yp[s], g[s], acc);
-                    const double r = qtl_r(acc, h.yy[k], h.gg[v]);
-                    const uint64_t bits = qtl_abs_bits(r);
-                    if (!b && (q->best_variant[k] == RGX_NO_PAIR || bits > top)) {
-                        q->best_variant[k] = v; q->best_r[k] = r; q->best_slope[k] = qtl_slope(acc, h.gg[v]);
-                    }
-                    if (bits > top) top = bits;
-                }
-                memcpy(&row[b], &top, 8);
-            }
+            const uint32_t row = (uint32_t)k;
+            qtl_series_products(h, S, B, perm, &row, 1, q->perm_r + k * ((size_t)B + 1), nullptr, q->best_variant[k], q->best_r[k], q->best_slope[k]);
         });
     } catch (const std::exception &) { rgx_cohort_qtl_perm_free(q); return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory or threads for the permutation pass\n"); }
     const double t1 = now_ms();

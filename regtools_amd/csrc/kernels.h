@@ -422,27 +422,18 @@ void launch_qtl_pairs(const double *Yt, size_t ldy, const double *Gt, size_t ldg
                       const double *u_gg, const uint32_t *u_var, double *r, double *slope, uint32_t *pair_variant, hipStream_t st);
 void launch_qtl_best(const double *r, const uint32_t *pair_begin, uint32_t K, uint32_t *best, hipStream_t st);
 
-// ---- the cis-sQTL permutation pass (qtl_perm_kernels.hip; host side in cohort_qtl_perm.cpp) --------------------------------------------------------
-// perm_r (K x n_perm1) = per row and permutation the largest |r| over the row's cis variants, best_u (K) = permutation 0's usable variant (all ones:
-// none).  Y: the row-major residuals; permT: S rows of ldp uint16, ldp a multiple of 64 at or above n_perm1, index 0 behind it; Gt as for the
-// pairs.  K * (ldp / 64) workgroups: the caller keeps that inside 2^31 - 1
-void launch_qtl_perm(const double *Y, uint32_t K, uint32_t S, const uint16_t *permT, size_t ldp, uint32_t n_perm1, const double *Gt, size_t ldg,
-                     const uint32_t *lo, const uint32_t *count, const double *yy, const double *u_gg, double *perm_r, uint32_t *best_u,
-                     hipStream_t st);
-// the winning pair's chain again, a thread per row: the input variant (RGX_NO_PAIR: none), r and slope
-void launch_qtl_perm_best(const double *Y, const double *G, uint32_t K, uint32_t S, const uint32_t *best_u, const uint32_t *u_var, const double *yy,
-                          const double *gg, uint32_t *best_variant, double *best_r, double *best_slope, hipStream_t st);
-
-// ---- the grouped cis-sQTL permutation pass (qtl_group_kernels.hip; host side in cohort_qtl_group.cpp) ----------------------------------------------
-// perm_r (n_groups x n_perm1) = per group and permutation the largest |r| over all members' cis variants; best_row and best_u (n_groups) =
-// permutation 0's table row and usable variant (all ones: none).  grp_begin (n_groups + 1) and grp_row: the member rows, ascending inside a group;
-// the rest as launch_qtl_perm takes it.  n_groups * (ldp / 64) workgroups: the caller keeps that inside 2^31 - 1
-void launch_qtl_perm_group(const double *Y, uint32_t n_groups, uint32_t S, const uint16_t *permT, size_t ldp, uint32_t n_perm1, const double *Gt,
-                           size_t ldg, const uint32_t *lo, const uint32_t *count, const double *yy, const double *u_gg, const uint32_t *grp_begin,
-                           const uint32_t *grp_row, double *perm_r, uint32_t *best_row, uint32_t *best_u, hipStream_t st);
-// the winning pair's chain again, a thread per group: the input variant (RGX_NO_PAIR: none), r and slope
-void launch_qtl_group_best(const double *Y, const double *G, uint32_t n_groups, uint32_t S, const uint32_t *best_row, const uint32_t *best_u,
-                           const uint32_t *u_var, const double *yy, const double *gg, uint32_t *best_variant, double *best_r, double *best_slope,
-                           hipStream_t st);
+// ---- the cis-sQTL permutation pass, ungrouped and grouped (qtl_perm_kernels.hip; host side in cohort_qtl_perm.cpp) ------------------------------
+// perm_r (n_series x n_perm1) = per series and permutation the largest |r| over all members' cis variants; best_row and best_u (n_series) =
+// permutation 0's table row and usable variant (all ones: none).  grp_begin (n_series + 1) and grp_row: the series' member rows, ascending inside
+// a series; a null grp_begin: series g is table row g alone, grp_row is not read and best_row may be null.  Y: the row-major residuals; permT: S
+// rows of ldp uint16, ldp a multiple of 64 at or above n_perm1, index 0 behind it; Gt as for the pairs.  n_series * (ldp / 64) workgroups: the
+// caller keeps that inside 2^31 - 1
+void launch_qtl_perm(const double *Y, uint32_t n_series, uint32_t S, const uint16_t *permT, size_t ldp, uint32_t n_perm1, const double *Gt,
+                     size_t ldg, const uint32_t *lo, const uint32_t *count, const double *yy, const double *u_gg, const uint32_t *grp_begin,
+                     const uint32_t *grp_row, double *perm_r, uint32_t *best_row, uint32_t *best_u, hipStream_t st);
+// the winning pair's chain again, a thread per series: the input variant (RGX_NO_PAIR: none), r and slope; a null best_row: series g is row g
+void launch_qtl_perm_best(const double *Y, const double *G, uint32_t n_series, uint32_t S, const uint32_t *best_row, const uint32_t *best_u,
+                          const uint32_t *u_var, const double *yy, const double *gg, uint32_t *best_variant, double *best_r, double *best_slope,
+                          hipStream_t st);
 
 }  // namespace rgx

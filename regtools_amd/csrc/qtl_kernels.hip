@@ -11,20 +11,16 @@
 //   k_qtl_totals  P and the tile count as 64-bit sums (the 32-bit scans wrap), for the call's one host wait
 //   k_qtl_pairs   one workgroup per (row block, variant tile): 4 x 4 chains per thread in registers, each the contract's acc = fma(Y[k][s],
 //                 G[v][s], acc) in ascending s from +0.0 -- one thread owns a chain from s = 0 to S - 1.  The samples come in slabs of 16 through
-//                 two LDS panels, the next slab's loads in flight under the current slab's FMAs: k_pca_gram's structure and its conflict-free
-//                 16-byte LDS index pattern (pca_kernels.hip).  r and slope are stored where lo[k] <= u < lo[k] + count[k].
+//                 two LDS panels, the next slab's loads in flight under the current slab's FMAs (qtl_tile.h, shared with k_qtl_perm): k_pca_gram's
+//                 structure and its conflict-free 16-byte LDS index pattern (pca_kernels.hip).  r and slope are stored where lo[k] <= u < lo[k] + count[k].
 //   k_qtl_best    a wave per row over its pairs: largest |r|, earliest on ties, by a shuffle reduction on (|r| bits, pair)
 // No atomics, every word has one writer (the two flag words aside: their writers all store 1).  256 threads per workgroup, wave64, FP64 vector
 // FMAs (the f64 MFMA's order of adding its four products is not documented: not used).
-#include "kernels.h"
-#include "qtl_core.h"
+#include "qtl_tile.h"
 
 namespace rgx {
 
 namespace {
-
-constexpr uint32_t kSlab = 16;               // samples per trip through LDS
-constexpr uint32_t kPerThread = kSlab * kQtlTile / 256;   // a thread's entries of one panel of one slab
 
 __device__ __forceinline__ double qtl_halve(double p) {
 #pragma unroll
@@ -188,53 +184,14 @@ __global__ __launch_bounds__(256) void k_qtl_pairs(const double *__restrict__ Yt
                                                    const uint32_t *__restrict__ count, const uint32_t *__restrict__ pair_begin,
                                                    const double *__restrict__ yy, const double *__restrict__ u_gg, const uint32_t *__restrict__ u_var,
                                                    double *__restrict__ r, double *__restrict__ slope, uint32_t *__restrict__ pair_variant) {
-    __shared__ __attribute__((aligned(16))) double A[kSlab][kQtlTile];
-    __shared__ __attribute__((aligned(16))) double B[kSlab][kQtlTile];
     const uint32_t tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
     // the last row block whose first tile is at or in front of this one (it has tiles: the next block's first tile lies behind this one)
     uint32_t b_lo = 0, b_hi = n_blocks;
     while (b_lo + 1 < b_hi) { const uint32_t mid = b_lo + (b_hi - b_lo) / 2; if (tile_begin[mid] <= blockIdx.x) b_lo = mid; else b_hi = mid; }
     const uint32_t blk = b_lo, k0 = blk * kQtlTile, v0 = blk_lo[blk] + (blockIdx.x - tile_begin[blk]) * kQtlTile;
-    const double *ya = Yt + k0 + tid % kQtlTile, *gb = Gt + v0 + tid % kQtlTile;
 
     double acc[4][4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) acc[i][j] = 0.0;
-
-    double va[kPerThread], vb[kPerThread];
-    auto gather = [&](uint32_t s0) {
-#pragma unroll
-        for (uint32_t j = 0; j < kPerThread; ++j) {
-            const uint32_t s = s0 + tid / kQtlTile + 4 * j;
-            va[j] = s < S ? ya[(size_t)s * ldy] : 0.0; vb[j] = s < S ? gb[(size_t)s * ldg] : 0.0;
-        }
-    };
-    gather(0);
-    for (uint32_t s0 = 0; s0 < S; s0 += kSlab) {
-#pragma unroll
-        for (uint32_t j = 0; j < kPerThread; ++j) { A[tid / kQtlTile + 4 * j][tid % kQtlTile] = va[j]; B[tid / kQtlTile + 4 * j][tid % kQtlTile] = vb[j]; }
-        __syncthreads();
-        if (s0 + kSlab < S) gather(s0 + kSlab);              // (the same for the whole workgroup)
-        const uint32_t rows = S - s0 < kSlab ? S - s0 : kSlab;
-        auto step = [&](uint32_t kk) {
-            const double2 a0 = *(const double2 *)&A[kk][2 * ty], a1 = *(const double2 *)&A[kk][32 + 2 * ty];
-            const double2 b0 = *(const double2 *)&B[kk][2 * tx], b1 = *(const double2 *)&B[kk][32 + 2 * tx];
-            const double a[4] = {a0.x, a0.y, a1.x, a1.y}, b[4] = {b0.x, b0.y, b1.x, b1.y};
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) acc[i][j] = qtl_fma(a[i], b[j], acc[i][j]);
-        };
-        if (rows == kSlab) {
-#pragma unroll
-            for (uint32_t kk = 0; kk < kSlab; ++kk) step(kk);
-        } else {
-            for (uint32_t kk = 0; kk < rows; ++kk) step(kk);
-        }
-        __syncthreads();
-    }
+    qtl_tile_product(QtlTileRows{Yt + k0 + tid % kQtlTile, ldy}, Gt + v0 + tid % kQtlTile, ldg, S, acc);
 
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) {

@@ -1,6 +1,7 @@
 // qtl_run.h -- what the nominal cis-sQTL scan (cohort_qtl.cpp) and its permutation pass (cohort_qtl_perm.cpp) share: the arguments and their checks,
-// the host half of the contract (basis, dot64, residual, the twin's steps (1)-(6)) and QtlRun, the device stages both calls are made of.  The
-// functions are defined in cohort_qtl.cpp.
+// the host half of the contract (basis, dot64, residual, the twin's steps (1)-(6)) and QtlRun, the device stages both calls are made of, defined
+// in cohort_qtl.cpp; then what the permutation pass shares with the grouped pass (cohort_qtl_group.cpp), PermRun among it, defined in
+// cohort_qtl_perm.cpp.
 #pragma once
 #include "cohort_internal.h"
 #include "qtl_core.h"
@@ -28,13 +29,55 @@ int qtl_host_prepare(const QtlArgs &a, QtlHost &h, char *err, size_t errlen);
 long double qtl_beta_cf(long double a, long double b, long double x);
 
 
-// What the permutation pass (cohort_qtl_perm.cpp, where they are defined) shares with the grouped pass (cohort_qtl_group.cpp).
+// What the permutation pass (cohort_qtl_perm.cpp, where they are defined) shares with the grouped pass (cohort_qtl_group.cpp).  A SERIES of B + 1
+// values is a table row's, or a group's with its member lists.
 // the permutations as the host can judge them; n_series of `series` ("rows", "groups") get B + 1 values each
 int check_perm(uint64_t n_series, const char *series, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen);
 size_t qtl_host_threads();
 // one series of B + 1 |r| values: n_ge, p_perm and, when the series has pairs, the beta approximation with p_beta at best_r; p: room for B doubles
 void qtl_series_finish(const double *row, uint32_t B, double best_r, uint32_t dof, bool has_pairs, double *p, uint32_t &n_ge, double &p_perm,
                        double &shape1, double &shape2, double &p_beta, uint8_t &status);
+// The twin's products of one series, its members rows[0 .. n) in ascending table row: series[b] = the largest |r| of permutation b over all members'
+// cis variants (+0.0 without pairs), and permutation 0's best pair, RGX_NO_PAIR and +0.0 without one.  best_row may be null.
+void qtl_series_products(const QtlHost &h, uint32_t S, uint32_t B, const uint16_t *perm, const uint32_t *rows, uint32_t n, double *series,
+                         uint32_t *best_row, uint32_t &best_variant, double &best_r, double &best_slope);
+
+// The members of every group in ascending table row.
+struct Members { std::vector<uint32_t> begin, row; };
+// What a series is in each of the two results.  Without lists (begin null) series k is table row k alone and its pairs are n_cis[k].
+struct Series { uint64_t n; const uint32_t *begin, *row; uint64_t *pairs; uint32_t *best_row; };
+inline Series series_of(rgx_qtl_perm_result *q) { return {q->n_rows, nullptr, nullptr, nullptr, nullptr}; }
+inline Series series_of(rgx_qtl_group_result *q) { return {q->n_groups, q->grp_begin, q->grp_row, q->group_n_cis, q->best_row}; }
+// the pair counts of the series (and the grouped result's n_pairs), the verdict counts, the tile count, then qtl_series_finish for every series,
+// sixteen a task among the host's threads; q's arrays from steps (1)-(6), its lists and perm_r, best_* are in place
+template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen);
+
+// A result and the one block its arrays live in.  arrays(q, take) names every array once with its length; it runs twice, to size the block (a
+// running offset, every array 16-byte aligned) and to hand out the pointers.  Page-locked when asked for and possible.
+template <class R> struct ResultBox { R q; void *block; size_t block_cap; bool pinned; };
+struct BlockTake {
+    uint8_t *base; size_t o = 0;
+    template <class T> void operator()(T *&p, size_t n) { if (base) p = (T *)(base + o); o += (n * sizeof(T) + 15) & ~(size_t)15; }
+};
+template <class R, class F> R *result_alloc(bool pinned, F arrays) {
+    ResultBox<R> *box = (ResultBox<R> *)calloc(1, sizeof *box);
+    if (!box) return nullptr;
+    BlockTake size{nullptr};
+    arrays(box->q, size);
+    box->pinned = pinned;
+    box->block = block_take(size.o, box->block_cap, pinned);
+    if (!box->block && pinned) { box->pinned = false; box->block = block_take(size.o, box->block_cap, false); }
+    if (!box->block) { free(box); return nullptr; }
+    BlockTake take{(uint8_t *)box->block};
+    arrays(box->q, take);
+    return &box->q;
+}
+template <class R> void result_free(R *q) {
+    if (!q) return;
+    ResultBox<R> *box = (ResultBox<R> *)q;                              // q is the first member
+    block_give(box->block, box->block_cap, box->pinned);
+    free(box);
+}
 
 // One device run, as the stages rgx_cohort_qtl_nominal is made of.  The caller holds the cohort's lock and has checked the arguments; every stage
 // enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
@@ -147,4 +190,26 @@ struct QtlRun {
     int plan();
     int pairs();
     int finish(rgx_qtl_result **out);
+};
+
+// The device run of the permutation pass, ungrouped (mem null: series k is table row k) or grouped: QtlRun's shared stages with the permutation
+// stage behind them.  `series` ("rows", "groups") is the word the messages use.
+struct PermRun {
+    QtlRun run; uint32_t B; const uint16_t *perm; size_t ldp; uint32_t n_series; const char *series; const Members *mem;
+    std::vector<uint16_t> permT;
+    uint16_t *d_permT = nullptr; uint32_t *d_begin = nullptr, *d_row = nullptr;
+    double *perm_r = nullptr, *best_r = nullptr, *best_slope = nullptr; uint32_t *best_row = nullptr, *best_u = nullptr, *best_variant = nullptr;
+
+    PermRun(rgx_cohort *co, const QtlArgs &a, uint32_t B_, const uint16_t *perm_, uint32_t n_series_, const char *series_, const Members *mem_,
+            char *err, size_t errlen)
+        : run(co, a, err, errlen), B(B_), perm(perm_), ldp(((size_t)B_ + 1 + kQtlTile - 1) / kQtlTile * kQtlTile), n_series(n_series_),
+          series(series_), mem(mem_) { run.best_only = true; }
+    // 1.-5. every stage up to the products and the best pairs, enqueued: no wait
+    int launch();
+    // 5. the member lists and the permutations sample-major in HBM, the products, the best pairs
+    int products();
+    // 6. the copies back into q behind the call's one wait, then the host's part (perm_finish); q stays the caller's
+    template <class R> int finish(R *q);
+    // RGX_ERR_DEVICE: q could not be had
+    int no_result();
 };

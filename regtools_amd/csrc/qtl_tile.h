@@ -1,0 +1,78 @@
+// qtl_tile.h -- the one slab loop of the cis-sQTL product kernels (device only): k_qtl_pairs (qtl_kernels.hip) and k_qtl_perm
+// (qtl_perm_kernels.hip) run it; they differ in where an entry of the A panel comes from, which a small source type says.
+#pragma once
+#include "kernels.h"
+#include "qtl_core.h"
+
+namespace rgx {
+
+constexpr uint32_t kSlab = 16;               // samples per trip through LDS
+constexpr uint32_t kPerThread = kSlab * kQtlTile / 256;   // a thread's entries of one panel of one slab
+
+// The A sources.  load(s): what this thread fetches from HBM for sample s (its column is tid % 64), in flight under the previous slab's FMAs;
+// stage(raw): the double that goes into the panel.  A Raw{} (sample s >= S) must stage without a fault: its value is never multiplied.
+struct QtlTileRows {                         // a column of the sample-major residuals: staged as it is
+    using Raw = double;
+    const double *col; size_t ld;
+    __device__ __forceinline__ Raw load(uint32_t s) const { return col[(size_t)s * ld]; }
+    __device__ __forceinline__ double stage(Raw v) const { return v; }
+};
+struct QtlTilePerms {                        // a column of the sample-major permutation matrix: y[index], y the row's residual in LDS
+    using Raw = uint32_t;
+    const uint16_t *col; size_t ld; const double *y;
+    __device__ __forceinline__ Raw load(uint32_t s) const { return col[(size_t)s * ld]; }
+    __device__ __forceinline__ double stage(Raw i) const { return y[i]; }
+};
+
+// acc[i][j] = the contract's chain over s = 0 .. S - 1 from +0.0 of A[s][a(i)] * B[s][b(j)], a(i) = (i < 2 ? 0 : 32) + 2 * ty + (i & 1) with
+// ty = tid / 16 and b(j) the same of tx = tid % 16, for one tile of 64 x 64: 4 x 4 chains per thread in registers, one thread per chain.  The B
+// panel is gb[s * ldg] (gb: this thread's column of Gt).  The samples come in slabs of 16 through two LDS panels (16,384 B static), the next
+// slab's loads in flight under the current slab's FMAs.  Called by the whole workgroup of 256; it ends behind a barrier, so nothing of the
+// panels -- or of what a_src.stage() reads -- is read once it has returned.
+template <class ASource>
+__device__ __forceinline__ void qtl_tile_product(const ASource &a_src, const double *__restrict__ gb, size_t ldg, uint32_t S, double (&acc)[4][4]) {
+    __shared__ __attribute__((aligned(16))) double A[kSlab][kQtlTile];
+    __shared__ __attribute__((aligned(16))) double B[kSlab][kQtlTile];
+    const uint32_t tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) acc[i][j] = 0.0;
+
+    typename ASource::Raw va[kPerThread]; double vb[kPerThread];
+    auto gather = [&](uint32_t s0) {
+#pragma unroll
+        for (uint32_t j = 0; j < kPerThread; ++j) {
+            const uint32_t s = s0 + tid / kQtlTile + 4 * j;
+            va[j] = s < S ? a_src.load(s) : typename ASource::Raw{}; vb[j] = s < S ? gb[(size_t)s * ldg] : 0.0;
+        }
+    };
+    gather(0);
+    for (uint32_t s0 = 0; s0 < S; s0 += kSlab) {
+#pragma unroll
+        for (uint32_t j = 0; j < kPerThread; ++j) {
+            A[tid / kQtlTile + 4 * j][tid % kQtlTile] = a_src.stage(va[j]); B[tid / kQtlTile + 4 * j][tid % kQtlTile] = vb[j];
+        }
+        __syncthreads();
+        if (s0 + kSlab < S) gather(s0 + kSlab);              // (the same for the whole workgroup)
+        const uint32_t rows = S - s0 < kSlab ? S - s0 : kSlab;
+        auto step = [&](uint32_t kk) {
+            const double2 a0 = *(const double2 *)&A[kk][2 * ty], a1 = *(const double2 *)&A[kk][32 + 2 * ty];
+            const double2 c0 = *(const double2 *)&B[kk][2 * tx], c1 = *(const double2 *)&B[kk][32 + 2 * tx];
+            const double a[4] = {a0.x, a0.y, a1.x, a1.y}, c[4] = {c0.x, c0.y, c1.x, c1.y};
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) acc[i][j] = qtl_fma(a[i], c[j], acc[i][j]);
+        };
+        if (rows == kSlab) {
+#pragma unroll
+            for (uint32_t kk = 0; kk < kSlab; ++kk) step(kk);
+        } else {                                             // (its own loop: a padded step would turn an acc of -0.0 into +0.0)
+            for (uint32_t kk = 0; kk < rows; ++kk) step(kk);
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace rgx

@@ -113,6 +113,24 @@ def two_rows_with(S, n0, n1, seed, window=qc.WINDOW):
     return qc.Case(**dict(c.__dict__, regions=regions, var_pos=pos, window=0))
 
 
+def rows_with(S, counts, seed, window=qc.WINDOW):
+    """two_rows_with for every row: row k reaches the first counts[k] variants (none when 0).  K = len(counts)."""
+    V = max(max(counts), 8)
+    c = qc.simple(S, len(counts), V, 0, seed=seed, window=window, span=4 * window, contigs=1)
+    pos = (1 + np.sort(np.random.default_rng(seed).choice(4 * window, V, replace=False))).astype(np.uint32)
+    regions = np.array([(0, 1, pos[n - 1]) if n else (0, 4 * window + 10, 4 * window + 20) for n in counts], np.uint32)
+    return qc.Case(**dict(c.__dict__, regions=regions, var_pos=pos, window=0))
+
+
+# the smallest table that crosses the slab's tail (S = 17), a variant-tile edge (64 and 65 cis variants) and has members without pairs between
+# members with pairs: singleton groups of it against the ungrouped pass
+MERGED_S, MERGED_COUNTS = 17, (0, 1, 65, 0, 64)
+
+
+def merged_case():
+    return rows_with(MERGED_S, MERGED_COUNTS, seed=1765)
+
+
 # ---- rows without pairs -----------------------------------------------------------------------------------------------------------------------------
 FAR = (1, 4 * qc.WINDOW * 3 + 10 * qc.WINDOW + 5, 4 * qc.WINDOW * 3 + 10 * qc.WINDOW + 300)   # qc.planted's far region for V = 24
 

@@ -96,6 +96,21 @@ def test_singleton_groups_reproduce_the_ungrouped_pass(S, K, V, n_cov):
         assert np.isnan(q.p_beta).any() and (q.beta_status != 2).any()
 
 
+def test_the_ungrouped_twin_is_the_grouped_twin_of_singleton_groups():
+    """One product loop and one finish behind both twins: S = 17, five rows of 0, 1, 65, 0 and 64 cis variants, B = 64, group[k] = k."""
+    c = gc.merged_case()
+    groups, G = gc.singletons(5)
+    q, ung = _twin(c, groups, G, n_perm=64), _ungrouped(c, n_perm=64)
+    assert tuple(ung.n_cis) == gc.MERGED_COUNTS and (ung.variant_verdict == 0).all() and ung.n_samples == 17
+    assert q.perm_r.shape == ung.perm_r.shape == (5, 65) and q.n_ge.shape == ung.n_ge.shape == (5,)
+    gref.same_as_ungrouped(q, ung)                              # (perm_r, best_*, n_ge, p_perm, the shapes and p_beta as bit patterns; best_row)
+    assert q.best_row.tolist() == [gc.NO_PAIR, 1, 2, gc.NO_PAIR, 4]
+    assert (q.n_constant, q.n_explained, q.n_flat_rows, q.n_tiles) == (ung.n_constant, ung.n_explained, ung.n_flat_rows, ung.n_tiles)
+    for g in (0, 3):
+        gref.no_pairs(q, g)
+    assert (q.perm_r[[1, 2, 4], 1:] != q.perm_r[[1, 2, 4], :1]).any() and (q.beta_status[[1, 2, 4]] != 2).all()
+
+
 def _nominal_top(c):
     """(row, variant) of the largest |r| of the whole table by the nominal twin, with the rows and variants that reach the same bits."""
     from regtools_amd import cohort

@@ -1,8 +1,9 @@
-"""The grouped permutation pass of the cis-sQTL scan on the device (rgx_cohort_qtl_permute_grouped: csrc/qtl_group_kernels.hip,
-csrc/cohort_qtl_group.cpp): a workgroup per (group, 64 permutations) that walks the group's members, each member's residual in LDS in turn, the
+"""The grouped permutation pass of the cis-sQTL scan on the device (rgx_cohort_qtl_permute_grouped: k_qtl_perm of csrc/qtl_perm_kernels.hip with
+member lists, csrc/cohort_qtl_group.cpp): a workgroup per (group, 64 permutations) that walks the group's members, each member's residual in LDS in turn, the
 running maximum per permutation in registers across members.  Expectations: the library's host twin in every array of the result as bit patterns;
-the device's own ungrouped pass (singleton groups reproduce it, every group is the maximum of its members); the device's nominal scan at the best
-pair; and the restatement of tests/qtl_group_ref.py (exact fused multiply-adds) at sampled (group, permutation)."""
+the device's own ungrouped pass (singleton groups reproduce it, every group is the maximum of its members) -- the same kernel without its lists, so
+that comparison checks the two ways into it against each other and is no independent evidence; the device's nominal scan at the best pair; and the
+restatement of tests/qtl_group_ref.py (exact fused multiply-adds) at sampled (group, permutation)."""
 import os
 import subprocess
 
@@ -199,6 +200,28 @@ def test_device_against_device(co, S, K, V, n_cov):
     dev, _ = _check(co, c, groups, G, n_perm=7, seed=11)
     gref.max_identity(dev, ung, groups, G)
     _nominal_best(co, c, dev)
+
+
+def test_the_kernel_without_lists_and_with_singleton_lists(co):
+    """One kernel behind both passes: S = 17 (the slab's tail), five rows of 0, 1, 65, 0 and 64 cis variants (a variant-tile edge; members
+    without pairs between members with pairs), B + 1 = 65 (a second tile of permutations), through Cohort.qtl_permute -- no lists on the device
+    -- and through singleton groups -- the lists -- and both against the host twins."""
+    from regtools_amd import cohort
+    c = gc.merged_case()
+    groups, G = gc.singletons(5)
+    dev, twin = _check(co, c, groups, G, n_perm=64, seed=3)
+    ung = _ungrouped(co, c, n_perm=64, seed=3)
+    assert tuple(ung.n_cis) == gc.MERGED_COUNTS and (ung.variant_verdict == 0).all() and ung.perm_r.shape == (5, 65)
+    gref.same_as_ungrouped(dev, ung)
+    assert dev.best_row.tolist() == [gc.NO_PAIR, 1, 2, gc.NO_PAIR, 4] and dev.n_tiles == ung.n_tiles == 2 * (1 + 2 + 1)
+    ung_twin = cohort.qtl_permute_host(cohort.pheno_table_from_rank2(c.rank2), **_args(c, n_perm=64, seed=3))
+    gref.same_as_ungrouped(twin, ung_twin)
+    gref.same_as_ungrouped(dev, ung_twin)
+    assert ung.n_pairs == ung_twin.n_pairs == 130 and ung_twin.n_tiles == 0
+    assert (ung.n_constant, ung.n_explained, ung.n_flat_rows) == (ung_twin.n_constant, ung_twin.n_explained, ung_twin.n_flat_rows)
+    for g in (0, 3):
+        gref.no_pairs(dev, g)
+    assert (dev.perm_r[[1, 2, 4], 1:] != dev.perm_r[[1, 2, 4], :1]).any()
 
 
 def test_larger_run_against_the_ungrouped_pass_and_the_restatement(co):

@@ -1,5 +1,5 @@
-"""The permutation pass of the cis-sQTL scan on the device (rgx_cohort_qtl_permute: csrc/qtl_perm_kernels.hip, csrc/cohort_qtl_perm.cpp): a
-workgroup per (row, 64 permutations) over all the row's tiles of 64 usable variants, the row's residual in LDS, the permuted panel gathered from it.
+"""The permutation pass of the cis-sQTL scan on the device (rgx_cohort_qtl_permute: k_qtl_perm of csrc/qtl_perm_kernels.hip without member
+lists, csrc/cohort_qtl_perm.cpp): a workgroup per (row, 64 permutations) over all the row's tiles of 64 usable variants, the row's residual in LDS, the permuted panel gathered from it.
 Expectations: the library's host twin in every array of the result as bit patterns, the nominal scan's best pair, and the restatement of
 tests/qtl_perm_ref.py (exact fused multiply-adds) at sampled (row, permutation)."""
 import os
