@@ -799,6 +799,42 @@ int  rgx_k_group_by(rgx_ctx *ctx, const uint32_t *d_tid, const uint32_t *d_start
 int  rgx_k_components(rgx_ctx *ctx, uint32_t n_vertices, uint32_t n_edges, const uint32_t *d_a, const uint32_t *d_b, uint32_t *d_label_out,
                       uint32_t *n_rounds, char *err, size_t errlen);
 
+/* The interval kernels of `cis-splice-effects identify / associate` and the two annotate commands, stage by stage (tests): the junction scan
+ * (a11), the window join's pair lists (a9) and `associate`'s pair join on the caller's own junctions, events and windows.  (The variant scan,
+ * a10, has had its entry all along: rgx_variant_windows, below.)  Each runs the half its command runs, on the context's stream, with the
+ * variable-length outputs in scratch that has guard words behind every list: RGX_ERR_DEVICE when a fill pass wrote more than its count pass
+ * counted.  Results are malloc'ed host arrays, freed by the matching *_free. */
+typedef struct rgx_gtf rgx_gtf;
+/* 1: the annotation carries the direct (contig, bin) index, 0: the kernels find a bin's transcripts by binary search (the model builds the
+ * index only while contigs x (largest bin + 1) <= 2^23). */
+int  rgx_gtf_bin_index(const rgx_gtf *g);
+/* a11 as the kernel leaves it: junction i (contig = index into the annotation's contigs or -1, start, end1 = Junction.end + 1, strand byte)
+ * -> flags (bit0 known_donor, bit1 known_acceptor, bit2 known_junction), visits (exon records of its candidate transcripts; form 1 counts all
+ * junctions into visits_total only and leaves visits 0) and its items item_off[i] .. item_off[i + 1]: (kind, a, b) in the order written, kind
+ * 0 = transcript a listed, 1 = exon a-b skipped, 2 = donor a skipped, 3 = acceptor a skipped; duplicates are NOT removed
+ * (rgx_annotate_junctions does that).  keep_single: `junctions annotate -S`.  form: 0 = one wave per junction, 1 = one lane per junction. */
+typedef struct {
+    uint64_t n, visits_total; uint32_t *flags, *visits, *item_off, *item_kind, *item_a, *item_b;
+} rgx_junction_items;
+int  rgx_k_junction_scan(rgx_ctx *ctx, const rgx_gtf *g, uint64_t n, const int32_t *contig, const uint32_t *start, const uint32_t *end1,
+                         const char *strand, int keep_single, int form, rgx_junction_items **out, char *err, size_t errlen);
+void rgx_junction_items_free(rgx_junction_items *r);
+/* n pairs (first[k], window[k]), window-major; n_batches = the batches they were made in (1 for rgx_k_assoc_pairs) */
+typedef struct { uint64_t n; uint32_t n_batches; uint32_t *first, *window; } rgx_pair_list;
+void rgx_pair_list_free(rgx_pair_list *r);
+/* a9: events as DEVICE columns (tid, read pos, read end; sorted by (tid, pos); complete before the call), windows (tid, beg, end) as host
+ * arrays -> pairs (event, window): for window w in order the events with tid == w_tid, rpos < end, rend > beg (signed 32-bit compares) in
+ * event order.  pair_batch: the lists are made in batches of whole windows of at most this many pairs (a larger window is a batch of its own);
+ * 0 = the product's size (2^26, or REGTOOLS_AMD_PAIR_BATCH). */
+int  rgx_k_window_pairs(rgx_ctx *ctx, const uint32_t *d_tid, const uint32_t *d_rpos, const uint32_t *d_rend, uint32_t n_events, uint32_t n_windows,
+                        const int32_t *w_tid, const int32_t *w_beg, const int32_t *w_end, uint64_t pair_batch, rgx_pair_list **out, char *err,
+                        size_t errlen);
+/* `associate`: windows (contig index or -1, cis range [ces, cee]) against junctions bucketed by contig (contig_off: n_contigs + 1 host entries;
+ * start / end in bucket order) -> pairs (junction, window): window w keeps the junctions of its contig whose start or end lies in [ces, cee]. */
+int  rgx_k_assoc_pairs(rgx_ctx *ctx, uint32_t n_windows, const int32_t *w_contig, const uint32_t *w_ces, const uint32_t *w_cee, uint32_t n_contigs,
+                       const uint32_t *contig_off, uint32_t n_junctions, const uint32_t *j_start, const uint32_t *j_end, rgx_pair_list **out,
+                       char *err, size_t errlen);
+
 /* =====================================================================================================
  * `cis-splice-effects identify`.
  * Replaces CisSpliceEffectsIdentifier::identify() + annotate_junctions()
@@ -872,8 +908,7 @@ int  rgx_junctions_annotate(rgx_ctx *ctx, const char *bed_path, const char *fast
 int  rgx_junctions_annotate_opts(rgx_ctx *ctx, const char *bed_path, const char *fasta_path, const char *gtf_path, const char *out_path,
                                  int options, uint64_t *n_rows, char *err, size_t errlen);
 
-/* Stage entry points over a loaded annotation (flat exon/transcript/bin arrays in HBM). */
-typedef struct rgx_gtf rgx_gtf;
+/* Stage entry points over a loaded annotation (flat exon/transcript/bin arrays in HBM; rgx_gtf is declared with the rgx_k_* entries above). */
 int  rgx_gtf_load(rgx_ctx *ctx, const char *gtf_path, rgx_gtf **out, char *err, size_t errlen);   /* GtfParser::load, gtf_parser.cc:257-263 */
 void rgx_gtf_free(rgx_gtf *g);
 int  rgx_gtf_info(const rgx_gtf *g, uint32_t *n_transcripts, uint32_t *n_exons, uint32_t *n_chroms);

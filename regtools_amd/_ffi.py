@@ -64,7 +64,8 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_qtl_permutations", "rgx_cohort_qtl_permute", "rgx_cohort_qtl_permute_host", "rgx_cohort_qtl_perm_free", "rgx_qtl_digamma",
            "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm",
            "rgx_cohort_pheno_groups", "rgx_cohort_qtl_permute_grouped", "rgx_cohort_qtl_permute_grouped_host", "rgx_cohort_qtl_group_free",
-           "rgx_cohort_format_qtl_group"]
+           "rgx_cohort_format_qtl_group",
+           "rgx_gtf_bin_index", "rgx_k_junction_scan", "rgx_junction_items_free", "rgx_pair_list_free", "rgx_k_window_pairs", "rgx_k_assoc_pairs"]
 
 
 class CohortParams(C.Structure):
@@ -187,6 +188,16 @@ class JunctionAnnot(C.Structure):
                 ("n_exons_skipped", C.POINTER(C.c_uint32)), ("n_donors_skipped", C.POINTER(C.c_uint32)), ("tx_off", C.POINTER(C.c_uint32)),
                 ("tx", C.POINTER(C.c_uint32))]
 
+
+class JunctionItems(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("visits_total", C.c_uint64)] + \
+               [(k, C.POINTER(C.c_uint32)) for k in ("flags", "visits", "item_off", "item_kind", "item_a", "item_b")]
+
+
+class PairList(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_batches", C.c_uint32), ("first", C.POINTER(C.c_uint32)), ("window", C.POINTER(C.c_uint32))]
+
+
 _lib = None
 
 
@@ -279,6 +290,15 @@ def lib():
         L.rgx_annotate_junctions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_char_p), P(C.c_uint32), P(C.c_uint32), C.c_char_p,
                                              P(P(JunctionAnnot)), C.c_char_p, C.c_size_t]
         L.rgx_junction_annot_free.argtypes = [P(JunctionAnnot)]
+        L.rgx_gtf_bin_index.argtypes = [C.c_void_p]
+        L.rgx_k_junction_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_int32), P(C.c_uint32), P(C.c_uint32), C.c_char_p, C.c_int, C.c_int,
+                                          P(P(JunctionItems)), C.c_char_p, C.c_size_t]
+        L.rgx_junction_items_free.argtypes = [P(JunctionItems)]
+        L.rgx_pair_list_free.argtypes = [P(PairList)]
+        L.rgx_k_window_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                         C.c_uint64, P(P(PairList)), C.c_char_p, C.c_size_t]
+        L.rgx_k_assoc_pairs.argtypes = [C.c_void_p, C.c_uint32, P(C.c_int32), P(C.c_uint32), P(C.c_uint32), C.c_uint32, P(C.c_uint32), C.c_uint32,
+                                        P(C.c_uint32), P(C.c_uint32), P(P(PairList)), C.c_char_p, C.c_size_t]
         L.rgx_window_join.argtypes = [C.c_void_p, C.c_char_p, P(ExtractParams), C.c_uint64, P(C.c_char_p), P(C.c_int32), P(C.c_int32), P(P(WindowRows)), C.c_char_p, C.c_size_t]
         L.rgx_window_rows_free.argtypes = [P(WindowRows)]
         L.rgx_cohort_params_default.argtypes = [P(CohortParams)]

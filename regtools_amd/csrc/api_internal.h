@@ -226,6 +226,23 @@ struct DevBuf {
     explicit operator Carve() const { return Carve(p, cap); }      // Carve w(buffer): the whole buffer, to be cut into its arrays (carve.h)
 };
 
+// Guard words behind an array of a stage entry point's scratch (api_stage.cpp): armed in front of the launches, read back behind them -- a pass
+// that writes behind what its sizing gave it fails the call instead of going unseen in a buffer's growth slack.
+constexpr uint32_t kGuardWords = 64, kGuardFill = 0xA5C3F00Du;
+struct StageGuard {
+    uint32_t *d = nullptr;
+    void arm(uint32_t *at, hipStream_t st) { d = at; launch_fill_u32(d, kGuardFill, kGuardWords, st); }
+    // behind the stream's work: hipSuccess and *touched says whether a word changed
+    hipError_t check(hipStream_t st, bool *touched) const {
+        uint32_t h[kGuardWords];
+        hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        *touched = false;
+        if (e == hipSuccess) for (uint32_t k = 0; k < kGuardWords; ++k) if (h[k] != kGuardFill) *touched = true;
+        return e;
+    }
+};
+
 // The context's device buffers: one enumerator per workspace, spelt like the name CARVE_TRY and the traces call it by.
 enum class Buf {
     arena, bad_members, bam, barcode_text, barcodes, cand, cse_assoc, cse_events_all, cse_junction_items, cse_junctions, cse_pairs, cse_variant_hits,

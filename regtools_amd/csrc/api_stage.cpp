@@ -5,23 +5,9 @@
 // radix_tmp_words or scan_tmp_words that is too small for what a pass writes fails the call instead of going unseen in the buffer's growth slack.
 #include "api_internal.h"
 
-namespace {
-constexpr uint32_t kGuardWords = 64, kGuardFill = 0xA5C3F00Du;
+#include "cse_internal.h"
 
-struct Guard {
-    uint32_t *d = nullptr;
-    void arm(uint32_t *at, hipStream_t st) { d = at; launch_fill_u32(d, kGuardFill, kGuardWords, st); }
-    // behind the stream's work: hipSuccess and *touched says whether a word changed
-    hipError_t check(hipStream_t st, bool *touched) const {
-        uint32_t h[kGuardWords];
-        hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        *touched = false;
-        if (e == hipSuccess) for (uint32_t k = 0; k < kGuardWords; ++k) if (h[k] != kGuardFill) *touched = true;
-        return e;
-    }
-};
-}  // namespace
+typedef StageGuard Guard;       // (api_internal.h: the interval stages' shared halves arm theirs where they carve)
 
 extern "C" int rgx_k_scan_u32(rgx_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint32_t n, uint32_t *d_total, char *err, size_t errlen) {
     if (!c || (n && (!d_in || !d_out))) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
@@ -125,5 +111,93 @@ extern "C" int rgx_k_components(rgx_ctx *c, uint32_t n_vertices, uint32_t n_edge
     bool touched = false;
     HIP_TRY(g.check(st, &touched));
     if (touched) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the component search wrote behind its %u flag words\n", kCcBatch);
+    return RGX_OK;
+}
+
+// ---- the interval kernels of cis-splice-effects / annotate (cse_kernels.hip) on the caller's own junctions, events and windows ---------------------
+// (tests/test_gpu_cse_edges.py).  Each runs the half its command runs: junction_scan_items is annotate_junctions' front, window_pair_batches is
+// window_join's, assoc_join is `associate`'s join as it stands.  The variable-length outputs lie in Buf::stage with guard words behind them.
+extern "C" int rgx_gtf_bin_index(const rgx_gtf *g) { return g && g->view.bin_start ? 1 : 0; }
+
+extern "C" int rgx_k_junction_scan(rgx_ctx *c, const rgx_gtf *g, uint64_t n, const int32_t *contig, const uint32_t *start, const uint32_t *end1,
+                                   const char *strand, int keep_single, int form, rgx_junction_items **out, char *err, size_t errlen) {
+    if (!c || !g || !out || form < 0 || form > 1 || n >= (1ull << 31) || (n && (!contig || !start || !end1 || !strand)))
+        return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
+    *out = nullptr;
+    const int64_t n_chroms = (int64_t)g->m.chroms.size();
+    for (uint64_t i = 0; i < n; ++i) if (contig[i] >= n_chroms) return fail(err, errlen, RGX_ERR_ARG,
+        "regtools_amd: junction %llu is on contig %d of an annotation with %lld\n", (unsigned long long)i, contig[i], (long long)n_chroms);
+    std::vector<int32_t> ci(contig, contig + n); std::vector<uint32_t> js(start, start + n), je(end1, end1 + n);
+    std::vector<uint8_t> sd((const uint8_t *)strand, (const uint8_t *)strand + n);
+    GtfView view = g->view; view.keep_single = keep_single ? 1u : 0u;
+    JunctionItemsHost R;
+    const int rc = junction_scan_items(c, view, ci, js, je, sd, form, /*guarded=*/true, R, err, errlen);
+    if (rc != RGX_OK) return rc;
+    rgx_junction_items *r = (rgx_junction_items *)calloc(1, sizeof *r);
+    r->n = n; r->visits_total = R.visits_total; r->flags = dup_u32(R.flags); r->visits = dup_u32(R.visits); r->item_off = dup_u32(R.off);
+    r->item_kind = dup_u32(R.kind); r->item_a = dup_u32(R.a); r->item_b = dup_u32(R.b);
+    *out = r;
+    return RGX_OK;
+}
+extern "C" void rgx_junction_items_free(rgx_junction_items *r) {
+    if (!r) return;
+    free(r->flags); free(r->visits); free(r->item_off); free(r->item_kind); free(r->item_a); free(r->item_b); free(r);
+}
+
+static rgx_pair_list *pair_list(const std::vector<uint32_t> &first, const std::vector<uint32_t> &window, uint32_t n_batches) {
+    rgx_pair_list *r = (rgx_pair_list *)calloc(1, sizeof *r);
+    r->n = first.size(); r->n_batches = n_batches; r->first = dup_u32(first); r->window = dup_u32(window);
+    return r;
+}
+extern "C" void rgx_pair_list_free(rgx_pair_list *r) { if (!r) return; free(r->first); free(r->window); free(r); }
+
+extern "C" int rgx_k_window_pairs(rgx_ctx *c, const uint32_t *d_tid, const uint32_t *d_rpos, const uint32_t *d_rend, uint32_t n_events, uint32_t n_windows,
+                                  const int32_t *w_tid, const int32_t *w_beg, const int32_t *w_end, uint64_t pair_batch, rgx_pair_list **out, char *err,
+                                  size_t errlen) {
+    if (!c || !out || (n_events && (!d_tid || !d_rpos || !d_rend)) || (n_windows && (!w_tid || !w_beg || !w_end)))
+        return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
+    *out = nullptr;
+    HIP_ENTER(c->device);
+    hipStream_t st = c->stream;
+    HIP_TRY(c->buf(Buf::scalars).ensure(sizeof(Scalars)));
+    EventSoA ev; memset(&ev, 0, sizeof ev);
+    ev.tid = (uint32_t *)d_tid; ev.rpos = (uint32_t *)d_rpos; ev.rend = (uint32_t *)d_rend;
+    const std::vector<int32_t> wt(w_tid, w_tid + n_windows), wb(w_beg, w_beg + n_windows), we(w_end, w_end + n_windows);
+    std::vector<uint32_t> pe, pw;
+    uint64_t n_pairs = 0; uint32_t n_batches = 0;
+    const int rc = window_pair_batches(c, ev, n_events, wt, wb, we, pair_batch, /*guarded=*/true, [&](uint32_t w0, uint32_t, uint32_t total, const PairLayout &L) {
+        const size_t at = pe.size();
+        pe.resize(at + total); pw.resize(at + total);
+        HIP_TRY(hipMemcpyAsync(pe.data() + at, L.pair_ev, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(pw.data() + at, L.pair_win, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = at; k < pw.size(); ++k) pw[k] += w0;                  // (a batch numbers its windows from 0)
+        return (int)RGX_OK;
+    }, n_pairs, n_batches, err, errlen);
+    if (rc != RGX_OK) return rc;
+    if (n_pairs != pe.size()) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: %llu pairs counted, %zu filled\n", (unsigned long long)n_pairs, pe.size());
+    *out = pair_list(pe, pw, n_batches);
+    return RGX_OK;
+}
+
+extern "C" int rgx_k_assoc_pairs(rgx_ctx *c, uint32_t n_windows, const int32_t *w_contig, const uint32_t *w_ces, const uint32_t *w_cee, uint32_t n_contigs,
+                                 const uint32_t *contig_off, uint32_t n_junctions, const uint32_t *j_start, const uint32_t *j_end, rgx_pair_list **out,
+                                 char *err, size_t errlen) {
+    if (!c || !out || !contig_off || (n_windows && (!w_contig || !w_ces || !w_cee)) || (n_junctions && (!j_start || !j_end)))
+        return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
+    *out = nullptr;
+    // the kernel trusts the buckets: they must tile [0, n_junctions), and every window's contig must have one
+    bool ok = contig_off[0] == 0 && contig_off[n_contigs] == n_junctions;
+    for (uint32_t k = 0; ok && k < n_contigs; ++k) ok = contig_off[k] <= contig_off[k + 1];
+    for (uint32_t w = 0; ok && w < n_windows; ++w) ok = w_contig[w] < (int64_t)n_contigs;
+    if (!ok) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: the contig buckets do not tile the junctions, or a window names a contig without one\n");
+    const std::vector<int32_t> wch(w_contig, w_contig + n_windows);
+    const std::vector<uint32_t> wces(w_ces, w_ces + n_windows), wcee(w_cee, w_cee + n_windows), off(contig_off, contig_off + n_contigs + 1),
+        js(j_start, j_start + n_junctions), je(j_end, j_end + n_junctions);
+    std::vector<uint32_t> pj, pw;
+    uint64_t n_pairs = 0;
+    const int rc = assoc_join(c, wch, wces, wcee, off, js, je, pj, pw, n_pairs, err, errlen);
+    if (rc != RGX_OK) return rc;
+    *out = pair_list(pj, pw, 1);
     return RGX_OK;
 }

@@ -56,6 +56,8 @@ struct SideLoad {
 // ---- results of the stages -------------------------------------------------------------------------------------------------------------
 struct VariantHitsHost { std::vector<uint32_t> ces, cee, off, tx, ann, dist, last; };      // last: upstream's variant.score behind the walk (0xffffffff = "-1")
 struct JunctionAnnotHost { std::vector<uint32_t> flags, n_acc, n_exo, n_don, tx_off, tx; };
+// a11 as the kernel leaves it: junction i's items (kind, a, b) are off[i] .. off[i + 1], in visiting order, duplicates included
+struct JunctionItemsHost { std::vector<uint32_t> flags, visits, off, kind, a, b; uint64_t visits_total = 0; };
 struct VStr { std::string genes, transcripts, distances, annotations; };
 struct VariantStage {
     VcfText vcf;
@@ -91,8 +93,20 @@ int gtf_upload(rgx_ctx *c, rgx_gtf *g, char *err, size_t errlen, bool pooled = f
 int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32_t> &chrom, const std::vector<uint32_t> &js, const std::vector<uint32_t> &je,
                        const std::vector<uint8_t> &strand, JunctionAnnotHost &A, char *err, size_t errlen, uint64_t *exon_visits = nullptr,
                        bool keep_single = false);
+int junction_scan_items(rgx_ctx *c, const GtfView &view, const std::vector<int32_t> &chrom, const std::vector<uint32_t> &js, const std::vector<uint32_t> &je,
+                        const std::vector<uint8_t> &strand, int form, bool guarded, JunctionItemsHost &R, char *err, size_t errlen);
 int variant_scan_stage(rgx_ctx *c, const rgx_gtf *g, const VariantOpts &vo, VariantStage &V, uint64_t *exon_visits, char *err, size_t errlen);
 // cse_join.cpp
+// The pair workspace of one batch of windows: the two pair lists of the window join (window numbers batch-local), then -- in the product's
+// Buf::cse_pairs -- room for the pairs' events as an EventSoA of as many rows.
+struct PairLayout { uint32_t *pair_ev, *pair_win; EventSoA pe; };
+// on_batch(first window, windows, pairs, the batch's lists): called for every batch that holds a pair, behind its fill pass on the stream
+typedef std::function<int(uint32_t w0, uint32_t nw, uint32_t total, const PairLayout &L)> PairBatchFn;
+// The planning and counting half of the window join and its per-batch fill.  pair_batch: pairs per batch of whole windows (a window above it is a
+// batch of its own), 0 = the product's (2^26, or REGTOOLS_AMD_PAIR_BATCH).  guarded: the lists lie in Buf::stage with guard words behind each.
+int window_pair_batches(rgx_ctx *c, const EventSoA &ev, uint32_t n_events, const std::vector<int32_t> &w_tid, const std::vector<int32_t> &w_beg,
+                        const std::vector<int32_t> &w_end, uint64_t pair_batch, bool guarded, const PairBatchFn &on_batch, uint64_t &n_pairs,
+                        uint32_t &n_batches, char *err, size_t errlen);
 int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_tid, const std::vector<int32_t> &w_beg, const std::vector<int32_t> &w_end,
                 uint32_t ilen_bits, HostRows &R, uint64_t &n_pairs, char *err, size_t errlen);
 int window_join_by_seeks(rgx_ctx *c, const uint8_t *d_file, size_t bam_len, const uint8_t *bai, size_t bai_len, const rgx_extract_params &ep0,

@@ -2,9 +2,8 @@
 // window through the index for a damaged file, the pair join of `associate`, and the gather of a sharded extraction's events (8e).
 #include "cse_internal.h"
 
-// The pair workspace (Buf::cse_pairs): the two pair lists of the window join, then the pairs' events as an EventSoA of Pn rows.  A caller that brings
-// the events itself leaves the lists' place empty.  The caller's CARVE_TRY(q, "cse_pairs") follows.
-struct PairLayout { uint32_t *pair_ev, *pair_win; EventSoA pe; };
+// The pair workspace (Buf::cse_pairs, PairLayout of cse_internal.h): the two pair lists of the window join, then the pairs' events as an EventSoA of Pn
+// rows.  A caller that brings the events itself leaves the lists' place empty.  The caller's CARVE_TRY(q, "cse_pairs") follows.
 static PairLayout pair_layout(Carve &q, size_t Pn) {
     PairLayout L; memset(&L.pe, 0, sizeof L.pe);
     L.pair_ev = q.u32(Pn); L.pair_win = q.u32(Pn);
@@ -25,12 +24,12 @@ static int reduce_pair_batch(rgx_ctx *c, const EventSoA &pe, uint32_t total, uin
 }
 
 // ---- a9: window join -------------------------------------------------------------------------------------------------------
-// rows of every window in the order get_all_junctions would give for that window's extraction (thick_start, thick_end, name)
-int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_tid, const std::vector<int32_t> &w_beg, const std::vector<int32_t> &w_end,
-                uint32_t ilen_bits, HostRows &R, uint64_t &n_pairs, char *err, size_t errlen) {
-    R = HostRows(); n_pairs = 0;
+int window_pair_batches(rgx_ctx *c, const EventSoA &ev, uint32_t n_events, const std::vector<int32_t> &w_tid, const std::vector<int32_t> &w_beg,
+                        const std::vector<int32_t> &w_end, uint64_t pair_batch, bool guarded, const PairBatchFn &on_batch, uint64_t &n_pairs,
+                        uint32_t &n_batches, char *err, size_t errlen) {
+    n_pairs = 0; n_batches = 0;
     const uint32_t W = (uint32_t)w_tid.size();
-    if (!W || !P.n_events) return RGX_OK;
+    if (!W || !n_events) return RGX_OK;
     hipStream_t st = c->stream;
     DevBuf &b = c->buf(Buf::cse_windows), &sc = c->buf(Buf::scalars);
     const size_t Wn = W;
@@ -45,9 +44,9 @@ int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_tid, co
     HIP_TRY(upload(d_beg, w_beg, Wn, st));
     HIP_TRY(upload(d_end, w_end, Wn, st));
     HIP_TRY(hipMemsetAsync(d_span, 0, 4, st));
-    launch_max_span(P.ev, P.n_events, d_span, st);
+    launch_max_span(ev, n_events, d_span, st);
     ktime_begin(c, 2);
-    launch_window_pairs(false, P.ev, P.n_events, W, d_tid, d_beg, d_end, d_span, d_lo, d_hi, d_cnt, nullptr, nullptr, nullptr, st);
+    launch_window_pairs(false, ev, n_events, W, d_tid, d_beg, d_end, d_span, d_lo, d_hi, d_cnt, nullptr, nullptr, nullptr, st);
     ktime_end(c);
     // The (window, event) pairs are materialised in batches of whole windows: a VCF dense in splice-region variants of highly
     // expressed genes multiplies events by windows, and neither a 32-bit pair count nor HBM should be the limit of that.
@@ -60,32 +59,60 @@ int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_tid, co
             h_cnt[k] = c > 0xffffffffull ? 0xffffffffu : (uint32_t)c; }
     }
     static const uint64_t kPairBatch = getenv("REGTOOLS_AMD_PAIR_BATCH") ? strtoull(getenv("REGTOOLS_AMD_PAIR_BATCH"), nullptr, 10) : (1ull << 26);
+    if (!pair_batch) pair_batch = kPairBatch;
     for (uint32_t w0 = 0; w0 < W;) {
         uint64_t total64 = h_cnt[w0];
         uint32_t w1 = w0 + 1;
-        while (w1 < W && total64 + h_cnt[w1] <= kPairBatch) total64 += h_cnt[w1++];
+        while (w1 < W && total64 + h_cnt[w1] <= pair_batch) total64 += h_cnt[w1++];
         if (total64 >= (1ull << 31)) return fail(err, errlen, RGX_ERR_ARG,
             "regtools_amd: one variant window holds %llu junction-supporting reads; more than the join handles\n", (unsigned long long)total64);
         const uint32_t nw = w1 - w0, total = (uint32_t)total64;
         n_pairs += total;
+        ++n_batches;
         if (total) {
             launch_scan_u32(d_cnt + (size_t)w0 * kWinSlices, d_base + (size_t)w0 * kWinSlices, nw * kWinSlices, d_total, d_tmp, st);
-            DevBuf &bp = c->buf(Buf::cse_pairs);
             const size_t Pn = total;
-            HIP_TRY(bp.ensure(Pn * 4 * 7 + Pn + 256));
-            Carve q(bp);
-            const PairLayout L = pair_layout(q, Pn); CARVE_TRY(q, "cse_pairs");
+            PairLayout L;
+            StageGuard guard[2];
+            if (guarded) {
+                DevBuf &bp = c->buf(Buf::stage);
+                HIP_TRY(bp.ensure((Pn + kGuardWords) * 4 * 2 + 256));
+                Carve q(bp);
+                memset(&L.pe, 0, sizeof L.pe);
+                L.pair_ev = q.u32(Pn); uint32_t *g_ev = q.u32(kGuardWords); L.pair_win = q.u32(Pn); uint32_t *g_win = q.u32(kGuardWords); CARVE_TRY(q, "stage");
+                guard[0].arm(g_ev, st); guard[1].arm(g_win, st);
+            } else {
+                DevBuf &bp = c->buf(Buf::cse_pairs);
+                HIP_TRY(bp.ensure(Pn * 4 * 7 + Pn + 256));
+                Carve q(bp);
+                L = pair_layout(q, Pn); CARVE_TRY(q, "cse_pairs");
+            }
             ktime_begin(c, 2);
-            launch_window_pairs(true, P.ev, P.n_events, nw, d_tid + w0, d_beg + w0, d_end + w0, d_span, d_lo + w0, d_hi + w0,
+            launch_window_pairs(true, ev, n_events, nw, d_tid + w0, d_beg + w0, d_end + w0, d_span, d_lo + w0, d_hi + w0,
                 d_cnt + (size_t)w0 * kWinSlices, d_base + (size_t)w0 * kWinSlices, L.pair_ev, L.pair_win, st);
             ktime_end(c);
-            launch_pair_gather(P.ev, L.pair_ev, L.pair_win, total, L.pe, st);
-            const int rc = reduce_pair_batch(c, L.pe, total, nw, w0, ilen_bits, R, err, errlen);
+            if (guarded) for (const StageGuard &g : guard) {
+                bool touched = false;
+                HIP_TRY(g.check(st, &touched));
+                if (touched) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the window join's fill pass wrote behind the %u pairs its count pass counted\n", total);
+            }
+            const int rc = on_batch(w0, nw, total, L);
             if (rc != RGX_OK) return rc;
         }
         w0 = w1;
     }
     return RGX_OK;
+}
+
+// rows of every window in the order get_all_junctions would give for that window's extraction (thick_start, thick_end, name)
+int window_join(rgx_ctx *c, const Prep &P, const std::vector<int32_t> &w_tid, const std::vector<int32_t> &w_beg, const std::vector<int32_t> &w_end,
+                uint32_t ilen_bits, HostRows &R, uint64_t &n_pairs, char *err, size_t errlen) {
+    R = HostRows();
+    uint32_t n_batches = 0;
+    return window_pair_batches(c, P.ev, P.n_events, w_tid, w_beg, w_end, 0, false, [&](uint32_t w0, uint32_t nw, uint32_t total, const PairLayout &L) {
+        launch_pair_gather(P.ev, L.pair_ev, L.pair_win, total, L.pe, c->stream);
+        return reduce_pair_batch(c, L.pe, total, nw, w0, ilen_bits, R, err, errlen);
+    }, n_pairs, n_batches, err, errlen);
 }
 
 // `identify` on a file whose record stream ENDED somewhere (a member that does not inflate, an unreadable record): upstream reads every variant's window

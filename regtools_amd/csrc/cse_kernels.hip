@@ -295,9 +295,10 @@ void launch_variant_scan(bool fill, GtfView g, uint32_t n, const int32_t *chrom,
 }
 void launch_junction_scan(bool fill, GtfView g, uint32_t n, const int32_t *chrom, const uint32_t *js, const uint32_t *je, const uint8_t *strand, uint32_t *count,
                           const uint32_t *base, uint32_t *flags, uint32_t *item_kind, uint32_t *item_a, uint32_t *item_b, unsigned long long *visits, uint32_t *visit_each,
-                          hipStream_t stream) {
+                          hipStream_t stream, int form) {
     if (!n) return;
-    static const bool lane_form = [] { const char *e = getenv("REGTOOLS_AMD_JSCAN"); return e && !strcmp(e, "lane"); }();   // (tests: the one-lane-per-junction form, against which the wave form is checked)
+    static const bool lane_default = [] { const char *e = getenv("REGTOOLS_AMD_JSCAN"); return e && !strcmp(e, "lane"); }();   // (tests: the one-lane-per-junction form, against which the wave form is checked)
+    const bool lane_form = form < 0 ? lane_default : form == 1;
     if (!lane_form) {
         if (fill) hipLaunchKernelGGL(k_junction_scan_wave<true>, dim3((n + 3) / 4), dim3(256), 0, stream, g, n, chrom, js, je, strand, count, base, flags, item_kind, item_a, item_b, visit_each);
         else hipLaunchKernelGGL(k_junction_scan_wave<false>, dim3((n + 3) / 4), dim3(256), 0, stream, g, n, chrom, js, je, strand, count, base, flags, item_kind, item_a, item_b, visit_each);

@@ -167,12 +167,15 @@ extern "C" void rgx_variant_hits_free(rgx_variant_hits *h) {
 }
 
 // ---- a11 ----------------------------------------------------------------------------------------------------------------
-int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32_t> &chrom, const std::vector<uint32_t> &js, const std::vector<uint32_t> &je,
-                       const std::vector<uint8_t> &strand, JunctionAnnotHost &A, char *err, size_t errlen, uint64_t *exon_visits, bool keep_single) {
+// The two launches of a11 and the scan between them: per junction the flags, the exon records of its candidates (wave form; the lane form adds into
+// one counter: R.visits_total) and its items (kind, a, b) as the kernel wrote them, item_off[i] .. item_off[i + 1].  annotate_junctions makes the
+// items unique behind this; the stage entry point rgx_k_junction_scan hands them out as they are.  guarded: the three item columns lie in Buf::stage
+// with guard words behind each -- a fill pass that writes more than the count pass counted fails the call.
+int junction_scan_items(rgx_ctx *c, const GtfView &view, const std::vector<int32_t> &chrom, const std::vector<uint32_t> &js, const std::vector<uint32_t> &je,
+                        const std::vector<uint8_t> &strand, int form, bool guarded, JunctionItemsHost &R, char *err, size_t errlen) {
     const uint32_t n = (uint32_t)chrom.size();
-    GtfView view = g->view; view.keep_single = keep_single ? 1u : 0u;          // (`junctions annotate -S` only)
-    A = JunctionAnnotHost();
-    A.tx_off.assign((size_t)n + 1, 0);
+    R = JunctionItemsHost();
+    R.off.assign((size_t)n + 1, 0);
     if (!n) return RGX_OK;
     hipStream_t st = c->stream;
     HIP_ENTER(c->device);
@@ -192,37 +195,60 @@ int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32_t> 
     unsigned long long *d_visits = &sc.as<Scalars>()->junction_visits, h_visits = 0;
     HIP_TRY(hipMemsetAsync(d_visits, 0, 8, st));
     ktime_begin(c, 1);
-    launch_junction_scan(false, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, nullptr, d_flags, nullptr, nullptr, nullptr, d_visits, d_visit_each, st);
+    launch_junction_scan(false, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, nullptr, d_flags, nullptr, nullptr, nullptr, d_visits, d_visit_each, st, form);
     ktime_end(c);
     launch_scan_u32(d_cnt, d_base, n, d_total, d_tmp, st);
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&h_visits, d_visits, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::vector<uint32_t> off((size_t)n + 1), kind(total), ia(total), ib(total);
-    A.flags.resize(N);
-    HIP_TRY(hipMemcpy(A.flags.data(), d_flags, N * 4, hipMemcpyDeviceToHost));
+    R.flags.resize(N); R.visits.resize(N); R.kind.resize(total); R.a.resize(total); R.b.resize(total);
+    HIP_TRY(hipMemcpy(R.flags.data(), d_flags, N * 4, hipMemcpyDeviceToHost));
     // SURVEY 8d's E_j: the lane form adds into one counter, the wave form writes one count per junction
-    if (exon_visits) {
-        HIP_TRY(hipMemcpy(off.data(), d_visit_each, N * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < N; ++i) h_visits += off[i];
-        *exon_visits = h_visits;
-    }
-    HIP_TRY(hipMemcpy(off.data(), d_base, N * 4, hipMemcpyDeviceToHost));
-    off[N] = total;
+    HIP_TRY(hipMemcpy(R.visits.data(), d_visit_each, N * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) h_visits += R.visits[i];
+    R.visits_total = h_visits;
+    HIP_TRY(hipMemcpy(R.off.data(), d_base, N * 4, hipMemcpyDeviceToHost));
+    R.off[N] = total;
     if (total) {
-        DevBuf &bi = c->buf(Buf::cse_junction_items);
-        HIP_TRY(bi.ensure((size_t)total * 12 + 256));
+        DevBuf &bi = c->buf(guarded ? Buf::stage : Buf::cse_junction_items);
+        const size_t G = guarded ? kGuardWords : 0;
+        HIP_TRY(bi.ensure(((size_t)total + G) * 12 + 256));
         Carve wi(bi);
-        uint32_t *d_k = wi.u32(total), *d_a = wi.u32(total), *d_b = wi.u32(total); CARVE_TRY(wi, "cse_junction_items");
+        uint32_t *d_k = wi.u32(total), *g_k = wi.u32(G), *d_a = wi.u32(total), *g_a = wi.u32(G), *d_b = wi.u32(total), *g_b = wi.u32(G);
+        CARVE_TRY(wi, guarded ? "stage" : "cse_junction_items");
+        StageGuard guard[3];
+        if (guarded) { guard[0].arm(g_k, st); guard[1].arm(g_a, st); guard[2].arm(g_b, st); }
         ktime_begin(c, 1);
-        launch_junction_scan(true, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, d_base, d_flags, d_k, d_a, d_b, nullptr, nullptr, st);
+        launch_junction_scan(true, view, n, d_chrom, d_js, d_je, d_strand, d_cnt, d_base, d_flags, d_k, d_a, d_b, nullptr, nullptr, st, form);
         ktime_end(c);
-        HIP_TRY(hipMemcpyAsync(kind.data(), d_k, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ia.data(), d_a, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ib.data(), d_b, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(R.kind.data(), d_k, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(R.a.data(), d_a, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(R.b.data(), d_b, (size_t)total * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        if (guarded) for (const StageGuard &g : guard) {
+            bool touched = false;
+            HIP_TRY(g.check(st, &touched));
+            if (touched) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the junction scan's fill pass wrote behind the %u items its count pass counted\n", total);
+        }
     }
+    return RGX_OK;
+}
+
+int annotate_junctions(rgx_ctx *c, const rgx_gtf *g, const std::vector<int32_t> &chrom, const std::vector<uint32_t> &js, const std::vector<uint32_t> &je,
+                       const std::vector<uint8_t> &strand, JunctionAnnotHost &A, char *err, size_t errlen, uint64_t *exon_visits, bool keep_single) {
+    const uint32_t n = (uint32_t)chrom.size();
+    GtfView view = g->view; view.keep_single = keep_single ? 1u : 0u;          // (`junctions annotate -S` only)
+    A = JunctionAnnotHost();
+    A.tx_off.assign((size_t)n + 1, 0);
+    if (!n) return RGX_OK;
+    const size_t N = n;
+    JunctionItemsHost R;
+    const int rc = junction_scan_items(c, view, chrom, js, je, strand, /*form=*/-1, /*guarded=*/false, R, err, errlen);
+    if (rc != RGX_OK) return rc;
+    if (exon_visits) *exon_visits = R.visits_total;
+    A.flags.swap(R.flags);
+    const std::vector<uint32_t> &off = R.off, &kind = R.kind, &ia = R.a, &ib = R.b;
     // the reference keeps sets (junctions_annotator.h:41-45): unique skipped elements by coordinate, transcripts by id -- here small
     // vectors, sorted and made unique, ranges of junctions on the host's threads (std::set per junction: 20 of config 4's 280 ms)
     A.n_acc.resize(N); A.n_exo.resize(N); A.n_don.resize(N);

@@ -276,10 +276,11 @@ namespace rgx {
 void launch_variant_scan(bool fill, GtfView g, uint32_t n, const int32_t *chrom, const uint32_t *pos0, VariantOpts o, uint32_t *count, const uint32_t *base,
                          uint32_t *ces, uint32_t *cee, uint32_t *hit_tx, uint32_t *hit_ad, unsigned long long *visits /* count pass: += exon records visited */,
                          hipStream_t stream, uint32_t *last_score = nullptr /* count pass: upstream's variant.score behind the walk (cse_core.h) */);
-// count pass: count[i], flags[i] = known_donor | known_acceptor<<1 | known_junction<<2; fill pass: items (kind,a,b) in visitation order
+// count pass: count[i], flags[i] = known_donor | known_acceptor<<1 | known_junction<<2; fill pass: items (kind,a,b) in visitation order.
+// form: 0 = one wave per junction, 1 = one lane per junction, -1 = the process's default (the wave form unless REGTOOLS_AMD_JSCAN=lane)
 void launch_junction_scan(bool fill, GtfView g, uint32_t n, const int32_t *chrom, const uint32_t *js, const uint32_t *je, const uint8_t *strand, uint32_t *count,
                           const uint32_t *base, uint32_t *flags, uint32_t *item_kind, uint32_t *item_a, uint32_t *item_b, unsigned long long *visits,
-                          uint32_t *visit_each /* wave form: exon records per junction */, hipStream_t stream);
+                          uint32_t *visit_each /* wave form: exon records per junction */, hipStream_t stream, int form = -1);
 void launch_max_span(EventSoA ev, uint32_t n, uint32_t *out /* zeroed by the caller */, hipStream_t stream);
 constexpr uint32_t kWinSlices = 4;      // workgroups per variant window (k_window_pairs); count / base arrays hold n_win x kWinSlices entries
 void launch_window_pairs(bool fill, EventSoA ev, uint32_t n_events, uint32_t n_win, const int32_t *w_tid, const int32_t *w_beg, const int32_t *w_end,

@@ -303,3 +303,63 @@ extern "C" long emu_jtable(size_t n_names, const char *const *names, size_t n_vn
     *n_vars = t.vars.size();
     return (long)t.size();
 }
+
+// The two annotation cores of cse_core.h over host memory (tests/test_cse_edges_host.py): GtfModel::load, a GtfView over its vectors in whichever
+// index form the model chose (bin_start empty: the kernels' binary search), then junction_scan / variant_scan junction by junction -- the raw lists
+// rgx_k_junction_scan and rgx_variant_windows return.  Outputs beyond `cap` items are counted, not written; the return value is the item count.
+struct emu_gtf { rgx::GtfModel m; rgx::GtfView v; };
+extern "C" void *emu_gtf_open(const char *gtf_path, char *err, size_t errlen) {
+    emu_gtf *g = new emu_gtf();
+    const std::string e = g->m.load(gtf_path);
+    if (!e.empty()) { snprintf(err, errlen, "%s", e.c_str()); delete g; return nullptr; }
+    const rgx::GtfModel &m = g->m;
+    g->v.tx_strand = m.tx_strand.data(); g->v.tx_exon_off = m.tx_exon_off.data(); g->v.tx_n_exons = m.tx_n_exons.data();
+    g->v.es = m.es.data(); g->v.ee = m.ee.data(); g->v.bin_key = m.bin_key.data(); g->v.bin_tx = m.bin_tx.data(); g->v.n_bin = (uint32_t)m.bin_key.size();
+    g->v.bin_start = m.bin_start.size() ? m.bin_start.data() : nullptr; g->v.bin_stride = m.bin_start.size() ? m.bin_stride : 0;
+    g->v.keep_single = 0;
+    return g;
+}
+extern "C" void emu_gtf_close(void *h) { delete (emu_gtf *)h; }
+extern "C" int emu_gtf_bin_index(const void *h) { return ((const emu_gtf *)h)->v.bin_start ? 1 : 0; }
+extern "C" uint32_t emu_gtf_n_tx(const void *h) { return (uint32_t)((const emu_gtf *)h)->m.tx_id.size(); }
+extern "C" uint32_t emu_gtf_n_chroms(const void *h) { return (uint32_t)((const emu_gtf *)h)->m.chroms.size(); }
+extern "C" const char *emu_gtf_tx_id(const void *h, uint32_t t) { return ((const emu_gtf *)h)->m.tx_id[t].c_str(); }
+extern "C" uint32_t emu_gtf_tx_bin(const void *h, uint32_t t) { return ((const emu_gtf *)h)->m.tx_bin[t]; }
+extern "C" int32_t emu_gtf_chrom_of(const void *h, const char *name) { return ((const emu_gtf *)h)->m.chrom_of(name); }
+
+extern "C" long emu_junction_scan(const void *h, uint32_t n, const int32_t *contig, const uint32_t *js, const uint32_t *je, const char *strand, int keep_single,
+                                  uint32_t *flags, uint32_t *visits, uint32_t *item_off, size_t cap, uint32_t *kind, uint32_t *a, uint32_t *b) {
+    rgx::GtfView v = ((const emu_gtf *)h)->v;
+    v.keep_single = keep_single ? 1u : 0u;
+    size_t k = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (contig[i] >= (int64_t)((const emu_gtf *)h)->m.chroms.size()) return -1;
+        rgx::JunctionFlags f;
+        item_off[i] = (uint32_t)k;
+        rgx::junction_scan(v, contig[i], js[i], je[i], strand[i], f, visits[i], [&](uint32_t kd, uint32_t x, uint32_t y) {
+            if (k < cap) { kind[k] = kd; a[k] = x; b[k] = y; }
+            ++k;
+        });
+        flags[i] = f.known_donor | f.known_acceptor << 1 | f.known_junction << 2;
+    }
+    item_off[n] = (uint32_t)k;
+    return (long)k;
+}
+
+extern "C" long emu_variant_scan(const void *h, uint32_t n, const int32_t *contig, const uint32_t *pos0, uint32_t intronic_min, uint32_t exonic_min,
+                                 int all_intronic, int all_exonic, int skip_single, uint32_t *ces, uint32_t *cee, uint32_t *visits, uint32_t *hit_off,
+                                 size_t cap, uint32_t *tx, uint32_t *ann, uint32_t *dist) {
+    const rgx::GtfView &v = ((const emu_gtf *)h)->v;
+    const rgx::VariantOpts o{intronic_min, exonic_min, all_intronic, all_exonic, skip_single};
+    size_t k = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (contig[i] >= (int64_t)((const emu_gtf *)h)->m.chroms.size()) return -1;
+        hit_off[i] = (uint32_t)k;
+        rgx::variant_scan(v, contig[i], pos0[i], o, ces[i], cee[i], visits[i], [&](uint32_t t, uint32_t an, uint32_t d) {
+            if (k < cap) { tx[k] = t; ann[k] = an; dist[k] = d; }
+            ++k;
+        });
+    }
+    hit_off[n] = (uint32_t)k;
+    return (long)k;
+}
