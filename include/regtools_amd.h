@@ -775,6 +775,23 @@ int  rgx_k_inflate_form(int form, const void *d_comp, const rgx_member *d_member
 /* d_out[i] = d_in[0] + ... + d_in[i - 1] (mod 2^32); d_out may be d_in; *d_total = the sum of all n, written only when d_total is not NULL
  * (0 for n = 0). */
 int  rgx_k_scan_u32(rgx_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint32_t n, uint32_t *d_total, char *err, size_t errlen);
+/* The front of the pipeline on its own (tests): BGZF member discovery on a file that lies in HBM, as rgx_extract_device runs it -- d_bam readable to
+ * bam_len + 8.  Every offset o with o + 18 <= bam_len that carries the ten fixed bytes of a BGZF header is a candidate; the members are the
+ * candidates that chain up (BSIZE + 1) from offset 0, and with root2 != ~0 -- a second pass over the same candidates and buffers, as behind a seek
+ * the first chain does not reach -- also those that chain up from root2; cpos = o + 18, clen clipped to cpos + clen + 8 <= bam_len, isize the
+ * footer's (~0: the header runs past the file or BSIZE + 1 < 26; such a candidate is listed and ends its chain), upos the running sum of the
+ * sizes <= 65536.  d_true_sizes (device, one per member, or NULL) replaces the footers' sizes before the sum.  q_index[k] / q_upos[k]: the
+ * member whose header starts at q_coff[k] (n_members and ~0 when there is none); stop: the first member at or behind q_index[0] that is empty
+ * or larger than 65536 (0xffffffff: none).  bam_len == 0 or a file without candidates gives counts of 0, not an error.  RGX_ERR_DEVICE also
+ * when the candidate fill or the member fill wrote behind its count. */
+typedef struct {
+    uint64_t n_candidates, n_members, total_inflated;
+    uint64_t *candidates; rgx_member *members;
+    uint64_t q_upos[3]; uint32_t q_index[3], stop;
+} rgx_members_result;
+int  rgx_k_members(rgx_ctx *ctx, const void *d_bam, uint64_t bam_len, uint64_t root2, const uint32_t *d_true_sizes, const uint64_t *q_coff,
+                   rgx_members_result **out, char *err, size_t errlen);
+void rgx_members_result_free(rgx_members_result *r);
 /* d_perm_out = the positions 0 .. n-1 in stable order of the key whose word k (k = 0 the LEAST significant) is the low nbits[k] (1 .. 32) bits of
  * d_words[k][position]; d_words and nbits are host arrays of n_words entries.  mode = how the sort is driven, word by word: 0 = plain passes that
  * gather the word through the permutation, 1 = the word gathered once and its passes keyed, 2 = keyed passes on a word the caller's gather

@@ -52,7 +52,7 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_pipeline_create", "rgx_pipeline_depth", "rgx_pipeline_ctx", "rgx_extract_submit", "rgx_extract_wait", "rgx_pipeline_destroy",
            "rgx_cohort_params_default", "rgx_cohort_create", "rgx_cohort_add", "rgx_cohort_add_path", "rgx_cohort_finish", "rgx_cohort_destroy",
            "rgx_cohort_matrix_free", "rgx_cohort_merge_host", "rgx_cohort_format_bed12", "rgx_cohort_format_counts",
-           "rgx_k_scan_u32", "rgx_k_radix_sort", "rgx_k_group_by",
+           "rgx_k_scan_u32", "rgx_k_members", "rgx_members_result_free", "rgx_k_radix_sort", "rgx_k_group_by",
            "rgx_cluster_params_default", "rgx_cohort_cluster", "rgx_cohort_cluster_path", "rgx_cohort_cluster_host", "rgx_cohort_clusters_free",
            "rgx_cohort_format_cluster_counts", "rgx_k_components",
            "rgx_refine_params_default", "rgx_cohort_refine", "rgx_cohort_refine_host",
@@ -198,6 +198,11 @@ class PairList(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_batches", C.c_uint32), ("first", C.POINTER(C.c_uint32)), ("window", C.POINTER(C.c_uint32))]
 
 
+class MembersResult(C.Structure):
+    _fields_ = [("n_candidates", C.c_uint64), ("n_members", C.c_uint64), ("total_inflated", C.c_uint64), ("candidates", C.POINTER(C.c_uint64)),
+                ("members", C.POINTER(Member)), ("q_upos", C.c_uint64 * 3), ("q_index", C.c_uint32 * 3), ("stop", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -268,6 +273,8 @@ def lib():
         L.rgx_k_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rgx_k_inflate_form.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rgx_k_scan_u32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+        L.rgx_k_members.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, P(C.c_uint64), P(P(MembersResult)), C.c_char_p, C.c_size_t]
+        L.rgx_members_result_free.argtypes = [P(MembersResult)]
         L.rgx_k_radix_sort.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p), P(C.c_uint32), C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
         L.rgx_k_group_by.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p,
                                      P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]

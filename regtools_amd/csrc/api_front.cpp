@@ -260,7 +260,7 @@ int EventsRun::stage_upload() {
 int EventsRun::stage_members() {
     // -- BGZF member discovery on the device (replaces the serial BSIZE walk, bgzf.c:421-546) -------------------------------
     std::vector<Member> &hm = c->hm_scratch;
-    DevBuf &b_members = c->buf(Buf::members), &b_disc = c->buf(Buf::discover);
+    DevBuf &b_members = c->buf(Buf::members);
     if (overlap) {
         // the member list came from the host scan: what the discovery kernels would have left in HBM.  It goes there from page-locked host memory
         // by a kernel on the pipeline's stream, one coalesced pass (a copy would queue behind the file's chunks on the copy engine, measured 4 ms).
@@ -281,33 +281,15 @@ int EventsRun::stage_members() {
         HIP_TRY(hipMemcpyAsync(&d_sc->n_members, &h_sc->n_members, 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(&d_sc->total_inflated, &h_sc->total_inflated, 8, hipMemcpyHostToDevice, st));
     } else {
-    const uint32_t n_tiles = (uint32_t)((bam_len + kMagicTile - 1) / kMagicTile);
-    HIP_TRY(b_disc.ensure((size_t)n_tiles * 4 + scan_tmp_words(n_tiles) * 4 + 256));
-    Carve wd(b_disc);
-    uint32_t *tile_cnt = wd.u32(n_tiles), *tile_tmp = wd.u32(scan_tmp_words(n_tiles)); CARVE_TRY(wd, "discover");
-    launch_magic_count(d_bam, bam_len, n_tiles, tile_cnt, st);
-    launch_scan_u32(tile_cnt, tile_cnt, n_tiles, &d_sc->n_cand, tile_tmp, st);
-    HIP_TRY(fetch(h_sc->n_cand));
-    HIP_TRY(hipStreamSynchronize(st));
-    n_cand = h_sc->n_cand;
-    if (n_cand == 0) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);
-    DevBuf &b_cand = c->buf(Buf::cand);
-    {
-        const size_t N = n_cand;
-        HIP_TRY(b_cand.ensure(N * 8 + N * 4 * 6 + scan_tmp_words(n_cand) * 4 + 256));
-        HIP_TRY(b_members.ensure((N + 1) * sizeof(Member)));
-    }
-    Carve wc(b_cand);
-    cand = wc.u64(n_cand);
-    nx[0] = wc.u32(n_cand); nx[1] = wc.u32(n_cand);
-    c_isize = wc.u32(n_cand); c_reach = wc.u32(n_cand); c_rank = wc.u32(n_cand); c_isz2 = wc.u32(n_cand); c_tmp = wc.u32(scan_tmp_words(n_cand));
-    CARVE_TRY(wc, "cand");
-    launch_magic_fill(d_bam, bam_len, n_tiles, tile_cnt, cand, st);
+        disc.c = c; disc.st = st; disc.d_bam = d_bam; disc.bam_len = bam_len; disc.d_true_sizes = d_true_sizes; disc.d_sc = d_sc; disc.h_sc = h_sc;
+        { const int rc = disc.candidates(/*guarded=*/false, err, errlen); if (rc != kGoOn) return rc; }
+        n_cand = disc.n_cand;
+        if (n_cand == 0) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);
     }
     d_members = b_members.as<Member>();
     h_members = overlap ? (const Member *)c->pinned_members : nullptr;
     from_members = overlap ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
-    if (!overlap) chain(UINT64_MAX);
+    if (!overlap) disc.chain(UINT64_MAX);
     if (bai_thread.joinable()) bai_thread.join();
     if (!bai_ok) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_INDEX, "%s", kMsgIndex);
     mark("parse_bai");
@@ -403,17 +385,7 @@ int EventsRun::stage_members() {
             h_sc->stop = stop_; h_sc->n_members = nm; h_sc->total_inflated = hm_total;
             return hipSuccess;
         }
-        memcpy(h_sc->q_coff, q, sizeof q);
-        hipError_t e = hipMemcpyAsync(d_sc->q_coff, h_sc->q_coff, sizeof q, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(&d_sc->stop, 0xff, 4, st);
-        if (e != hipSuccess) return e;
-        launch_member_query(d_members, &d_sc->n_members, d_sc->q_coff, 3, d_sc->q_index, d_sc->q_upos, st);
-        // the stream ends at the first empty (or oversized = corrupt) member at/after the first one read (bgzf.c:548-578)
-        launch_member_stop(d_members, n_cand, &d_sc->n_members, d_sc->q_index, &d_sc->stop, st);
-        e = hipMemcpyAsync(h_sc, d_sc, kScalarsQueryPart, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(st);
+        return disc.query(q);
     };
     HIP_TRY(query());
     if (overlap && seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
@@ -429,13 +401,13 @@ int EventsRun::stage_members() {
     if (seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
         // the seek target is no member of the chain from offset 0: something in front of it is broken.  bgzf_seek (hts_itr_next, hts.c:1935)
         // goes there regardless -- take it as a second chain root.  (Only damaged files get here.)
-        chain(seek_voff >> 16);
+        disc.chain(seek_voff >> 16);
         HIP_TRY(query());
         mark("second chain root");
         if (h_sc->q_index[0] >= h_sc->n_members) {
             // there is no BGZF member at the seek target at all (a truncated file, an index that belongs to another file): the
             // reference's read after bgzf_seek fails and the iterator returns nothing.  Keep the head of the file for the header only.
-            chain(UINT64_MAX);
+            disc.chain(UINT64_MAX);
             seek = false; cut_lo = 0; cut_hi = 1; empty_stream = true;
             HIP_TRY(query());
         }

@@ -432,6 +432,74 @@ int prepare_events(rgx_ctx *c, const uint8_t *d_bam_in, const uint8_t *h_bam, si
 
 constexpr int kGoOn = -1;                                  // a stage of EventsRun: nothing to report, the next one
 
+// BGZF member discovery over a file that lies in HBM (kernels.hip a1), in the form its two callers share: EventsRun::stage_members, and the stage entry
+// rgx_k_members (api_stage.cpp) that hands it files no compressor writes.  candidates() costs one host wait (the candidate count sizes the buffers),
+// query() the other; chain() only enqueues.  `guarded` (the stage entry) puts kGuardWords behind the candidate list and behind the room of the member
+// list and arms them in front of the fill: the only launches the product's call does not make.
+struct MemberDiscovery {
+    rgx_ctx *c = nullptr; hipStream_t st = nullptr;
+    const uint8_t *d_bam = nullptr; size_t bam_len = 0;
+    const uint32_t *d_true_sizes = nullptr;                   // second run of a file whose footers lie: lengths from the probe (or NULL)
+    Scalars *d_sc = nullptr, *h_sc = nullptr;
+    uint32_t n_cand = 0;
+    uint64_t *cand = nullptr;
+    uint32_t *nx[2] = {nullptr, nullptr}, *c_isize = nullptr, *c_reach = nullptr, *c_rank = nullptr, *c_isz2 = nullptr, *c_tmp = nullptr;
+    Member *d_members = nullptr;
+    StageGuard g_cand, g_members;
+    // every offset that carries the ten fixed header bytes, in file order: cand[0 .. n_cand).  n_cand == 0 enqueues nothing more and is the caller's to judge.
+    int candidates(bool guarded, char *err, size_t errlen) {
+        DevBuf &b_disc = c->buf(Buf::discover), &b_cand = c->buf(Buf::cand), &b_members = c->buf(Buf::members);
+        const uint32_t n_tiles = (uint32_t)((bam_len + kMagicTile - 1) / kMagicTile);
+        HIP_TRY(b_disc.ensure((size_t)n_tiles * 4 + scan_tmp_words(n_tiles) * 4 + 256));
+        Carve wd(b_disc);
+        uint32_t *tile_cnt = wd.u32(n_tiles), *tile_tmp = wd.u32(scan_tmp_words(n_tiles)); CARVE_TRY(wd, "discover");
+        launch_magic_count(d_bam, bam_len, n_tiles, tile_cnt, st);
+        launch_scan_u32(tile_cnt, tile_cnt, n_tiles, &d_sc->n_cand, tile_tmp, st);
+        HIP_TRY(fetch_scalar(d_sc, h_sc, h_sc->n_cand, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_cand = h_sc->n_cand;
+        if (n_cand == 0) return kGoOn;
+        const size_t N = n_cand, guard_bytes = guarded ? kGuardWords * 4 : 0;
+        HIP_TRY(b_cand.ensure(N * 8 + N * 4 * 6 + scan_tmp_words(n_cand) * 4 + guard_bytes + 256));
+        HIP_TRY(b_members.ensure((N + 1) * sizeof(Member) + guard_bytes));
+        Carve wc(b_cand);
+        cand = wc.u64(n_cand);
+        uint32_t *guard_at = guarded ? wc.u32(kGuardWords) : nullptr;
+        nx[0] = wc.u32(n_cand); nx[1] = wc.u32(n_cand);
+        c_isize = wc.u32(n_cand); c_reach = wc.u32(n_cand); c_rank = wc.u32(n_cand); c_isz2 = wc.u32(n_cand); c_tmp = wc.u32(scan_tmp_words(n_cand));
+        CARVE_TRY(wc, "cand");
+        d_members = b_members.as<Member>();
+        if (guarded) { g_cand.arm(guard_at, st); g_members.arm((uint32_t *)(d_members + N), st); }      // (a list of n_cand members ends there)
+        launch_magic_fill(d_bam, bam_len, n_tiles, tile_cnt, cand, st);
+        return kGoOn;
+    }
+    // the members = the candidates that chain up from offset 0 (and, second try of stage_members, from the offset a seek lands on)
+    void chain(uint64_t root2) {
+        launch_member_link(d_bam, bam_len, cand, n_cand, nx[0], c_isize, c_reach, root2, st);
+        int cur = 0;
+        for (uint32_t span = 1; span < n_cand; span <<= 1) { launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st); cur ^= 1; }
+        launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st);
+        launch_scan_u32(c_reach, c_rank, n_cand, &d_sc->n_members, c_tmp, st);
+        launch_member_compact(d_bam, bam_len, cand, c_isize, c_reach, c_rank, n_cand, d_members, c_isz2, st);
+        if (d_true_sizes) launch_member_fix(d_members, c_isz2, n_cand, &d_sc->n_members, d_true_sizes, st);   // second run: lengths from the probe, not the footers
+        launch_member_upos(d_members, c_isz2, &d_sc->n_members, &d_sc->total_inflated, st);
+    }
+    // the members at three compressed offsets, and where the stream ends; the front of the scalar block is in *h_sc when this returns
+    hipError_t query(const uint64_t q[3]) {
+        memcpy(h_sc->q_coff, q, sizeof h_sc->q_coff);
+        hipError_t e = hipMemcpyAsync(d_sc->q_coff, h_sc->q_coff, sizeof h_sc->q_coff, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        e = hipMemsetAsync(&d_sc->stop, 0xff, 4, st);
+        if (e != hipSuccess) return e;
+        launch_member_query(d_members, &d_sc->n_members, d_sc->q_coff, 3, d_sc->q_index, d_sc->q_upos, st);
+        // the stream ends at the first empty (or oversized = corrupt) member at/after the first one read (bgzf.c:548-578)
+        launch_member_stop(d_members, n_cand, &d_sc->n_members, d_sc->q_index, &d_sc->stop, st);
+        e = hipMemcpyAsync(h_sc, d_sc, kScalarsQueryPart, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+        return hipStreamSynchronize(st);
+    }
+};
+
 // One call of the front half of the pipeline: file bytes -> junction events in file order.  The stages run in the order of
 // run(); each returns kGoOn, or the call's result (an error, or the result of the call starting over on another path: a file whose footers
 // lie, a record the lite walk must not accept, a shard whose range was not uploaded).  What one stage leaves for the next are the members below.
@@ -477,23 +545,11 @@ struct EventsRun {
     }
     // stage_members: the member list (device discovery, or the host scan's), the record stream's start, cuts and chunks
     uint32_t n_cand = 0;
-    uint64_t *cand = nullptr;
-    uint32_t *nx[2] = {nullptr, nullptr}, *c_isize = nullptr, *c_reach = nullptr, *c_rank = nullptr, *c_isz2 = nullptr, *c_tmp = nullptr;
+    MemberDiscovery disc;                                     // (the device's discovery; unused when the list is the host scan's)
     Member *d_members = nullptr; hipMemcpyKind from_members = hipMemcpyDeviceToHost;
     // the host scan's list has two copies: the page-locked one the host reads (h_members) and the one in HBM the kernels read (d_members)
     const Member *h_members = nullptr;
     const Member *members_src() const { return h_members ? h_members : d_members; }      // what a copy of kind from_members to the host reads
-    // the members = the candidates that chain up from offset 0 (and, second try below, from the offset a seek lands on)
-    void chain(uint64_t root2) {
-        launch_member_link(d_bam, bam_len, cand, n_cand, nx[0], c_isize, c_reach, root2, st);
-        int cur = 0;
-        for (uint32_t span = 1; span < n_cand; span <<= 1) { launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st); cur ^= 1; }
-        launch_member_jump(n_cand, nx[cur], nx[cur ^ 1], c_reach, st);
-        launch_scan_u32(c_reach, c_rank, n_cand, &d_sc->n_members, c_tmp, st);
-        launch_member_compact(d_bam, bam_len, cand, c_isize, c_reach, c_rank, n_cand, d_members, c_isz2, st);
-        if (d_true_sizes) launch_member_fix(d_members, c_isz2, n_cand, &d_sc->n_members, d_true_sizes, st);   // second run: lengths from the probe, not the footers
-        launch_member_upos(d_members, c_isz2, &d_sc->n_members, &d_sc->total_inflated, st);
-    }
     bool whole = false, seek = false, chunked = false, geom_chunked_hint = false, empty_stream = false;
     uint64_t seek_voff = 0, cut_lo = 0, cut_hi = UINT64_MAX, total_all = 0, q_upos[3] = {0, 0, 0};
     std::vector<VChunk> chunks;

@@ -26,6 +26,55 @@ extern "C" int rgx_k_scan_u32(rgx_ctx *c, const uint32_t *d_in, uint32_t *d_out,
     return RGX_OK;
 }
 
+// BGZF member discovery (kernels.hip a1) on the caller's file in HBM (tests/test_gpu_member_discovery.py): MemberDiscovery is what stage_members runs, the
+// scalar block is prepared the way stage_upload prepares it.  The candidate list and the member list have guard words behind them.
+extern "C" int rgx_k_members(rgx_ctx *c, const void *d_bam, uint64_t bam_len, uint64_t root2, const uint32_t *d_true_sizes, const uint64_t *q_coff,
+                             rgx_members_result **out, char *err, size_t errlen) {
+    if (!c || !out || !q_coff || (bam_len && !d_bam)) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: bad arguments\n");
+    *out = nullptr;
+    rgx_members_result *r = (rgx_members_result *)calloc(1, sizeof *r);
+    if (!r) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: out of memory\n");
+    struct Holder { rgx_members_result *r; ~Holder() { rgx_members_result_free(r); } } hold{r};
+    r->candidates = (uint64_t *)malloc(8); r->members = (rgx_member *)malloc(sizeof(rgx_member));
+    for (int k = 0; k < 3; ++k) { r->q_index[k] = 0; r->q_upos[k] = ~0ull; }
+    r->stop = 0xffffffffu;
+    if (bam_len) {
+        HIP_ENTER(c->device);
+        hipStream_t st = c->stream;
+        DevBuf &b_scalars = c->buf(Buf::scalars);
+        HIP_TRY(b_scalars.ensure(sizeof(Scalars)));
+        MemberDiscovery md;
+        md.c = c; md.st = st; md.d_bam = (const uint8_t *)d_bam; md.bam_len = bam_len; md.d_true_sizes = d_true_sizes;
+        md.d_sc = b_scalars.as<Scalars>(); md.h_sc = (Scalars *)c->pinned;
+        HIP_TRY(hipMemsetAsync(md.d_sc, 0, sizeof(Scalars), st));
+        { const int rc = md.candidates(/*guarded=*/true, err, errlen); if (rc != kGoOn) return rc; }
+        if (md.n_cand) {
+            md.chain(UINT64_MAX);
+            if (root2 != UINT64_MAX) md.chain(root2);
+            HIP_TRY(md.query(q_coff));
+            const Scalars &h = *md.h_sc;
+            if (h.n_members > md.n_cand) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: %u members of %u candidates\n", h.n_members, md.n_cand);
+            r->n_candidates = md.n_cand; r->n_members = h.n_members; r->total_inflated = h.total_inflated; r->stop = h.stop;
+            for (int k = 0; k < 3; ++k) { r->q_index[k] = h.q_index[k]; r->q_upos[k] = h.q_upos[k]; }
+            free(r->candidates); free(r->members);
+            r->candidates = (uint64_t *)malloc((size_t)md.n_cand * 8 + 8); r->members = (rgx_member *)malloc(((size_t)h.n_members + 1) * sizeof(rgx_member));
+            if (!r->candidates || !r->members) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: out of memory\n");
+            static_assert(sizeof(rgx_member) == sizeof(Member), "rgx_member is rgx::Member");
+            HIP_TRY(hipMemcpyAsync(r->candidates, md.cand, (size_t)md.n_cand * 8, hipMemcpyDeviceToHost, st));
+            if (r->n_members) HIP_TRY(hipMemcpyAsync(r->members, md.d_members, (size_t)r->n_members * sizeof(Member), hipMemcpyDeviceToHost, st));
+            bool past_cand = false, past_members = false;
+            HIP_TRY(md.g_cand.check(st, &past_cand));
+            HIP_TRY(md.g_members.check(st, &past_members));
+            if (past_cand) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the candidate fill wrote behind its %u candidates\n", md.n_cand);
+            if (past_members) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the member fill wrote behind the room of %u members\n", md.n_cand);
+        }
+    }
+    hold.r = nullptr;
+    *out = r;
+    return RGX_OK;
+}
+extern "C" void rgx_members_result_free(rgx_members_result *r) { if (!r) return; free(r->candidates); free(r->members); free(r); }
+
 extern "C" int rgx_k_radix_sort(rgx_ctx *c, uint32_t n, uint32_t n_scratch, uint32_t n_words, const uint32_t *const *d_words, const uint32_t *nbits,
                                 int mode, uint32_t *d_perm_out, char *err, size_t errlen) {
     if (!c || !n_words || !d_words || !nbits || mode < 0 || mode > 2 || (n && !d_perm_out)) return fail(err, errlen, RGX_ERR_ARG,
