@@ -16,20 +16,66 @@ def _params(only_anchored, min_samples, min_total):
     return p
 
 
-def _text(fn, handle):
-    n = fn(handle, None, 0)
+def _text(fn, *args):
+    """fn(*args, buf, cap) twice: once for the size, once into a buffer of it."""
+    n = fn(*args, None, 0)
     buf = C.create_string_buffer(n + 1)
-    fn(handle, buf, n)
+    fn(*args, buf, n)
     return buf.raw[:n]
 
 
-class CohortMatrix(object):
-    """rgx_cohort_matrix.  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+def _call(fn, out_type, wrap, *args):
+    """fn(*args, &out, err, len(err)) with out a pointer to out_type: RegtoolsError on a code, else wrap(out)."""
+    out = C.POINTER(out_type)()
+    err = C.create_string_buffer(512)
+    rc = fn(*args, C.byref(out), err, len(err))
+    if rc != 0:
+        raise RegtoolsError(rc, err.value.decode())
+    return wrap(out)
+
+
+class _Owned(object):
+    """A result handle the library allocated and this object owns: _free names the function that gives it back."""
+    _free = None
 
     def __init__(self, handle):
-        import numpy as np               # (only the matrix needs it: importing the package does not)
         self._lib = _ffi.lib()
         self._h = handle
+
+    @staticmethod
+    def _view(ptr, k, dtype):
+        import numpy as np               # (only the results need it: importing the package does not)
+        return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+
+    def close(self):
+        if self._h:
+            getattr(self._lib, self._free)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _qtl_text(fn, result, matrix, clusters, ph, var_pos, variant_ids):
+    import numpy as np
+    pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+    ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
+    if len(pos) != result.n_variants or len(variant_ids) != result.n_variants:
+        raise ValueError("one position and one id per variant")
+    return _text(fn, matrix._h, clusters._h, ph._h, result._h, pos.ctypes.data, ids)
+
+
+class CohortMatrix(_Owned):
+    """rgx_cohort_matrix.  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
+
+    _free = "rgx_cohort_matrix_free"
+
+    def __init__(self, handle):
+        import numpy as np
+        _Owned.__init__(self, handle)
         m = handle.contents
         self.n, self.n_samples, self.n_triples = int(m.n), int(m.n_samples), int(m.n_triples)
         self.ms_add_total, self.ms_finish = m.ms_add_total, m.ms_finish
@@ -37,9 +83,7 @@ class CohortMatrix(object):
         self.ref_len = [int(m.ref_len[i]) for i in range(m.n_ref)]
         self.sample_name = [m.sample_name[i].decode() for i in range(m.n_samples)]
         nnz = int(m.row_begin[self.n])
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         self.tid, self.start, self.end = view(m.tid, self.n, np.uint32), view(m.start, self.n, np.uint32), view(m.end, self.n, np.uint32)
         self.thick_start, self.thick_end = view(m.thick_start, self.n, np.uint32), view(m.thick_end, self.n, np.uint32)
         self.n_with, self.total = view(m.n_with, self.n, np.uint32), view(m.total, self.n, np.uint64)
@@ -64,33 +108,21 @@ class CohortMatrix(object):
     def counts_tsv(self):
         return _text(self._lib.rgx_cohort_format_counts, self._h)
 
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_matrix_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CohortClusters(object):
+class CohortClusters(_Owned):
     """rgx_cohort_clusters: the intron clusters of a matrix (rows linked through a shared start or end) and, per cluster and sample, the reads on
     it.  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
 
+    _free = "rgx_cohort_clusters_free"
+
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         c = handle.contents
         self.n_rows, self.n_clusters, self.n_components = int(c.n_rows), int(c.n_clusters), int(c.n_components)
         self.n_rounds, self.ms_cluster = int(c.n_rounds), c.ms_cluster
         self.n_ineligible, self.n_weak = int(c.n_ineligible), int(c.n_weak)          # (0, 0 unless the clusters are refined ones)
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         self.cluster = view(c.cluster, self.n_rows, np.uint32)
         self.cl_begin = np.ctypeslib.as_array(c.cl_begin, shape=(self.n_clusters + 1,))
         self.cs_begin = np.ctypeslib.as_array(c.cs_begin, shape=(self.n_clusters + 1,))
@@ -99,22 +131,7 @@ class CohortClusters(object):
 
     def counts_text(self, matrix):
         """The cluster counts of `matrix` (the CohortMatrix these clusters were made from) in the layout of LeafCutter's perind.counts."""
-        fn = self._lib.rgx_cohort_format_cluster_counts
-        n = fn(matrix._h, self._h, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, self._h, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_clusters_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _text(self._lib.rgx_cohort_format_cluster_counts, matrix._h, self._h)
 
 
 def _cluster_params(min_rows, min_total):
@@ -127,12 +144,7 @@ def _cluster_params(min_rows, min_total):
 def cluster_host(matrix, min_rows=1, min_total=0):
     """rgx_cohort_cluster_host: the clusters of a CohortMatrix by the library's plain C++ twin, no device involved."""
     p = _cluster_params(min_rows, min_total)
-    out = C.POINTER(_ffi.CohortClusters)()
-    err = C.create_string_buffer(512)
-    rc = _ffi.lib().rgx_cohort_cluster_host(matrix._h, C.byref(p), C.byref(out), err, len(err))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortClusters(out)
+    return _call(_ffi.lib().rgx_cohort_cluster_host, _ffi.CohortClusters, CohortClusters, matrix._h, C.byref(p))
 
 
 def _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total):
@@ -146,29 +158,23 @@ def refine_host(matrix, max_intron=0, min_reads=0, min_ratio=(0, 1), min_rows=1,
     """rgx_cohort_refine_host: the refined clusters of a CohortMatrix by the library's plain C++ twin, no device involved.  min_ratio is an exact
     fraction (numerator, denominator)."""
     p = _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total)
-    out = C.POINTER(_ffi.CohortClusters)()
-    err = C.create_string_buffer(512)
-    rc = _ffi.lib().rgx_cohort_refine_host(matrix._h, C.byref(p), C.byref(out), err, len(err))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortClusters(out)
+    return _call(_ffi.lib().rgx_cohort_refine_host, _ffi.CohortClusters, CohortClusters, matrix._h, C.byref(p))
 
 
-class CohortPhenotypes(object):
+class CohortPhenotypes(_Owned):
     """rgx_pheno_table: the splicing phenotype table of a clustered matrix -- the kept rows, their missing samples, mean and sd of the
     intron-excision ratio, and rank2 (K x S), twice the average rank of each standardised entry in its sample's column.  The array attributes
     are numpy VIEWS of memory this object owns: copy what must outlive it."""
 
+    _free = "rgx_cohort_phenotypes_free"
+
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         p = handle.contents
         self.n_rows, self.n_samples = int(p.n_rows), int(p.n_samples)
         self.n_clustered, self.n_drop_na, self.n_drop_sd, self.ms_pheno = int(p.n_clustered), int(p.n_drop_na), int(p.n_drop_sd), p.ms_pheno
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         K = self.n_rows
         self.row, self.n_na = view(p.row, K, np.uint32), view(p.n_na, K, np.uint32)
         self.mean, self.sd = view(p.mean, K, np.float64), view(p.sd, K, np.float64)
@@ -183,22 +189,7 @@ class CohortPhenotypes(object):
 
     def text(self, matrix, clusters):
         """The table as text: "#Chr start end ID" and the samples, one line per kept row.  matrix and clusters are what this came from."""
-        fn = self._lib.rgx_cohort_format_phenotypes
-        n = fn(matrix._h, clusters._h, self._h, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, clusters._h, self._h, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_phenotypes_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _text(self._lib.rgx_cohort_format_phenotypes, matrix._h, clusters._h, self._h)
 
 
 def quantile(rank2, n_rows):
@@ -217,23 +208,19 @@ def phenotypes_host(matrix, clusters, max_missing=(4, 10), min_sd=0.005):
     """rgx_cohort_phenotypes_host: the phenotype table of a CohortMatrix and its CohortClusters by the library's plain C++ twin, no device
     involved.  max_missing is an exact fraction (numerator, denominator)."""
     p = _pheno_params(max_missing, min_sd)
-    out = C.POINTER(_ffi.PhenoTable)()
-    err = C.create_string_buffer(512)
-    rc = _ffi.lib().rgx_cohort_phenotypes_host(matrix._h, clusters._h, C.byref(p), C.byref(out), err, len(err))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortPhenotypes(out)
+    return _call(_ffi.lib().rgx_cohort_phenotypes_host, _ffi.PhenoTable, CohortPhenotypes, matrix._h, clusters._h, C.byref(p))
 
 
-class CohortPCs(object):
+class CohortPCs(_Owned):
     """rgx_pheno_pcs: the principal components of a phenotype table -- col_sum (S) and gram (S x S) of its quantiles, variance (all S eigenvalues
     of their covariance, descending) and component (n_pcs x S, unit length, the largest entry positive).  The array attributes are numpy VIEWS of
     memory this object owns: copy what must outlive it."""
 
+    _free = "rgx_cohort_pheno_pcs_free"
+
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         p = handle.contents
         self.n_rows, self.n_samples, self.n_pcs = int(p.n_rows), int(p.n_samples), int(p.n_pcs)
         self.ms_pcs, self.ms_gram, self.ms_eigen = p.ms_pcs, p.ms_gram, p.ms_eigen
@@ -245,43 +232,26 @@ class CohortPCs(object):
 
     def text(self, matrix):
         """The components as text, LeafCutter's .PCs layout: "id" and the samples of `matrix`, one line per component."""
-        fn = self._lib.rgx_cohort_format_pheno_pcs
-        n = fn(matrix._h, self._h, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, self._h, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_pheno_pcs_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _text(self._lib.rgx_cohort_format_pheno_pcs, matrix._h, self._h)
 
 
-class CohortQTL(object):
+class CohortQTL(_Owned):
     """rgx_qtl_result: the nominal cis-sQTL scan of a phenotype table -- per variant its verdict (0 usable, 1 constant, 2 explained by the
     covariates) and gg, per row yy, the pairs as a CSR (pair_begin, pair_variant) with r and slope, and per row its best pair (NO_PAIR: none).
     The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
     NO_PAIR = 0xffffffff
+    _free = "rgx_cohort_qtl_free"
 
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         p = handle.contents
         self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
         self.n_cov, self.dof, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_pairs)
         self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
         self.n_tiles = int(p.n_tiles)
         self.ms_qtl, self.ms_residual, self.ms_pairs = p.ms_qtl, p.ms_residual, p.ms_pairs
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         K, V, n = self.n_rows, self.n_variants, self.n_pairs
         self.variant_verdict = view(p.variant_verdict, V, np.uint8)
         self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
@@ -291,27 +261,7 @@ class CohortQTL(object):
     def text(self, matrix, clusters, ph, var_pos, variant_ids):
         """The pairs as text: phenotype_id, variant_id, distance, r, slope, slope_se, tstat, pval_nominal, is_best; one line per pair.  matrix,
         clusters and ph are what the scan came from; var_pos and variant_ids (str or bytes) are per input variant."""
-        import numpy as np
-        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
-        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
-        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
-            raise ValueError("one position and one id per variant")
-        fn = self._lib.rgx_cohort_format_qtl
-        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_qtl_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _qtl_text(self._lib.rgx_cohort_format_qtl, self, matrix, clusters, ph, var_pos, variant_ids)
 
 
 class Genotypes(object):
@@ -375,13 +325,8 @@ def _qtl_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, wind
         raise ValueError("one region per table row, one position and one row of dosages per variant")
     if not 0 <= int(window) <= 0xffffffff:
         raise ValueError("window must fit 32 bits")
-    out = C.POINTER(_ffi.QtlResult)()
-    err = C.create_string_buffer(512)
-    rc = fn(*(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
-                       C.byref(out), err, len(err))))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortQTL(out)
+    return _call(fn, _ffi.QtlResult, CohortQTL, *(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov),
+                                                          cov.ctypes.data, int(window))))
 
 
 def qtl_nominal_host(ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000):
@@ -390,26 +335,24 @@ def qtl_nominal_host(ph, regions, var_tid, var_pos, dosage, covariates=None, win
     return _qtl_call(_ffi.lib().rgx_cohort_qtl_nominal_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window)
 
 
-class CohortQTLPerm(object):
+class CohortQTLPerm(_Owned):
     """rgx_qtl_perm_result: the permutation pass of the cis-sQTL scan -- per variant its verdict and gg, per row yy, n_cis (its pairs), perm_r
     (K x (B + 1): the largest |r| over its cis variants under the identity and the B permutations), the best pair of the identity (best_variant, an
     input variant or NO_PAIR; best_r, best_slope), n_ge, p_perm, and the beta approximation (beta_shape1, beta_shape2, p_beta, beta_status: 0
     converged, 1 moment estimates, 2 no fit).  The array attributes are numpy VIEWS of memory this object owns: copy what must outlive it."""
     NO_PAIR = 0xffffffff
+    _free = "rgx_cohort_qtl_perm_free"
 
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         p = handle.contents
         self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
         self.n_cov, self.dof, self.n_perm, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_perm), int(p.n_pairs)
         self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
         self.n_tiles = int(p.n_tiles)
         self.ms_perm, self.ms_residual, self.ms_products, self.ms_beta = p.ms_perm, p.ms_residual, p.ms_products, p.ms_beta
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         K, V, B1 = self.n_rows, self.n_variants, self.n_perm + 1
         self.variant_verdict = view(p.variant_verdict, V, np.uint8)
         self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
@@ -423,27 +366,7 @@ class CohortQTLPerm(object):
     def text(self, matrix, clusters, ph, var_pos, variant_ids):
         """One line per row that has pairs: phenotype_id, num_var, beta_shape1, beta_shape2, dof, variant_id, distance, r, slope, slope_se, tstat,
         pval_nominal, pval_perm, pval_beta.  The arguments are CohortQTL.text's."""
-        import numpy as np
-        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
-        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
-        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
-            raise ValueError("one position and one id per variant")
-        fn = self._lib.rgx_cohort_format_qtl_perm
-        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_qtl_perm_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _qtl_text(self._lib.rgx_cohort_format_qtl_perm, self, matrix, clusters, ph, var_pos, variant_ids)
 
 
 def qtl_permutations(n_samples, n_perm, seed=0):
@@ -503,7 +426,6 @@ def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates,
         n_perm = len(pm) - 1
         if n_perm < 0:
             raise ValueError("perms needs the identity as its row 0")
-    err = C.create_string_buffer(512)
     shared = front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
                       n_perm, pm.ctypes.data)
     if groups is not None:
@@ -512,16 +434,8 @@ def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates,
             raise ValueError("one group per table row")
         if not 0 <= int(n_groups) <= 0xffffffff:
             raise ValueError("n_groups must fit 32 bits")
-        out = C.POINTER(_ffi.QtlGroupResult)()
-        rc = fn(*(shared + (int(n_groups), grp.ctypes.data, C.byref(out), err, len(err))))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
-        return CohortQTLGroup(out)
-    out = C.POINTER(_ffi.QtlPermResult)()
-    rc = fn(*(shared + (C.byref(out), err, len(err))))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortQTLPerm(out)
+        return _call(fn, _ffi.QtlGroupResult, CohortQTLGroup, *(shared + (int(n_groups), grp.ctypes.data)))
+    return _call(fn, _ffi.QtlPermResult, CohortQTLPerm, *shared)
 
 
 def qtl_permute_host(ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0, perms=None):
@@ -530,7 +444,7 @@ def qtl_permute_host(ph, regions, var_tid, var_pos, dosage, covariates=None, win
     return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms)
 
 
-class CohortQTLGroup(object):
+class CohortQTLGroup(_Owned):
     """rgx_qtl_group_result: the grouped permutation pass of the cis-sQTL scan -- per variant its verdict and gg, per row yy and n_cis, the
     groups' member lists (grp_begin, grp_row), and per group group_n_cis, perm_r (G x (B + 1): the largest |r| over all members' cis variants
     under the identity and the B permutations), the best pair of the identity (best_row, a table row, and best_variant, an input variant, or
@@ -538,20 +452,18 @@ class CohortQTLGroup(object):
     are numpy VIEWS of memory this object owns: copy what must outlive it."""
     NO_PAIR = 0xffffffff
     NO_GROUP = 0xffffffff
+    _free = "rgx_cohort_qtl_group_free"
 
     def __init__(self, handle):
         import numpy as np
-        self._lib = _ffi.lib()
-        self._h = handle
+        _Owned.__init__(self, handle)
         p = handle.contents
         self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
         self.n_cov, self.dof, self.n_perm, self.n_groups, self.n_pairs = int(p.n_cov), int(p.dof), int(p.n_perm), int(p.n_groups), int(p.n_pairs)
         self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
         self.n_tiles = int(p.n_tiles)
         self.ms_perm, self.ms_residual, self.ms_products, self.ms_beta = p.ms_perm, p.ms_residual, p.ms_products, p.ms_beta
-
-        def view(ptr, k, dtype):
-            return np.ctypeslib.as_array(ptr, shape=(k,)) if k else np.zeros(0, dtype)
+        view = self._view
         K, V, G, B1 = self.n_rows, self.n_variants, self.n_groups, self.n_perm + 1
         self.variant_verdict = view(p.variant_verdict, V, np.uint8)
         self.yy, self.gg, self.n_cis = view(p.yy, K, np.float64), view(p.gg, V, np.float64), view(p.n_cis, K, np.uint32)
@@ -567,27 +479,7 @@ class CohortQTLGroup(object):
     def text(self, matrix, clusters, ph, var_pos, variant_ids):
         """One line per group that has pairs: group_id, group_size, then CohortQTLPerm.text's columns for the group's best pair with num_var =
         group_n_cis.  The arguments are CohortQTL.text's."""
-        import numpy as np
-        pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
-        ids = (C.c_char_p * max(len(variant_ids), 1))(*[v if isinstance(v, bytes) else v.encode() for v in variant_ids])
-        if len(pos) != self.n_variants or len(variant_ids) != self.n_variants:
-            raise ValueError("one position and one id per variant")
-        fn = self._lib.rgx_cohort_format_qtl_group
-        n = fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, None, 0)
-        buf = C.create_string_buffer(n + 1)
-        fn(matrix._h, clusters._h, ph._h, self._h, pos.ctypes.data, ids, buf, n)
-        return buf.raw[:n]
-
-    def close(self):
-        if self._h:
-            self._lib.rgx_cohort_qtl_group_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _qtl_text(self._lib.rgx_cohort_format_qtl_group, self, matrix, clusters, ph, var_pos, variant_ids)
 
 
 def pheno_groups(clusters, ph):
@@ -635,12 +527,7 @@ def pheno_table_from_rank2(rank2):
 
 def pheno_pcs_host(ph, n_pcs):
     """rgx_cohort_pheno_pcs_host: the first n_pcs principal components of a phenotype table by the library's plain C++ twin, no device involved."""
-    out = C.POINTER(_ffi.PhenoPCs)()
-    err = C.create_string_buffer(512)
-    rc = _ffi.lib().rgx_cohort_pheno_pcs_host(ph._h, n_pcs, C.byref(out), err, len(err))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortPCs(out)
+    return _call(_ffi.lib().rgx_cohort_pheno_pcs_host, _ffi.PhenoPCs, CohortPCs, ph._h, n_pcs)
 
 
 def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1):
@@ -651,12 +538,7 @@ def merge_host(extractors, names, only_anchored=True, min_samples=1, min_total=1
     anchors = (C.c_uint32 * max(n, 1))(*[je.min_anchor_length_ & 0xffffffff for je in extractors])
     nm = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
     p = _params(only_anchored, min_samples, min_total)
-    out = C.POINTER(_ffi.CohortMatrix)()
-    err = C.create_string_buffer(512)
-    rc = lib.rgx_cohort_merge_host(tabs, anchors, nm, n, C.byref(p), C.byref(out), err, len(err))
-    if rc != 0:
-        raise RegtoolsError(rc, err.value.decode())
-    return CohortMatrix(out)
+    return _call(lib.rgx_cohort_merge_host, _ffi.CohortMatrix, CohortMatrix, tabs, anchors, nm, n, C.byref(p))
 
 
 def _index_bytes(path):
@@ -698,60 +580,38 @@ class Cohort(object):
         return idx.value
 
     def finish(self):
-        out = C.POINTER(_ffi.CohortMatrix)()
-        err = C.create_string_buffer(512)
-        rc = self._lib.rgx_cohort_finish(self._h, C.byref(out), err, len(err))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
-        return CohortMatrix(out)
+        return _call(self._lib.rgx_cohort_finish, _ffi.CohortMatrix, CohortMatrix, self._h)
 
     def cluster(self, matrix, min_rows=1, min_total=0):
         """The intron clusters of `matrix` (any CohortMatrix) on this cohort's device.  The matrix of the most recent finish is read where it lies
         in HBM; any other one is uploaded."""
         p = _cluster_params(min_rows, min_total)
-        out = C.POINTER(_ffi.CohortClusters)()
-        err = C.create_string_buffer(512)
-        rc = self._lib.rgx_cohort_cluster(self._h, matrix._h, C.byref(p), C.byref(out), err, len(err))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
+        cl = _call(self._lib.rgx_cohort_cluster, _ffi.CohortClusters, CohortClusters, self._h, matrix._h, C.byref(p))
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
-        return CohortClusters(out)
+        return cl
 
     def refine(self, matrix, max_intron=0, min_reads=0, min_ratio=(0, 1), min_rows=1, min_total=0):
         """The refined clusters of `matrix` on this cohort's device (rgx_cohort_refine): introns longer than max_intron take no part, junctions
         with fewer than min_reads reads or less than min_ratio = (numerator, denominator) of their cluster's reads are removed, and the rest is
         clustered again.  The matrix is found as in cluster()."""
         p = _refine_params(max_intron, min_reads, min_ratio, min_rows, min_total)
-        out = C.POINTER(_ffi.CohortClusters)()
-        err = C.create_string_buffer(512)
-        rc = self._lib.rgx_cohort_refine(self._h, matrix._h, C.byref(p), C.byref(out), err, len(err))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
+        cl = _call(self._lib.rgx_cohort_refine, _ffi.CohortClusters, CohortClusters, self._h, matrix._h, C.byref(p))
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
-        return CohortClusters(out)
+        return cl
 
     def phenotypes(self, matrix, clusters, max_missing=(4, 10), min_sd=0.005):
         """The splicing phenotype table of `matrix` and its `clusters` on this cohort's device (rgx_cohort_phenotypes): intron-excision ratios,
         rows dropped when more than max_missing = (numerator, denominator) of the samples have no reads on the cluster or when their sd is
         below min_sd, each row standardised, each sample's column ranked.  The matrix is found as in cluster()."""
         p = _pheno_params(max_missing, min_sd)
-        out = C.POINTER(_ffi.PhenoTable)()
-        err = C.create_string_buffer(512)
-        rc = self._lib.rgx_cohort_phenotypes(self._h, matrix._h, clusters._h, C.byref(p), C.byref(out), err, len(err))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
+        ph = _call(self._lib.rgx_cohort_phenotypes, _ffi.PhenoTable, CohortPhenotypes, self._h, matrix._h, clusters._h, C.byref(p))
         self.cluster_paths.append(self._lib.rgx_cohort_cluster_path(self._h))
-        return CohortPhenotypes(out)
+        return ph
 
     def pheno_pcs(self, ph, n_pcs):
         """The first n_pcs principal components of the phenotype table `ph` on this cohort's device (rgx_cohort_pheno_pcs): the Gram matrix of
         its quantiles in HBM, the eigen-decomposition of their covariance on the host."""
-        out = C.POINTER(_ffi.PhenoPCs)()
-        err = C.create_string_buffer(512)
-        rc = self._lib.rgx_cohort_pheno_pcs(self._h, ph._h, n_pcs, C.byref(out), err, len(err))
-        if rc != 0:
-            raise RegtoolsError(rc, err.value.decode())
-        return CohortPCs(out)
+        return _call(self._lib.rgx_cohort_pheno_pcs, _ffi.PhenoPCs, CohortPCs, self._h, ph._h, n_pcs)
 
     def qtl_nominal(self, ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000):
         """The nominal cis-sQTL scan of the phenotype table `ph` on this cohort's device (rgx_cohort_qtl_nominal): residuals of rows and variants

@@ -394,8 +394,7 @@ hipError_t ensure_upload_streams(rgx_ctx *c);
 rgx_junction_table *table_alloc(const BamHeader &h, uint64_t n, bool zero = true, bool pinned = false);
 void host_sort_rows(rgx_junction_table *t);
 void format_bed12_rows(const rgx_junction_table *t, int only_anchored, uint64_t r0, uint64_t r1, std::string &out);
-void *block_take(size_t need, size_t &cap, bool pinned);
-void block_give(void *p, size_t cap, bool pinned);
+#include "result_block.h"                    // block_take / block_give, declared where the cohort results' boxes are
 // Result tables: all row columns of a table live in ONE block, and released blocks are kept (a few, bounded) for the next table.  A
 // pipeline that runs step after step -- bench.py, a multi-GPU job merging every step -- then writes its rows into pages that are already
 // mapped instead of paying mmap + first-touch faults + munmap for ~50 bytes per row each time (measured: 9 of 14 ms of an 8-shard merge).

@@ -16,21 +16,18 @@ inline bool anchored(const rgx_junction_table *t, uint64_t i, uint32_t min_ancho
 std::atomic<uint64_t> g_matrix_serial{0};
 
 rgx_cohort_matrix *matrix_alloc(const CohortContigs &c, const std::vector<std::string> &samples, uint64_t n, uint64_t nnz, bool pinned) {
-    MatrixBox *box = (MatrixBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
+    // the block is the device's image (matrix_layout): ONE array, the members pointed into it from L
     const MatrixLayout L = matrix_layout(n, nnz);
-    box->pinned = pinned; box->serial = ++g_matrix_serial;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    rgx_cohort_matrix *m = &box->m;
+    uint8_t *q = nullptr;
+    rgx_cohort_matrix *m = result_alloc<rgx_cohort_matrix, uint64_t>(pinned, [&](rgx_cohort_matrix &, BlockTake &take) { take(q, L.bytes); });
+    if (!m) return nullptr;
+    result_extra<uint64_t>(m) = ++g_matrix_serial;
     m->n_ref = (int32_t)c.names.size();
     m->ref_name = (char **)calloc(c.names.size() + 1, sizeof(char *)); m->ref_len = (uint32_t *)calloc(c.names.size() + 1, 4);
     for (size_t i = 0; i < c.names.size(); ++i) { m->ref_name[i] = strdup(c.names[i].c_str()); m->ref_len[i] = c.lens[i]; }
     m->n_samples = (uint32_t)samples.size();
     m->sample_name = (char **)calloc(samples.size() + 1, sizeof(char *));
     for (size_t i = 0; i < samples.size(); ++i) m->sample_name[i] = strdup(samples[i].c_str());
-    uint8_t *q = (uint8_t *)box->block;
     m->n = n;
     m->total = (uint64_t *)(q + L.total); m->row_begin = (uint64_t *)(q + L.row_begin); m->tid = (uint32_t *)(q + L.tid); m->start = (uint32_t *)(q + L.start);
     m->end = (uint32_t *)(q + L.end); m->thick_start = (uint32_t *)(q + L.ts); m->thick_end = (uint32_t *)(q + L.te); m->n_with = (uint32_t *)(q + L.n_with);
@@ -200,8 +197,7 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
     auto mark = [&](const char *what) { if (trace) { (void)hipStreamSynchronize(st); const double t = now_ms(); fprintf(stderr,
         "[rgx trace] cohort: %-28s +%8.3f ms\n", what, t - t_last); t_last = t; } };
     uint32_t filled = 0;
-    HIP_TRY(hipMemcpyAsync(&filled, co->d_fill, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                                   // (every append has run)
+    HIP_TRY(read_back(st, &filled, co->d_fill, 4));                      // (every append has run)
     co->up_pending = false;
     if (filled != co->n_triples) return fail(err, errlen, RGX_ERR_DEVICE,
         "regtools_amd: the cohort holds %u triples on the device and %llu by the host's count (a table changed between its extraction and its add?)\n",
@@ -235,8 +231,7 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         launch_cohort_gather(co->d_blocks, by_key.sorted(), N, s, head, st);
         launch_scan_u32(head, seg, N, &d_tot->rows, tmp, st);
         launch_cohort_row_start(head, seg, N, row_start, st);
-        HIP_TRY(hipMemcpyAsync(&U, &d_tot->rows, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, &U, &d_tot->rows, 4));
         mark("gather + heads");
         const size_t Un = (size_t)U + 64;
         if (co->rows.ensure(Un * (2 + 6) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
@@ -248,8 +243,7 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         launch_scan_u32(r.keep, out_row, U, &d_tot->kept.rows, tmp, st);
         launch_scan_u32(r.kept_nnz, nnz_excl, U, &d_tot->kept.nnz, tmp, st);
         FinishTotals::Kept kept = {0, 0};
-        HIP_TRY(hipMemcpyAsync(&kept, &d_tot->kept, sizeof kept, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, &kept, &d_tot->kept, sizeof kept));
         Uk = kept.rows; NNZ = kept.nnz;
         mark("reduce + filters");
         const MatrixLayout L = matrix_layout(Uk, NNZ);
@@ -261,16 +255,16 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         launch_cohort_out(s, head, seg, row_start, r, out_row, nnz_excl, N, U, NNZ, o, st);
         m = matrix_alloc(co->contigs, co->sample_names, Uk, NNZ, /*pinned=*/true);
         if (!m) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the cohort matrix\n"); }
-        hipError_t e_ = hipMemcpyAsync(((MatrixBox *)m)->block, b, L.bytes, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+        CopyBack back{st};
+        back((uint8_t *)m->total - L.total, b, L.bytes);                // (the whole image, where matrix_alloc pointed the members)
+        const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_matrix_free(m); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s finishing the cohort\n", hipGetErrorString(e_)); }
-        co->image_serial = ((MatrixBox *)m)->serial;
+        co->image_serial = matrix_serial(m);
         mark("rows out + copy");
     } else {
         m = matrix_alloc(co->contigs, co->sample_names, 0, 0, false);
         if (!m) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the cohort matrix\n");
-        co->image_serial = ((MatrixBox *)m)->serial;                     // (no rows: nothing of it needs to be in HBM)
+        co->image_serial = matrix_serial(m);                             // (no rows: nothing of it needs to be in HBM)
     }
     m->n_triples = N; m->ms_add_total = co->ms_add_total; m->ms_finish = now_ms() - t0;
     *out = m;
@@ -279,12 +273,10 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
 
 extern "C" void rgx_cohort_matrix_free(rgx_cohort_matrix *m) {
     if (!m) return;
-    MatrixBox *box = (MatrixBox *)m;                                  // m is the first member
     for (int32_t i = 0; i < m->n_ref; ++i) free(m->ref_name[i]);
     for (uint32_t i = 0; i < m->n_samples; ++i) free(m->sample_name[i]);
     free(m->ref_name); free(m->ref_len); free(m->sample_name);
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
+    result_free<rgx_cohort_matrix, uint64_t>(m);
 }
 
 // ---- the host twin: the same contract in plain C++ (records, std::sort, one pass over the runs) ----------------------------------------
@@ -355,44 +347,33 @@ extern "C" int rgx_cohort_merge_host(const rgx_junction_table *const *tables, co
 // ---- text ------------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t rgx_cohort_format_bed12(const rgx_cohort_matrix *m, char *buf, size_t cap) {
     if (!m) return 0;
-    std::string out;
-    out.reserve((size_t)m->n * 96);
-    char tail[256];                                        // everything behind the contig name: bounded numeric fields (format_bed12_rows)
-    for (uint64_t i = 0; i < m->n; ++i) {
-        const uint32_t ts = m->thick_start[i], te = m->thick_end[i];
-        const int k = snprintf(tail, sizeof tail, "\t%u\t%u\tJUNC%08llu\t%llu\t%c\t%u\t%u\t255,0,0\t2\t%u,%u\t0,%u\n", ts, te, (unsigned long long)(i + 1),
-                               (unsigned long long)m->total[i], m->strand[i], ts, te, (uint32_t)(m->start[i] - ts), (uint32_t)(te - m->end[i]),
-                               (uint32_t)(m->end[i] - ts));
-        out.append(m->ref_name[m->tid[i]]); out.append(tail, (size_t)k);
-    }
-    if (buf && out.size() <= cap) memcpy(buf, out.data(), out.size());
-    return out.size();
+    return format_twice(buf, cap, [&](TextOut &o) {
+        for (uint64_t i = 0; i < m->n; ++i) {
+            const uint32_t ts = m->thick_start[i], te = m->thick_end[i];
+            o.put(m->ref_name[m->tid[i]]);                       // everything behind the contig name: bounded numeric fields (format_bed12_rows)
+            o.fmt("\t%u\t%u\tJUNC%08llu\t%llu\t%c\t%u\t%u\t255,0,0\t2\t%u,%u\t0,%u\n", ts, te, (unsigned long long)(i + 1),
+                  (unsigned long long)m->total[i], m->strand[i], ts, te, (uint32_t)(m->start[i] - ts), (uint32_t)(te - m->end[i]),
+                  (uint32_t)(m->end[i] - ts));
+        }
+    });
 }
 
 extern "C" size_t rgx_cohort_format_counts(const rgx_cohort_matrix *m, char *buf, size_t cap) {
     if (!m) return 0;
-    // one pass to size the text, a second one to write it when it fits: nothing is written into a buffer that is too small
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t k) { if (dst) memcpy(dst + need, s, k); need += k; };
-        put("chrom\tstart\tend\tstrand", 22);
-        for (uint32_t g = 0; g < m->n_samples; ++g) { put("\t", 1); put(m->sample_name[g], strlen(m->sample_name[g])); }
-        put("\n", 1);
-        char num[64];
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("chrom\tstart\tend\tstrand");
+        for (uint32_t g = 0; g < m->n_samples; ++g) { o.put("\t", 1); o.put(m->sample_name[g]); }
+        o.put("\n", 1);
         for (uint64_t i = 0; i < m->n; ++i) {
-            put(m->ref_name[m->tid[i]], strlen(m->ref_name[m->tid[i]]));
-            put(num, (size_t)snprintf(num, sizeof num, "\t%u\t%u\t%c", m->start[i], m->end[i], m->strand[i]));
+            o.put(m->ref_name[m->tid[i]]);
+            o.fmt("\t%u\t%u\t%c", m->start[i], m->end[i], m->strand[i]);
             uint64_t k = m->row_begin[i];
             const uint64_t e = m->row_begin[i + 1];
             for (uint32_t g = 0; g < m->n_samples; ++g) {
-                if (k < e && m->col_sample[k] == g) { num[0] = '\t'; char *d = std::to_chars(num + 1, num + sizeof num, m->val_count[k]).ptr; put(num, (size_t)(d - num)); ++k; }
-                else put("\t0", 2);
+                if (k < e && m->col_sample[k] == g) { o.put("\t", 1); o.u(m->val_count[k]); ++k; }
+                else o.put("\t0", 2);
             }
-            put("\n", 1);
+            o.put("\n", 1);
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

@@ -7,31 +7,13 @@
 
 namespace {
 
-struct ClustersLayout { size_t cluster, cl_begin, cl_row, cl_total, cs_begin, cs_sample, cs_total, bytes; };
-ClustersLayout clusters_layout(uint64_t n, uint64_t n_clusters, uint64_t n_kept, uint64_t n_cs) {
-    ClustersLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    L.cl_begin = take((size_t)(n_clusters + 1) * 8); L.cl_total = take((size_t)n_clusters * 8); L.cs_begin = take((size_t)(n_clusters + 1) * 8);
-    L.cs_total = take((size_t)n_cs * 8); L.cluster = take((size_t)n * 4); L.cl_row = take((size_t)n_kept * 4); L.cs_sample = take((size_t)n_cs * 4);
-    L.bytes = o + 16;
-    return L;
-}
-struct ClustersBox { rgx_cohort_clusters c; void *block; size_t block_cap; bool pinned; };
-
 rgx_cohort_clusters *clusters_alloc(uint64_t n, uint64_t n_clusters, uint64_t n_kept, uint64_t n_cs, bool pinned) {
-    ClustersBox *box = (ClustersBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    const ClustersLayout L = clusters_layout(n, n_clusters, n_kept, n_cs);
-    box->pinned = pinned;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    uint8_t *q = (uint8_t *)box->block;
-    rgx_cohort_clusters *c = &box->c;
+    rgx_cohort_clusters *c = result_alloc<rgx_cohort_clusters>(pinned, [&](rgx_cohort_clusters &r, BlockTake &take) {
+        take(r.cl_begin, n_clusters + 1); take(r.cl_total, n_clusters); take(r.cs_begin, n_clusters + 1); take(r.cs_total, n_cs);
+        take(r.cluster, n); take(r.cl_row, n_kept); take(r.cs_sample, n_cs);
+    });
+    if (!c) return nullptr;
     c->n_rows = n; c->n_clusters = n_clusters;
-    c->cluster = (uint32_t *)(q + L.cluster); c->cl_begin = (uint64_t *)(q + L.cl_begin); c->cl_row = (uint32_t *)(q + L.cl_row);
-    c->cl_total = (uint64_t *)(q + L.cl_total); c->cs_begin = (uint64_t *)(q + L.cs_begin); c->cs_sample = (uint32_t *)(q + L.cs_sample);
-    c->cs_total = (uint64_t *)(q + L.cs_total);
     c->cl_begin[0] = 0; c->cs_begin[0] = 0;
     return c;
 }
@@ -44,8 +26,6 @@ int check_limits(const rgx_cohort_matrix *m, char *err, size_t errlen) {
         (unsigned long long)kMaxClusterItems, (unsigned long long)m->n, (unsigned long long)m->row_begin[m->n]);
     return RGX_OK;
 }
-
-inline uint32_t class_of(char c) { return c == '+' ? 0u : c == '-' ? 1u : 2u; }
 
 // what the scans leave at the front of the row workspace (read back by one copy each time the host needs a size)
 struct ClusterScalars { uint32_t flags[kCcBatch]; uint32_t n_components, n_clusters, n_kept, n_entries, n_cs, n_alive; };
@@ -63,8 +43,7 @@ int components_run(uint32_t n_vertices, const EdgeList *lists, int n_lists, uint
             launch_cc_jump(parent, n_vertices, d_flags + k, st);
         }
         uint32_t h[kCcBatch];
-        HIP_TRY(hipMemcpyAsync(h, d_flags, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, h, d_flags, sizeof h));
         for (uint32_t k = 0; k < kCcBatch && !done; ++k) { ++rounds; done = h[k] == 0; }
         // (every round that changes something lowers a label: far fewer than one round per vertex, whatever the graph)
         if (!done && rounds > n_vertices + kCcBatch) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the component search did not settle in %u rounds\n", rounds);
@@ -77,7 +56,7 @@ int cohort_matrix_image(rgx_cohort *co, const rgx_cohort_matrix *m, hipStream_t 
     const uint32_t n = (uint32_t)m->n, nnz = (uint32_t)m->row_begin[m->n];
     const MatrixLayout L = matrix_layout(n, nnz);
     uint8_t *base = co->image.as<uint8_t>();
-    if (((const MatrixBox *)m)->serial != co->image_serial) {           // m is the first member of its box
+    if (matrix_serial(m) != co->image_serial) {
         // the columns needed, where the image has them: total, row_begin, tid, start, end in front of the thick bounds; col_sample, val_count, strand behind n_with
         if (co->cl_in.ensure(L.bytes + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory to upload the matrix (%u rows, %u counts)\n", n, nnz); }
@@ -94,12 +73,7 @@ extern "C" void rgx_cluster_params_default(rgx_cluster_params *p) { if (p) { p->
 
 extern "C" int rgx_cohort_cluster_path(rgx_cohort *co) { return co ? co->cluster_path : 0; }
 
-extern "C" void rgx_cohort_clusters_free(rgx_cohort_clusters *cl) {
-    if (!cl) return;
-    ClustersBox *box = (ClustersBox *)cl;                             // cl is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
-}
+extern "C" void rgx_cohort_clusters_free(rgx_cohort_clusters *cl) { result_free(cl); }
 
 namespace {
 
@@ -132,7 +106,7 @@ struct ClusterRun {
 
     // the matrix where the kernels read it (its image in HBM, or uploaded) and the row workspace; max_intron: what n_ineligible counts against
     int open(bool refine, uint32_t max_intron) {
-        const bool in_hbm = ((const MatrixBox *)m)->serial == co->image_serial;          // m is the first member of its box
+        const bool in_hbm = matrix_serial(m) == co->image_serial;
         co->cluster_path = in_hbm ? 1 : 0;
         n = (uint32_t)m->n; nnz = (uint32_t)m->row_begin[m->n];
         if (!n) return RGX_OK;
@@ -244,8 +218,7 @@ struct ClusterRun {
         launch_scan_u32(keep, cid_excl, n, &d_sc->n_clusters, tmp, st);
         launch_scan_u32(is_root, key0, n, &d_sc->n_components, tmp, st);
         ClusterScalars sc;
-        HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, &sc, d_sc, sizeof sc));
         const uint32_t C = sc.n_clusters, n_components = sc.n_components;
         if (n_alive_out) *n_alive_out = sc.n_alive;
         launch_cluster_assign(parent, keep, cid_excl, cnt, tot, n, C, cluster, sort_key, cl_count, cl_total, st);
@@ -260,8 +233,7 @@ struct ClusterRun {
         uint32_t *len = keep, *ent_off = cid_excl;
         launch_cluster_row_len(cluster, in.row_begin, in.val_count, n, wave_per_row, len, st);
         launch_scan_u32(len, ent_off, n, &d_sc->n_entries, tmp, st);
-        HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, &sc, d_sc, sizeof sc));
         const uint32_t n_kept = sc.n_kept, M = sc.n_entries;
         mark("clusters + cl_row");
 
@@ -287,8 +259,7 @@ struct ClusterRun {
             launch_cluster_cs_heads(by_pair.sorted(), e_cluster, e_sample, M, head, st);
             launch_scan_u32(head, seg, M, &d_sc->n_cs, etmp, st);
             launch_cohort_row_start(head, seg, M, seg_start, st);
-            HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(read_back(st, &sc, d_sc, sizeof sc));
             n_cs = sc.n_cs;
             uint32_t *seg_cluster = head, *samples = seg;                   // (the heads and their scan are used up)
             launch_cluster_cs_sum(by_pair.sorted(), e_cluster, e_sample, e_count, seg_start, M, n_cs, seg_cluster, samples, sums, st);
@@ -299,15 +270,11 @@ struct ClusterRun {
 
         rgx_cohort_clusters *c = clusters_alloc(n, C, n_kept, n_cs, /*pinned=*/true);
         if (!c) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the clusters\n"); }
-        hipError_t e_ = hipMemcpyAsync(c->cluster, cluster, (size_t)n * 4, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(c->cl_begin, o_cl_begin, ((size_t)C + 1) * 8, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(c->cs_begin, o_cs_begin, ((size_t)C + 1) * 8, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess && C) e_ = hipMemcpyAsync(c->cl_total, cl_total, (size_t)C * 8, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess && n_kept) e_ = hipMemcpyAsync(c->cl_row, cl_row, (size_t)n_kept * 4, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess && n_cs) e_ = hipMemcpyAsync(c->cs_sample, cs_sample, (size_t)n_cs * 4, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess && n_cs) e_ = hipMemcpyAsync(c->cs_total, cs_total, (size_t)n_cs * 8, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+        CopyBack back{st};
+        back(c->cluster, cluster, (size_t)n * 4); back(c->cl_begin, o_cl_begin, ((size_t)C + 1) * 8); back(c->cs_begin, o_cs_begin, ((size_t)C + 1) * 8);
+        back(c->cl_total, cl_total, (size_t)C * 8); back(c->cl_row, cl_row, (size_t)n_kept * 4); back(c->cs_sample, cs_sample, (size_t)n_cs * 4);
+        back(c->cs_total, cs_total, (size_t)n_cs * 8);
+        const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_clusters_free(c); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s clustering the cohort\n", hipGetErrorString(e_)); }
         mark("copy");
         c->n_rounds = n_rounds; c->n_components = n_components; c->ms_cluster = now_ms() - t0;
@@ -406,10 +373,10 @@ UnionFind host_components(const rgx_cohort_matrix *m, const uint8_t *alive) {
     for (uint32_t i = 0; i < n; ++i) if (!alive || alive[i]) order.push_back(i);
     for (int side = 0; side < 2; ++side) {
         const uint32_t *site = side ? m->end : m->start;
-        auto same = [&](uint32_t a, uint32_t b) { return m->tid[a] == m->tid[b] && class_of(m->strand[a]) == class_of(m->strand[b]) && site[a] == site[b]; };
+        auto same = [&](uint32_t a, uint32_t b) { return m->tid[a] == m->tid[b] && rgx::strand_class(m->strand[a]) == rgx::strand_class(m->strand[b]) && site[a] == site[b]; };
         std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
             if (m->tid[a] != m->tid[b]) return m->tid[a] < m->tid[b];
-            const uint32_t ca = class_of(m->strand[a]), cb = class_of(m->strand[b]);
+            const uint32_t ca = rgx::strand_class(m->strand[a]), cb = rgx::strand_class(m->strand[b]);
             if (ca != cb) return ca < cb;
             if (site[a] != site[b]) return site[a] < site[b];
             return a < b;
@@ -515,35 +482,23 @@ extern "C" int rgx_cohort_refine_host(const rgx_cohort_matrix *m, const rgx_refi
 // ---- text ------------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t rgx_cohort_format_cluster_counts(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, char *buf, size_t cap) {
     if (!m || !cl || cl->n_rows != m->n) return 0;
-    // one pass to size the text, a second one to write it when it fits (rgx_cohort_format_counts)
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t k) { if (dst) memcpy(dst + need, s, k); need += k; };
-        put("chrom", 5);
-        for (uint32_t g = 0; g < m->n_samples; ++g) { put(" ", 1); put(m->sample_name[g], strlen(m->sample_name[g])); }
-        put("\n", 1);
-        char num[96];
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("chrom");
+        for (uint32_t g = 0; g < m->n_samples; ++g) { o.put(" ", 1); o.put(m->sample_name[g]); }
+        o.put("\n", 1);
         for (uint64_t i = 0; i < m->n; ++i) {
             const uint32_t c = cl->cluster[i];
             if (c == RGX_NO_CLUSTER) continue;
-            put(m->ref_name[m->tid[i]], strlen(m->ref_name[m->tid[i]]));
-            const uint32_t k = class_of(m->strand[i]);
-            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s", m->start[i], m->end[i], (unsigned long long)c + 1, k == 0 ? "+" : k == 1 ? "-" : "NA"));
+            put_intron_id(o, m, cl, (uint32_t)i);
             uint64_t e = m->row_begin[i], d = cl->cs_begin[c];
             const uint64_t e_end = m->row_begin[i + 1], d_end = cl->cs_begin[c + 1];
             for (uint32_t g = 0; g < m->n_samples; ++g) {
                 uint32_t a = 0; uint64_t b = 0;
                 if (e < e_end && m->col_sample[e] == g) a = m->val_count[e++];
                 if (d < d_end && cl->cs_sample[d] == g) b = cl->cs_total[d++];
-                char *t = num; *t++ = ' ';
-                t = std::to_chars(t, num + sizeof num, a).ptr; *t++ = '/'; t = std::to_chars(t, num + sizeof num, b).ptr;
-                put(num, (size_t)(t - num));
+                o.put(" ", 1); o.u(a); o.put("/", 1); o.u(b);
             }
-            put("\n", 1);
+            o.put("\n", 1);
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

@@ -1,7 +1,10 @@
-// cohort_internal.h -- what cohort.cpp (the matrix) and cohort_cluster.cpp (the intron clusters of a matrix) share: the cohort itself, the layout of
-// a matrix's block and the box a matrix lives in.
+// cohort_internal.h -- what the cohort's translation units (cohort*.cpp) share: the cohort itself with its contig table, the layout of a matrix's
+// block and the serial kept beside a matrix, CopyBack (the one way results come back from the device) and the ids the text formats print.  A result's
+// block: result_block.h; the two-pass text writer: text_out.h; what the sQTL calls share beyond this: qtl_run.h.
 #pragma once
 #include "api_internal.h"
+#include "result_block.h"
+#include "text_out.h"
 
 // The cohort's contig table: the samples' header names in order of first appearance.
 struct CohortContigs {
@@ -54,8 +57,33 @@ inline CohortImage image_at(uint8_t *b, const MatrixLayout &L) {
     o.n_with = (uint32_t *)(b + L.n_with); o.col_sample = (uint32_t *)(b + L.col); o.val_count = (uint32_t *)(b + L.val); o.strand = b + L.strand;
     return o;
 }
-// serial: every matrix the library hands out has its own (never 0); a cohort remembers that of the matrix whose image its last finish left in HBM
-struct MatrixBox { rgx_cohort_matrix m; void *block; size_t block_cap; bool pinned; uint64_t serial; };
+// serial: every matrix the library hands out has its own (never 0), kept beside it in its box; a cohort remembers that of the matrix whose image
+// its last finish left in HBM
+inline uint64_t matrix_serial(const rgx_cohort_matrix *m) { return result_extra<uint64_t>(const_cast<rgx_cohort_matrix *>(m)); }
+
+// The one way results come back: device-to-host copies enqueued on the stream, none of no bytes and none behind a failed one, then the call's
+// one wait, which also answers for the kernel launches queued before it.
+struct CopyBack {
+    hipStream_t st; hipError_t e = hipSuccess;
+    void operator()(void *dst, const void *src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); }
+    hipError_t wait() {
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = rgx::pending_launch_error();
+        return e;
+    }
+};
+// a few scalars the host needs now: one copy, one wait
+inline hipError_t read_back(hipStream_t st, void *dst, const void *src, size_t bytes) { CopyBack back{st}; back(dst, src, bytes); return back.wait(); }
+
+// The ids of the text formats: "clu_N_strand" of row i's cluster (the strand by rgx::strand_class: +, -, NA), and the intron id
+// "contig:start:end:clu_N_strand".
+inline void put_clu(TextOut &o, const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, uint32_t i) {
+    const uint32_t cls = rgx::strand_class(m->strand[i]);
+    o.fmt("clu_%llu_%s", (unsigned long long)cl->cluster[i] + 1, cls == 0 ? "+" : cls == 1 ? "-" : "NA");
+}
+inline void put_intron_id(TextOut &o, const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, uint32_t i) {
+    o.put(m->ref_name[m->tid[i]]); o.fmt(":%u:%u:", m->start[i], m->end[i]); put_clu(o, m, cl, i);
+}
 
 constexpr uint64_t kMaxTriples = (1ull << 32) - (1ull << 16);        // (the sort's tiles round the count up inside 32 bits)
 constexpr uint32_t kMaxSamples = 1u << 24;                           // (a triple keeps its sample in 24 bits, beside the strand character)

@@ -11,30 +11,16 @@
 
 namespace {
 
-// One block: what the device copies back in one piece (gram, col_sum, the flag's slot) in front, the host part's results behind it.
-struct PcsLayout { size_t gram, col_sum, flag, variance, component, bytes; };
-PcsLayout pcs_layout(uint32_t S, uint32_t n_pcs) {
-    PcsLayout L; size_t o = 0;
-    auto take = [&](size_t doubles) { const size_t at = o; o += doubles * 8; return at; };
-    L.gram = take((size_t)S * S); L.col_sum = take(S); L.flag = take(1); L.variance = take(S); L.component = take((size_t)n_pcs * S);
-    L.bytes = o + 16;
-    return L;
-}
-struct PcsBox { rgx_pheno_pcs p; void *block; size_t block_cap; bool pinned; };
-
+// gram, col_sum and the flag's slot are ONE array of S * S + S + 1 doubles with no padding between them: the device writes that piece (PcsRun::open
+// carves pc_out in the same order) and finish copies it back in one call, and S * S * 8 is no multiple of 16 for odd S.  So the three are derived
+// from the one array, not taken apart; the host part's results lie behind it.
 rgx_pheno_pcs *pcs_alloc(uint64_t K, uint32_t S, uint32_t n_pcs, bool pinned) {
-    PcsBox *box = (PcsBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    const PcsLayout L = pcs_layout(S, n_pcs);
-    box->pinned = pinned;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    uint8_t *q = (uint8_t *)box->block;
-    rgx_pheno_pcs *p = &box->p;
+    rgx_pheno_pcs *p = result_alloc<rgx_pheno_pcs>(pinned, [&](rgx_pheno_pcs &r, BlockTake &take) {
+        take(r.gram, (size_t)S * S + S + 1); take(r.variance, S); take(r.component, (size_t)n_pcs * S);
+    });
+    if (!p) return nullptr;
     p->n_rows = K; p->n_samples = S; p->n_pcs = n_pcs;
-    p->gram = (double *)(q + L.gram); p->col_sum = (double *)(q + L.col_sum); p->variance = (double *)(q + L.variance);
-    p->component = (double *)(q + L.component);
+    p->col_sum = p->gram + (size_t)S * S;
     return p;
 }
 uint32_t *pcs_flag(rgx_pheno_pcs *p) { return (uint32_t *)(p->col_sum + p->n_samples); }
@@ -198,9 +184,9 @@ struct PcsRun {
     int finish(rgx_pheno_pcs **out) {
         rgx_pheno_pcs *p = pcs_alloc(K, S, n_pcs, /*pinned=*/true);
         if (!p) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the principal components\n"); }
-        hipError_t e_ = hipMemcpyAsync(p->gram, gram, ((size_t)S * S + S + 1) * 8, hipMemcpyDeviceToHost, st);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-        if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+        CopyBack back{st};
+        back(p->gram, gram, ((size_t)S * S + S + 1) * 8);                // (gram, col_sum and the flag: pcs_alloc)
+        const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_pheno_pcs_free(p); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s building the Gram matrix\n",
             hipGetErrorString(e_)); }
         mark("copy");
@@ -259,12 +245,7 @@ bool twin_rows_plain(const uint32_t *rank2, const double *T, uint64_t K, uint32_
 
 void pheno_quantile_table(uint64_t K, std::vector<double> &T) { quantile_table(K, T); }
 
-extern "C" void rgx_cohort_pheno_pcs_free(rgx_pheno_pcs *pcs) {
-    if (!pcs) return;
-    PcsBox *box = (PcsBox *)pcs;                                      // pcs is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
-}
+extern "C" void rgx_cohort_pheno_pcs_free(rgx_pheno_pcs *pcs) { result_free(pcs); }
 
 extern "C" int rgx_cohort_pheno_pcs(rgx_cohort *co, const rgx_pheno_table *ph, uint32_t n_pcs, rgx_pheno_pcs **out, char *err, size_t errlen) {
     if (!co || !ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_pheno_pcs needs a cohort and a phenotype table\n");
@@ -321,22 +302,14 @@ extern "C" int rgx_cohort_pheno_pcs_host(const rgx_pheno_table *ph, uint32_t n_p
 // ---- text: LeafCutter's .PCs layout ---------------------------------------------------------------------------------------------------------------
 extern "C" size_t rgx_cohort_format_pheno_pcs(const rgx_cohort_matrix *m, const rgx_pheno_pcs *pcs, char *buf, size_t cap) {
     if (!m || (pcs && pcs->n_samples != m->n_samples)) return 0;
-    // one pass to size the text, a second one to write it when it fits (rgx_cohort_format_counts)
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t k) { if (dst) memcpy(dst + need, s, k); need += k; };
-        put("id", 2);
-        for (uint32_t g = 0; g < m->n_samples; ++g) { put("\t", 1); put(m->sample_name[g], strlen(m->sample_name[g])); }
-        put("\n", 1);
-        char num[64];
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("id");
+        for (uint32_t g = 0; g < m->n_samples; ++g) { o.put("\t", 1); o.put(m->sample_name[g]); }
+        o.put("\n", 1);
         for (uint32_t i = 0; pcs && i < pcs->n_pcs; ++i) {
-            put(num, (size_t)snprintf(num, sizeof num, "%u", i + 1));
-            for (uint32_t g = 0; g < m->n_samples; ++g) put(num, (size_t)snprintf(num, sizeof num, "\t%.17g", pcs->component[(size_t)i * m->n_samples + g]));
-            put("\n", 1);
+            o.u(i + 1);
+            for (uint32_t g = 0; g < m->n_samples; ++g) o.fmt("\t%.17g", pcs->component[(size_t)i * m->n_samples + g]);
+            o.put("\n", 1);
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

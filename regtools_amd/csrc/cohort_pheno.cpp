@@ -11,30 +11,12 @@
 
 namespace {
 
-struct PhenoLayout { size_t mean, sd, row, n_na, rank2, bytes; };
-PhenoLayout pheno_layout(uint64_t K, uint64_t S) {
-    PhenoLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    L.mean = take((size_t)K * 8); L.sd = take((size_t)K * 8); L.row = take((size_t)K * 4); L.n_na = take((size_t)K * 4);
-    L.rank2 = take((size_t)K * (size_t)S * 4);
-    L.bytes = o + 16;
-    return L;
-}
-struct PhenoBox { rgx_pheno_table p; void *block; size_t block_cap; bool pinned; };
-
 rgx_pheno_table *pheno_alloc(uint64_t K, uint32_t S, bool pinned) {
-    PhenoBox *box = (PhenoBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    const PhenoLayout L = pheno_layout(K, S);
-    box->pinned = pinned;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    uint8_t *q = (uint8_t *)box->block;
-    rgx_pheno_table *p = &box->p;
+    rgx_pheno_table *p = result_alloc<rgx_pheno_table>(pinned, [&](rgx_pheno_table &r, BlockTake &take) {
+        take(r.mean, K); take(r.sd, K); take(r.row, K); take(r.n_na, K); take(r.rank2, (size_t)K * S);
+    });
+    if (!p) return nullptr;
     p->n_rows = K; p->n_samples = S;
-    p->mean = (double *)(q + L.mean); p->sd = (double *)(q + L.sd); p->row = (uint32_t *)(q + L.row); p->n_na = (uint32_t *)(q + L.n_na);
-    p->rank2 = (uint32_t *)(q + L.rank2);
     return p;
 }
 
@@ -89,7 +71,7 @@ struct PhenoRun {
 
     // 1. the matrix where the kernels read it (its image in HBM, or uploaded), the cluster result beside it, the row workspace
     int open() {
-        co->cluster_path = ((const MatrixBox *)m)->serial == co->image_serial ? 1 : 0;          // m is the first member of its box
+        co->cluster_path = matrix_serial(m) == co->image_serial ? 1 : 0;
         n = (uint32_t)m->n; S = m->n_samples;
         if (!n_clustered || !S) return RGX_OK;
         HIP_ENTER(co->device);
@@ -132,8 +114,7 @@ struct PhenoRun {
         launch_scan_u32(keep, pos, n, &d_sc->n_kept, tmp, st);
         launch_scan_u32(drop_na, drop_na, n, &d_sc->n_drop_na, tmp, st);
         PhenoScalars sc;
-        HIP_TRY(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(read_back(st, &sc, d_sc, sizeof sc));
         K = sc.n_kept; n_drop_na = sc.n_drop_na;
         if (K > n_clustered) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: %u rows kept of %llu clustered ones\n", K, (unsigned long long)n_clustered);
         launch_pheno_scatter(keep, pos, n_na, mean, sd, n, o_row, o_n_na, o_mean, o_sd, st);
@@ -170,13 +151,10 @@ struct PhenoRun {
         rgx_pheno_table *p = pheno_alloc(K, S, /*pinned=*/K != 0);
         if (!p) { if (st) (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the phenotype table\n"); }
         if (K) {
-            hipError_t e_ = hipMemcpyAsync(p->row, o_row, (size_t)K * 4, hipMemcpyDeviceToHost, st);
-            if (e_ == hipSuccess) e_ = hipMemcpyAsync(p->n_na, o_n_na, (size_t)K * 4, hipMemcpyDeviceToHost, st);
-            if (e_ == hipSuccess) e_ = hipMemcpyAsync(p->mean, o_mean, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-            if (e_ == hipSuccess) e_ = hipMemcpyAsync(p->sd, o_sd, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-            if (e_ == hipSuccess) e_ = hipMemcpyAsync(p->rank2, rank2, (size_t)K * S * 4, hipMemcpyDeviceToHost, st);
-            if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-            if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+            CopyBack back{st};
+            back(p->row, o_row, (size_t)K * 4); back(p->n_na, o_n_na, (size_t)K * 4); back(p->mean, o_mean, (size_t)K * 8);
+            back(p->sd, o_sd, (size_t)K * 8); back(p->rank2, rank2, (size_t)K * S * 4);
+            const hipError_t e_ = back.wait();
             if (e_ != hipSuccess) { rgx_cohort_phenotypes_free(p); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s building the phenotype table\n",
                 hipGetErrorString(e_)); }
             mark("copy");
@@ -198,12 +176,7 @@ double halve(double *P) {
 
 extern "C" void rgx_pheno_params_default(rgx_pheno_params *p) { if (p) { p->na_num = 4; p->na_den = 10; p->min_sd = 0.005; } }
 
-extern "C" void rgx_cohort_phenotypes_free(rgx_pheno_table *ph) {
-    if (!ph) return;
-    PhenoBox *box = (PhenoBox *)ph;                                   // ph is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
-}
+extern "C" void rgx_cohort_phenotypes_free(rgx_pheno_table *ph) { result_free(ph); }
 
 extern "C" int rgx_cohort_phenotypes(rgx_cohort *co, const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_params *p,
                                      rgx_pheno_table **out, char *err, size_t errlen) {
@@ -334,29 +307,17 @@ extern "C" size_t rgx_cohort_format_phenotypes(const rgx_cohort_matrix *m, const
                                                size_t cap) {
     if (!m || !cl || !ph || cl->n_rows != m->n || ph->n_samples != m->n_samples) return 0;
     for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return 0;
-    // one pass to size the text, a second one to write it when it fits (rgx_cohort_format_counts)
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t k) { if (dst) memcpy(dst + need, s, k); need += k; };
-        put("#Chr\tstart\tend\tID", 17);
-        for (uint32_t g = 0; g < m->n_samples; ++g) { put("\t", 1); put(m->sample_name[g], strlen(m->sample_name[g])); }
-        put("\n", 1);
-        char num[128];
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("#Chr\tstart\tend\tID");
+        for (uint32_t g = 0; g < m->n_samples; ++g) { o.put("\t", 1); o.put(m->sample_name[g]); }
+        o.put("\n", 1);
         for (uint64_t k = 0; k < ph->n_rows; ++k) {
-            const uint32_t i = ph->row[k], c = cl->cluster[i], cls = rgx::strand_class(m->strand[i]);
-            const char *contig = m->ref_name[m->tid[i]];
-            put(contig, strlen(contig));
-            put(num, (size_t)snprintf(num, sizeof num, "\t%u\t%u\t", m->start[i], m->end[i]));
-            put(contig, strlen(contig));
-            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s", m->start[i], m->end[i], (unsigned long long)c + 1,
-                                      cls == 0 ? "+" : cls == 1 ? "-" : "NA"));
-            for (uint32_t g = 0; g < m->n_samples; ++g)
-                put(num, (size_t)snprintf(num, sizeof num, "\t%.17g", rgx_pheno_quantile(ph->rank2[k * m->n_samples + g], ph->n_rows)));
-            put("\n", 1);
+            const uint32_t i = ph->row[k];
+            o.put(m->ref_name[m->tid[i]]);
+            o.fmt("\t%u\t%u\t", m->start[i], m->end[i]);
+            put_intron_id(o, m, cl, i);
+            for (uint32_t g = 0; g < m->n_samples; ++g) o.fmt("\t%.17g", rgx_pheno_quantile(ph->rank2[k * m->n_samples + g], ph->n_rows));
+            o.put("\n", 1);
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

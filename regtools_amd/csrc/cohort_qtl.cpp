@@ -13,42 +13,18 @@
 
 namespace {
 
-// One block, every array 16-byte aligned.
-struct QtlLayout { size_t yy, gg, r, slope, pair_begin, pair_variant, best, verdict, bytes; };
-QtlLayout qtl_layout(uint64_t K, uint32_t V, uint64_t P) {
-    QtlLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    L.yy = take((size_t)K * 8); L.gg = take((size_t)V * 8); L.r = take((size_t)P * 8); L.slope = take((size_t)P * 8);
-    L.pair_begin = take((size_t)(K + 1) * 4); L.pair_variant = take((size_t)P * 4); L.best = take((size_t)K * 4); L.verdict = take((size_t)V);
-    L.bytes = o + 16;
-    return L;
-}
-struct QtlBox { rgx_qtl_result q; void *block; size_t block_cap; bool pinned; };
-
 rgx_qtl_result *qtl_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, uint64_t P, bool pinned) {
-    QtlBox *box = (QtlBox *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    const QtlLayout L = qtl_layout(K, V, P);
-    box->pinned = pinned;
-    box->block = block_take(L.bytes, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(L.bytes, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    uint8_t *b = (uint8_t *)box->block;
-    rgx_qtl_result *q = &box->q;
+    rgx_qtl_result *q = result_alloc<rgx_qtl_result>(pinned, [&](rgx_qtl_result &r, BlockTake &take) {
+        take(r.yy, K); take(r.gg, V); take(r.r, P); take(r.slope, P); take(r.pair_begin, K + 1); take(r.pair_variant, P); take(r.best, K);
+        take(r.variant_verdict, V);
+    });
+    if (!q) return nullptr;
     q->n_rows = K; q->n_samples = S; q->n_variants = V; q->n_cov = n_cov; q->dof = S - n_cov - 2; q->n_pairs = P;
-    q->yy = (double *)(b + L.yy); q->gg = (double *)(b + L.gg); q->r = (double *)(b + L.r); q->slope = (double *)(b + L.slope);
-    q->pair_begin = (uint32_t *)(b + L.pair_begin); q->pair_variant = (uint32_t *)(b + L.pair_variant); q->best = (uint32_t *)(b + L.best);
-    q->variant_verdict = b + L.verdict;
     return q;
 }
 
 int too_many_pairs(uint64_t P, char *err, size_t errlen) {
     return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: %llu pairs of a row and a variant; the sQTL scan takes at most 2^32 - 2^16\n", (unsigned long long)P);
-}
-
-void count_verdicts(rgx_qtl_result *q) {
-    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
-    for (uint64_t k = 0; k < q->n_rows; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], q->n_samples);
 }
 
 }  // namespace
@@ -214,13 +190,11 @@ int QtlRun::finish(rgx_qtl_result **out) {
     rgx_qtl_result *q = qtl_alloc(K, S, V, a.n_cov, P, /*pinned=*/true);
     if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result of %llu pairs\n",
         (unsigned long long)P); }
-    hipError_t e_ = hipMemcpyAsync(q->yy, yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-    auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
-    copy(q->gg, gg, (size_t)V * 8); copy(q->variant_verdict, verdict, V); copy(q->pair_begin, pair_begin, ((size_t)K + 1) * 4);
-    copy(q->r, r, (size_t)P * 8); copy(q->slope, slope, (size_t)P * 8); copy(q->pair_variant, pair_variant, (size_t)P * 4);
-    copy(q->best, best, (size_t)K * 4);
-    if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-    if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+    CopyBack back{st};
+    back(q->yy, yy, (size_t)K * 8); back(q->gg, gg, (size_t)V * 8); back(q->variant_verdict, verdict, V);
+    back(q->pair_begin, pair_begin, ((size_t)K + 1) * 4); back(q->r, r, (size_t)P * 8); back(q->slope, slope, (size_t)P * 8);
+    back(q->pair_variant, pair_variant, (size_t)P * 4); back(q->best, best, (size_t)K * 4);
+    hipError_t e_ = back.wait();
     float ms_res = 0, ms_pr = 0;
     if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, ev[0], ev[1]);
     if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, ev[2], ev[3]);
@@ -233,12 +207,7 @@ int QtlRun::finish(rgx_qtl_result **out) {
     return RGX_OK;
 }
 
-extern "C" void rgx_cohort_qtl_free(rgx_qtl_result *q) {
-    if (!q) return;
-    QtlBox *box = (QtlBox *)q;                                        // q is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
-}
+extern "C" void rgx_cohort_qtl_free(rgx_qtl_result *q) { result_free(q); }
 
 extern "C" int rgx_cohort_pheno_regions(const rgx_cohort_matrix *m, const rgx_pheno_table *ph, rgx_qtl_region *out, char *err, size_t errlen) {
     if (!m || !ph || (ph->n_rows && (!out || !ph->row))) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_pheno_regions needs a matrix, a phenotype table and room\n");
@@ -370,33 +339,21 @@ extern "C" double rgx_qtl_pvalue(double t, uint32_t dof) {
 // ---- text ---------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t rgx_cohort_format_qtl(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, const rgx_qtl_result *q,
                                         const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap) {
-    if (!m || !cl || !ph || cl->n_rows != m->n || (q && (q->n_rows != ph->n_rows || (q->n_variants && (!var_pos || !variant_id))))) return 0;
-    for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return 0;
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t n) { if (dst) memcpy(dst + need, s, n); need += n; };
-        static const char head[] = "phenotype_id\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\tis_best\n";
-        put(head, sizeof head - 1);
-        char num[256];
+    if (!qtl_text_args_ok(m, cl, ph, q, var_pos, variant_id)) return 0;
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("phenotype_id\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\tis_best\n");
         for (uint64_t k = 0; q && k < q->n_rows; ++k) {
-            const uint32_t i = ph->row[k], c = cl->cluster[i], cls = rgx::strand_class(m->strand[i]);
-            const char *contig = m->ref_name[m->tid[i]];
+            const uint32_t i = ph->row[k];
             for (uint32_t p = q->pair_begin[k]; p < q->pair_begin[k + 1]; ++p) {
                 const uint32_t v = q->pair_variant[p];
                 const double t = rgx_qtl_tstat(q->r[p], q->dof);
-                put(contig, strlen(contig));
-                put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s\t", m->start[i], m->end[i], (unsigned long long)c + 1,
-                                          cls == 0 ? "+" : cls == 1 ? "-" : "NA"));
-                put(variant_id[v], strlen(variant_id[v]));
-                put(num, (size_t)snprintf(num, sizeof num, "\t%lld\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%d\n", (long long)var_pos[v] - (long long)m->start[i],
-                                          q->r[p], q->slope[p], q->slope[p] / t, t, rgx_qtl_pvalue(t, q->dof), q->best[k] == p ? 1 : 0));
+                put_intron_id(o, m, cl, i); o.put("\t", 1);
+                o.put(variant_id[v]);
+                o.fmt("\t%lld\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%d\n", (long long)var_pos[v] - (long long)m->start[i], q->r[p], q->slope[p],
+                      q->slope[p] / t, t, rgx_qtl_pvalue(t, q->dof), q->best[k] == p ? 1 : 0);
             }
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }
 
 // ---- genotypes from a VCF / BCF -------------------------------------------------------------------------------------------------------------------

@@ -147,43 +147,24 @@ extern "C" int rgx_cohort_qtl_permute_grouped_host(const rgx_pheno_table *ph, co
 extern "C" size_t rgx_cohort_format_qtl_group(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
                                               const rgx_qtl_group_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf,
                                               size_t cap) {
-    if (!m || !cl || !ph || cl->n_rows != m->n || (q && (q->n_rows != ph->n_rows || (q->n_variants && (!var_pos || !variant_id))))) return 0;
-    for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return 0;
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t n) { if (dst) memcpy(dst + need, s, n); need += n; };
-        char num[256];
-        auto put_g = [&](double x, char end) {
-            if (x != x) put(num, (size_t)snprintf(num, sizeof num, "nan%c", end)); else put(num, (size_t)snprintf(num, sizeof num, "%.17g%c", x, end));
-        };
-        auto put_clu = [&](uint32_t i, char end) {
-            const uint32_t cls = rgx::strand_class(m->strand[i]);
-            put(num, (size_t)snprintf(num, sizeof num, "clu_%llu_%s%c", (unsigned long long)cl->cluster[i] + 1, cls == 0 ? "+" : cls == 1 ? "-" : "NA", end));
-        };
-        static const char head[] = "group_id\tgroup_size\tphenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\t"
-                                   "tstat\tpval_nominal\tpval_perm\tpval_beta\n";
-        put(head, sizeof head - 1);
+    if (!qtl_text_args_ok(m, cl, ph, q, var_pos, variant_id)) return 0;
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("group_id\tgroup_size\tphenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\t"
+              "pval_perm\tpval_beta\n");
         for (uint64_t g = 0; q && g < q->n_groups; ++g) {
             if (!q->group_n_cis[g]) continue;
             const uint32_t i = ph->row[q->best_row[g]], v = q->best_variant[g];
-            const char *contig = m->ref_name[m->tid[i]];
             const double t = rgx_qtl_tstat(q->best_r[g], q->dof);
-            put_clu(ph->row[q->grp_row[q->grp_begin[g]]], '\t');
-            put(num, (size_t)snprintf(num, sizeof num, "%u\t", q->grp_begin[g + 1] - q->grp_begin[g]));
-            put(contig, strlen(contig));
-            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:", m->start[i], m->end[i]));
-            put_clu(i, '\t');
-            put(num, (size_t)snprintf(num, sizeof num, "%llu\t", (unsigned long long)q->group_n_cis[g]));
-            put_g(q->beta_shape1[g], '\t'); put_g(q->beta_shape2[g], '\t');
-            put(num, (size_t)snprintf(num, sizeof num, "%u\t", q->dof));
-            put(variant_id[v], strlen(variant_id[v]));
-            put(num, (size_t)snprintf(num, sizeof num, "\t%lld\t", (long long)var_pos[v] - (long long)m->start[i]));
-            put_g(q->best_r[g], '\t'); put_g(q->best_slope[g], '\t'); put_g(q->best_slope[g] / t, '\t'); put_g(t, '\t');
-            put_g(rgx_qtl_pvalue(t, q->dof), '\t'); put_g(q->p_perm[g], '\t'); put_g(q->p_beta[g], '\n');
+            put_clu(o, m, cl, ph->row[q->grp_row[q->grp_begin[g]]]);
+            o.fmt("\t%u\t", q->grp_begin[g + 1] - q->grp_begin[g]);
+            put_intron_id(o, m, cl, i);
+            o.fmt("\t%llu\t", (unsigned long long)q->group_n_cis[g]);
+            o.g17(q->beta_shape1[g], '\t'); o.g17(q->beta_shape2[g], '\t');
+            o.fmt("%u\t", q->dof);
+            o.put(variant_id[v]);
+            o.fmt("\t%lld\t", (long long)var_pos[v] - (long long)m->start[i]);
+            o.g17(q->best_r[g], '\t'); o.g17(q->best_slope[g], '\t'); o.g17(q->best_slope[g] / t, '\t'); o.g17(t, '\t');
+            o.g17(rgx_qtl_pvalue(t, q->dof), '\t'); o.g17(q->p_perm[g], '\t'); o.g17(q->p_beta[g], '\n');
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

@@ -169,9 +169,8 @@ void qtl_series_products(const QtlHost &h, uint32_t S, uint32_t B, const uint16_
 
 template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen) {
     const Series sr = series_of(q);
-    const uint64_t K = q->n_rows, N = sr.n; const uint32_t B = q->n_perm, S = q->n_samples, dof = q->dof;
-    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
-    for (uint64_t k = 0; k < K; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], S);
+    const uint64_t N = sr.n; const uint32_t B = q->n_perm, dof = q->dof;
+    count_verdicts(q);
     const uint64_t p_tiles = ((uint64_t)B + 1 + kQtlTile - 1) / kQtlTile;
     for (uint64_t g = 0; g < N; ++g) {
         const uint32_t m_end = sr.begin ? sr.begin[g + 1] : (uint32_t)g + 1;
@@ -253,14 +252,13 @@ template <class R> int PermRun::finish(R *q) {
     char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
     const uint32_t K = run.K, V = run.V; const size_t N = n_series;
     uint64_t h[4] = {0, 0, 0, 0};
-    hipError_t e_ = hipMemcpyAsync(q->yy, run.yy, (size_t)K * 8, hipMemcpyDeviceToHost, st);
-    auto copy = [&](void *dst, const void *src, size_t bytes) { if (e_ == hipSuccess && bytes) e_ = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
-    copy(q->gg, run.gg, (size_t)V * 8); copy(q->variant_verdict, run.verdict, V); copy(q->n_cis, run.count, (size_t)K * 4);
-    copy(q->perm_r, perm_r, N * ((size_t)B + 1) * 8); copy(q->best_r, best_r, N * 8); copy(q->best_slope, best_slope, N * 8);
-    if (mem) copy(series_of(q).best_row, best_row, N * 4);
-    copy(q->best_variant, best_variant, N * 4); copy(h, run.head, 32);
-    if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);
-    if (e_ == hipSuccess) e_ = rgx::pending_launch_error();
+    CopyBack back{st};
+    back(q->yy, run.yy, (size_t)K * 8); back(q->gg, run.gg, (size_t)V * 8); back(q->variant_verdict, run.verdict, V);
+    back(q->n_cis, run.count, (size_t)K * 4); back(q->perm_r, perm_r, N * ((size_t)B + 1) * 8); back(q->best_r, best_r, N * 8);
+    back(q->best_slope, best_slope, N * 8);
+    if (mem) back(series_of(q).best_row, best_row, N * 4);
+    back(q->best_variant, best_variant, N * 4); back(h, run.head, 32);
+    hipError_t e_ = back.wait();
     float ms_res = 0, ms_pr = 0;
     if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, run.ev[0], run.ev[1]);
     if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_pr, run.ev[2], run.ev[3]);
@@ -385,36 +383,22 @@ extern "C" int rgx_cohort_qtl_permute_host(const rgx_pheno_table *ph, const rgx_
 // ---- text ---------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t rgx_cohort_format_qtl_perm(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
                                              const rgx_qtl_perm_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap) {
-    if (!m || !cl || !ph || cl->n_rows != m->n || (q && (q->n_rows != ph->n_rows || (q->n_variants && (!var_pos || !variant_id))))) return 0;
-    for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return 0;
-    auto run = [&](char *dst) {
-        size_t need = 0;
-        auto put = [&](const char *s, size_t n) { if (dst) memcpy(dst + need, s, n); need += n; };
-        char num[256];
-        auto put_g = [&](double x, char end) {
-            if (x != x) put(num, (size_t)snprintf(num, sizeof num, "nan%c", end)); else put(num, (size_t)snprintf(num, sizeof num, "%.17g%c", x, end));
-        };
-        static const char head[] = "phenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\t"
-                                   "pval_perm\tpval_beta\n";
-        put(head, sizeof head - 1);
+    if (!qtl_text_args_ok(m, cl, ph, q, var_pos, variant_id)) return 0;
+    return format_twice(buf, cap, [&](TextOut &o) {
+        o.put("phenotype_id\tnum_var\tbeta_shape1\tbeta_shape2\tdof\tvariant_id\tdistance\tr\tslope\tslope_se\ttstat\tpval_nominal\t"
+              "pval_perm\tpval_beta\n");
         for (uint64_t k = 0; q && k < q->n_rows; ++k) {
             if (!q->n_cis[k]) continue;
-            const uint32_t i = ph->row[k], c = cl->cluster[i], cls = rgx::strand_class(m->strand[i]), v = q->best_variant[k];
-            const char *contig = m->ref_name[m->tid[i]];
+            const uint32_t i = ph->row[k], v = q->best_variant[k];
             const double t = rgx_qtl_tstat(q->best_r[k], q->dof);
-            put(contig, strlen(contig));
-            put(num, (size_t)snprintf(num, sizeof num, ":%u:%u:clu_%llu_%s\t%u\t", m->start[i], m->end[i], (unsigned long long)c + 1,
-                                      cls == 0 ? "+" : cls == 1 ? "-" : "NA", q->n_cis[k]));
-            put_g(q->beta_shape1[k], '\t'); put_g(q->beta_shape2[k], '\t');
-            put(num, (size_t)snprintf(num, sizeof num, "%u\t", q->dof));
-            put(variant_id[v], strlen(variant_id[v]));
-            put(num, (size_t)snprintf(num, sizeof num, "\t%lld\t", (long long)var_pos[v] - (long long)m->start[i]));
-            put_g(q->best_r[k], '\t'); put_g(q->best_slope[k], '\t'); put_g(q->best_slope[k] / t, '\t'); put_g(t, '\t');
-            put_g(rgx_qtl_pvalue(t, q->dof), '\t'); put_g(q->p_perm[k], '\t'); put_g(q->p_beta[k], '\n');
+            put_intron_id(o, m, cl, i);
+            o.fmt("\t%u\t", q->n_cis[k]);
+            o.g17(q->beta_shape1[k], '\t'); o.g17(q->beta_shape2[k], '\t');
+            o.fmt("%u\t", q->dof);
+            o.put(variant_id[v]);
+            o.fmt("\t%lld\t", (long long)var_pos[v] - (long long)m->start[i]);
+            o.g17(q->best_r[k], '\t'); o.g17(q->best_slope[k], '\t'); o.g17(q->best_slope[k] / t, '\t'); o.g17(t, '\t');
+            o.g17(rgx_qtl_pvalue(t, q->dof), '\t'); o.g17(q->p_perm[k], '\t'); o.g17(q->p_beta[k], '\n');
         }
-        return need;
-    };
-    const size_t need = run(nullptr);
-    if (buf && need <= cap) run(buf);
-    return need;
+    });
 }

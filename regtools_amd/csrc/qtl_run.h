@@ -1,7 +1,7 @@
 // qtl_run.h -- what the nominal cis-sQTL scan (cohort_qtl.cpp) and its permutation pass (cohort_qtl_perm.cpp) share: the arguments and their checks,
 // the host half of the contract (basis, dot64, residual, the twin's steps (1)-(6)) and QtlRun, the device stages both calls are made of, defined
 // in cohort_qtl.cpp; then what the permutation pass shares with the grouped pass (cohort_qtl_group.cpp), PermRun among it, defined in
-// cohort_qtl_perm.cpp.
+// cohort_qtl_perm.cpp.  The results' blocks are result_block.h's, their copies back CopyBack's and their text text_out.h's (cohort_internal.h).
 #pragma once
 #include "cohort_internal.h"
 #include "qtl_core.h"
@@ -52,31 +52,19 @@ inline Series series_of(rgx_qtl_group_result *q) { return {q->n_groups, q->grp_b
 // sixteen a task among the host's threads; q's arrays from steps (1)-(6), its lists and perm_r, best_* are in place
 template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen);
 
-// A result and the one block its arrays live in.  arrays(q, take) names every array once with its length; it runs twice, to size the block (a
-// running offset, every array 16-byte aligned) and to hand out the pointers.  Page-locked when asked for and possible.
-template <class R> struct ResultBox { R q; void *block; size_t block_cap; bool pinned; };
-struct BlockTake {
-    uint8_t *base; size_t o = 0;
-    template <class T> void operator()(T *&p, size_t n) { if (base) p = (T *)(base + o); o += (n * sizeof(T) + 15) & ~(size_t)15; }
-};
-template <class R, class F> R *result_alloc(bool pinned, F arrays) {
-    ResultBox<R> *box = (ResultBox<R> *)calloc(1, sizeof *box);
-    if (!box) return nullptr;
-    BlockTake size{nullptr};
-    arrays(box->q, size);
-    box->pinned = pinned;
-    box->block = block_take(size.o, box->block_cap, pinned);
-    if (!box->block && pinned) { box->pinned = false; box->block = block_take(size.o, box->block_cap, false); }
-    if (!box->block) { free(box); return nullptr; }
-    BlockTake take{(uint8_t *)box->block};
-    arrays(box->q, take);
-    return &box->q;
+// the verdict counts of any of the three results: constant and explained variants, rows without enough variance
+template <class R> void count_verdicts(R *q) {
+    for (uint32_t v = 0; v < q->n_variants; ++v) { q->n_constant += q->variant_verdict[v] == 1; q->n_explained += q->variant_verdict[v] == 2; }
+    for (uint64_t k = 0; k < q->n_rows; ++k) q->n_flat_rows += !qtl_enough(q->yy[k], q->n_samples);
 }
-template <class R> void result_free(R *q) {
-    if (!q) return;
-    ResultBox<R> *box = (ResultBox<R> *)q;                              // q is the first member
-    block_give(box->block, box->block_cap, box->pinned);
-    free(box);
+
+// what the three sQTL texts ask of their arguments: the clusters are the matrix's, every table row is a clustered matrix row, and the result
+// q (null: the header line alone) is the table's and comes with its variants' positions and ids
+template <class Q> bool qtl_text_args_ok(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph, const Q *q,
+                                         const uint32_t *var_pos, const char *const *variant_id) {
+    if (!m || !cl || !ph || cl->n_rows != m->n || (q && (q->n_rows != ph->n_rows || (q->n_variants && (!var_pos || !variant_id))))) return false;
+    for (uint64_t k = 0; k < ph->n_rows; ++k) if (ph->row[k] >= m->n || cl->cluster[ph->row[k]] == RGX_NO_CLUSTER) return false;
+    return true;
 }
 
 // One device run, as the stages rgx_cohort_qtl_nominal is made of.  The caller holds the cohort's lock and has checked the arguments; every stage

@@ -68,6 +68,24 @@ def test_hand_made_cohort_on_both_paths(gpu_ctx):
     cases.free_tables(tables)
 
 
+def test_filters_that_keep_no_cluster(gpu_ctx):
+    """Rows and components, but no cluster, no member row and no denominator: every copy back but the rows' cluster numbers and the two
+    begin arrays is empty."""
+    from regtools_amd import cohort
+    tables = [table_from_rows(cases.HAND_P), table_from_rows(cases.HAND_Q)]
+    co = _cohort_of(gpu_ctx, tables, ["p", "q"], only_anchored=False)
+    m = co.finish()
+    for path, mat in ((1, m), (0, cohort.merge_host([cases.Sample(t) for t in tables], ["p", "q"], only_anchored=False))):
+        a, b = co.cluster(mat, min_rows=99), cohort.cluster_host(mat, min_rows=99)
+        assert co.cluster_paths[-1] == path
+        cluster_ref.same_clusters(a, b)
+        assert (a.n_clusters, len(a.cl_row), len(a.cs_sample), len(a.cs_total)) == (0, 0, 0, 0) and a.n_components > 0
+        assert (a.cluster == 0xffffffff).all() and list(a.cl_begin) == [0] and list(a.cs_begin) == [0]
+        assert a.counts_text(mat) == b.counts_text(mat) == b"chrom p q\n"
+    co.close()
+    cases.free_tables(tables)
+
+
 def test_empty_matrix_and_a_cohort_without_samples(gpu_ctx):
     import regtools_amd
     from regtools_amd import cohort

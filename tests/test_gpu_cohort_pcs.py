@@ -52,6 +52,12 @@ def test_sample_counts_around_the_tile(co, S):
     _check(co, pca.random_rank2(41, S, seed=S))
 
 
+def test_three_samples(co):
+    """S = 3: gram's 72 bytes are no multiple of 16, and gram, col_sum and the flag word still come back in one piece (every component asked for)."""
+    dev = _check(co, pca.random_rank2(41, 3, seed=3), n_pcs=3)
+    assert dev.gram.shape == (3, 3) and dev.col_sum.ctypes.data == dev.gram.ctypes.data + 72
+
+
 @pytest.mark.parametrize("K", [2, 15, 16, 17, 33])
 def test_row_counts_around_the_slab(co, K):
     _check(co, pca.random_rank2(K, 5, seed=K))
