@@ -15,15 +15,18 @@ struct RecHead {
     int64_t  aux_off;     // offset of the aux area from the start of the variable data
 };
 
+// The fixed part from its eight little-endian words (the eighth, next_pos, is not kept).
+RGX_HD void rec_head_words(const uint32_t x[8], RecHead &h) {
+    h.block_len = (int32_t)x[0]; h.tid = (int32_t)x[1]; h.pos = (int32_t)x[2];
+    h.l_qname = x[3] & 0xff; h.n_cigar = x[4] & 0xffff; h.flag = x[4] >> 16;
+    h.l_qseq = (int32_t)x[5]; h.mtid = (int32_t)x[6];
+    h.aux_off = (int64_t)h.l_qname + 4 * (int64_t)h.n_cigar + (((int64_t)h.l_qseq + 1) >> 1) + h.l_qseq;
+}
 // Reads the fixed part at arena offset o (caller guarantees o+36 <= lim).
 RGX_HD void rec_head(const uint8_t *a, RecHead &h) {
-    h.block_len = (int32_t)ld32(a);
-    h.tid = (int32_t)ld32(a + 4); h.pos = (int32_t)ld32(a + 8);
-    uint32_t x2 = ld32(a + 12), x3 = ld32(a + 16);
-    h.l_qname = x2 & 0xff; h.n_cigar = x3 & 0xffff; h.flag = x3 >> 16;
-    h.l_qseq = (int32_t)ld32(a + 20);
-    h.mtid = (int32_t)ld32(a + 24);
-    h.aux_off = (int64_t)h.l_qname + 4 * (int64_t)h.n_cigar + (((int64_t)h.l_qseq + 1) >> 1) + h.l_qseq;
+    uint32_t x[8];
+    for (int q = 0; q < 8; ++q) x[q] = ld32(a + 4 * q);
+    rec_head_words(x, h);
 }
 
 // bam_read1's own acceptance test (sam.c:421-423): anything else ends iteration silently.
@@ -185,14 +188,18 @@ RGX_HD bool cig_advances_junction_state(uint32_t c) {   // ref-advancing for the
     uint32_t op = c & 0xf; return op == 0 || op == 7 || op == 2 || op == 8 || op == 3;
 }
 
-// bam_endpos (sam.c:336-342)
-RGX_HD int32_t rec_endpos(const uint8_t *cig, uint32_t n_cigar, uint32_t flag, int32_t pos) {
+// bam_endpos (sam.c:336-342); cigar_at(q) = the record's q-th CIGAR word, wherever it lies
+template <class CigarAt>
+RGX_HD int32_t rec_endpos_at(CigarAt &&cigar_at, uint32_t n_cigar, uint32_t flag, int32_t pos) {
     if (!(flag & 4) && n_cigar > 0) {
         int32_t l = 0;
-        for (uint32_t k = 0; k < n_cigar; ++k) l += (int32_t)cig_ref_len(ld32(cig + 4 * (size_t)k));
+        for (uint32_t k = 0; k < n_cigar; ++k) l += (int32_t)cig_ref_len(cigar_at(k));
         return pos + l;
     }
     return pos + 1;
+}
+RGX_HD int32_t rec_endpos(const uint8_t *cig, uint32_t n_cigar, uint32_t flag, int32_t pos) {
+    return rec_endpos_at([&](uint32_t k) { return ld32(cig + 4 * (size_t)k); }, n_cigar, flag, pos);
 }
 
 // The serial state machine of junctions_extractor.cc:377-497.  `emit(start,end,ts,te)` is
@@ -226,6 +233,84 @@ RGX_HD void cigar_walk(int32_t pos, const uint8_t *cig, uint32_t n_cigar, Emit &
 RGX_HD bool intron_ok(uint32_t start, uint32_t end, uint32_t min_intron, uint32_t max_intron) {
     uint32_t l = end - start;
     return !(l < min_intron || l > max_intron);
+}
+
+// ---- the decode rule: one BAM record -> one row of the read table --------------------------------------------------------
+struct ExtractCfg {
+    int32_t  n_ref;
+    int32_t  strandness;           // 0 tag, 1 RF, 2 FR, 3 intron-motif
+    uint8_t  tag0, tag1;
+    uint32_t min_anchor, min_intron, max_intron;
+    int32_t  region_tid;           // -2 = whole file
+    int32_t  region_beg, region_end;
+    uint32_t long_threshold;       // reads with more CIGAR ops than this go to the wave-per-read kernel
+    // intron-motif strand rule (a FASTA was given): file bytes + one descriptor per BAM contig, both in HBM
+    const uint8_t *fa_data;
+    const FaContig *fa_tab;
+    uint32_t *fa_missing;          // [0] set to 1+tid when a junction lies on a contig the FASTA does not have
+    // the iterator's end rule (hts_itr_next, hts.c:1946-1950: the first record read whose tid is not the region's or whose pos is not below
+    // its end finishes the iteration, whatever follows).  stop_out (null = off): [0] = smallest index of such a record (preset ~0),
+    // [1] = 1 + largest index of a record that passed the overlap test (preset 0); records at or behind stop_index are not iterated.
+    uint32_t *stop_out;
+    uint32_t stop_index;
+    uint32_t *insane_out;          // null = the framing made bam_read1's acceptance test itself; else [0] is set when a decoded record fails it (SegGeom::lite_walk)
+    // -s XS: the smallest index of an iterated read with an N operation whose strand tag lies behind an aux field of unknown type (preset ~0; null =
+    // off): the reference's bam_aux_get abort()s on it (sam.c:1233-1252) when the read's first junction asks for its strand (junctions_extractor.cc:283-286)
+    uint32_t *abort_out;
+    uint8_t  bc0, bc1;             // -b: the barcode tag (0 = no -b).  set_junction_barcode asks for it on every read with more than one CIGAR operation, before the
+                                   // CIGAR is looked at (junctions_extractor.cc:393-395): a field of unknown type in front of it (or anywhere, without it) is abort_out's too
+    // `identify -s XS` (one extraction for every window): such reads are COUNTED here (null = off) and marked in bit 7 of their row's strand byte; upstream
+    // abort()s in the first window -- in the order of the variants -- that reads one of them (launch_collect_odd_aux, cse_api.cpp)
+    uint32_t *odd_count;
+};
+
+// What record i of the file means to the extraction: the answers the decode kernels store and count.  Pure: nothing is written, and the
+// pointers of ExtractCfg are only tested for null.
+struct RecordRow {
+    bool in_region;        // the iterator returns the record
+    bool stop_candidate;   // a record of the end rule (ExtractCfg::stop_out): in front of stop_index and not below the region's end
+    bool is_long;          // goes to the wave-per-read emitter
+    bool abort_read;       // ExtractCfg::abort_out's read
+    bool odd_read;         // ExtractCfg::odd_count's read (bit 7 of `strand`)
+    uint8_t strand;
+    uint32_t nev;          // junction events inside -m / -M
+};
+// cigar_at(q) = the q-th CIGAR word; tag_strand(t0, t1, &unknown) = strand_from_tag over the record's aux area -- the two things a kernel reads
+// where the record's bytes lie.  `h` has passed rec_sane (or has been made inert: n_cigar = 0).  The questions are asked in the reference's
+// order, which decides where it aborts: barcode tag, CIGAR, strand tag.
+template <class CigarAt, class TagStrand>
+RGX_HD RecordRow record_row(const RecHead &h, uint32_t i, const ExtractCfg &cfg, CigarAt &&cigar_at, TagStrand &&tag_strand) {
+    RecordRow r = {true, false, false, false, false, (uint8_t)'?', 0};
+    if (cfg.region_tid != -2) {
+        r.in_region = h.tid == cfg.region_tid && h.pos < cfg.region_end;
+        if (cfg.stop_out) {                                // hts_itr_next's end rule (hts.c:1946-1950), see ExtractCfg
+            if (i >= cfg.stop_index) r.in_region = false;
+            else r.stop_candidate = !r.in_region;
+        }
+        if (r.in_region) r.in_region = rec_endpos_at(cigar_at, h.n_cigar, h.flag, h.pos) > cfg.region_beg;
+    }
+    if (!(r.in_region && h.n_cigar > 1 && h.tid >= 0 && h.tid < cfg.n_ref)) return r;
+    if (cfg.bc0 && cfg.abort_out) {                        // -b: the barcode tag is asked for first (the walk is strand_from_tag's; what it finds is the barcode kernels' business)
+        bool unknown = false;
+        (void)tag_strand(cfg.bc0, cfg.bc1, &unknown);
+        r.abort_read = unknown;
+    }
+    bool has_n = false;
+    for (uint32_t q = 0; q < h.n_cigar; ++q) {
+        const uint32_t c = cigar_at(q);
+        if (cig_is_N(c)) { r.nev += intron_ok(0, c >> 4, cfg.min_intron, cfg.max_intron) ? 1u : 0u; has_n = true; }
+    }
+    // (the tag is asked for by every junction the walk reaches, also one junction_qc then drops: any N operation, cc:415 / :447 / :467 / :490)
+    if (r.nev || (has_n && (cfg.abort_out || cfg.odd_count) && cfg.strandness == 0)) {
+        if (cfg.strandness == 0) {
+            bool unknown = false;
+            r.strand = (uint8_t)tag_strand(cfg.tag0, cfg.tag1, &unknown);
+            if (unknown && cfg.abort_out) r.abort_read = true;
+            if (unknown && cfg.odd_count) { r.odd_read = true; r.strand |= 0x80; }
+        } else r.strand = (uint8_t)strand_from_flag(h.flag, cfg.strandness);
+        r.is_long = r.nev && h.n_cigar > cfg.long_threshold;
+    }
+    return r;
 }
 
 }  // namespace rgx

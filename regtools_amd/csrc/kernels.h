@@ -147,33 +147,6 @@ struct ReadSoA {
     uint32_t *n_ev;        // junction events this read contributes (after region filter and junction_qc)
     uint64_t *rec_off;     // optional (may be null): arena offset of the record's block_size word (-b barcodes re-read the aux block)
 };
-struct ExtractCfg {
-    int32_t  n_ref;
-    int32_t  strandness;           // 0 tag, 1 RF, 2 FR, 3 intron-motif
-    uint8_t  tag0, tag1;
-    uint32_t min_anchor, min_intron, max_intron;
-    int32_t  region_tid;           // -2 = whole file
-    int32_t  region_beg, region_end;
-    uint32_t long_threshold;       // reads with more CIGAR ops than this go to the wave-per-read kernel
-    // intron-motif strand rule (a FASTA was given): file bytes + one descriptor per BAM contig, both in HBM
-    const uint8_t *fa_data;
-    const struct FaContig *fa_tab;
-    uint32_t *fa_missing;          // [0] set to 1+tid when a junction lies on a contig the FASTA does not have
-    // the iterator's end rule (hts_itr_next, hts.c:1946-1950: the first record read whose tid is not the region's or whose pos is not below
-    // its end finishes the iteration, whatever follows).  stop_out (null = off): [0] = smallest index of such a record (preset ~0),
-    // [1] = 1 + largest index of a record that passed the overlap test (preset 0); records at or behind stop_index are not iterated.
-    uint32_t *stop_out;
-    uint32_t stop_index;
-    uint32_t *insane_out;          // null = the framing made bam_read1's acceptance test itself; else [0] is set when a decoded record fails it (SegGeom::lite_walk)
-    // -s XS: the smallest index of an iterated read with an N operation whose strand tag lies behind an aux field of unknown type (preset ~0; null =
-    // off): the reference's bam_aux_get abort()s on it (sam.c:1233-1252) when the read's first junction asks for its strand (junctions_extractor.cc:283-286)
-    uint32_t *abort_out;
-    uint8_t  bc0, bc1;             // -b: the barcode tag (0 = no -b).  set_junction_barcode asks for it on every read with more than one CIGAR operation, before the
-                                   // CIGAR is looked at (junctions_extractor.cc:393-395): a field of unknown type in front of it (or anywhere, without it) is abort_out's too
-    // `identify -s XS` (one extraction for every window): such reads are COUNTED here (null = off) and marked in bit 7 of their row's strand byte; upstream
-    // abort()s in the first window -- in the order of the variants -- that reads one of them (launch_collect_odd_aux, cse_api.cpp)
-    uint32_t *odd_count;
-};
 // the reads the decode kernels marked (ExtractCfg::odd_count): out[3 k ..] = tid, pos, bam_endpos of the k-th found (any order); *count = how many (may exceed cap)
 void launch_collect_odd_aux(const uint8_t *arena, ReadSoA soa, uint32_t n_rec, uint32_t cap, uint32_t *count, int32_t *out, hipStream_t stream);
 

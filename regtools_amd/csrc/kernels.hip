@@ -792,6 +792,40 @@ void launch_seg_truncate(SegGeom g, uint32_t n_seg, uint32_t last, uint64_t *seg
 // Scattered 4-byte global reads of the record heads (one 64 B HBM sector per field group) become a streaming read.
 constexpr uint32_t kSegTail = 1024;                      // bytes past the segment end kept in LDS (record bodies)
 constexpr uint32_t kSegMaxRecs = kSegBytes / 36 + 2;     // a record is at least 36 bytes
+
+// What a decode kernel's lane gathers over its records; the kernel says how it walks its segment and where a record's bytes are read from
+// (cigar_at, tag_strand: LDS window or arena), what the record means is bam_core.h's record_row.
+struct DecodeTally { uint32_t n_iter = 0, n_long = 0, first_stop = 0xffffffffu, last_in = 0; };
+// Row i of the read table from the record at arena offset o, and everything the rule's answers cause.
+template <class CigarAt, class TagStrand>
+__device__ __forceinline__ void decode_record(RecHead &h, uint32_t i, uint64_t o, const ExtractCfg &cfg, const ReadSoA &soa, DecodeTally &t,
+                                              CigarAt &&cigar_at, TagStrand &&tag_strand) {
+    // (the framing only looked at block_size: the call starts over with the full walk.  Until then the record is inert: its CIGAR count and its
+    //  aux offset are not to be believed -- a negative l_seq puts the aux walk in front of the arena, 65,535 operations run past its end)
+    if (cfg.insane_out && !rec_sane(h)) { cfg.insane_out[0] = 1; h.n_cigar = 0; }
+    soa.tid[i] = h.tid; soa.pos[i] = h.pos;
+    soa.flag_nc[i] = h.flag << 16 | h.n_cigar;
+    soa.cig_off[i] = o + 36 + h.l_qname;
+    if (soa.rec_off) soa.rec_off[i] = o;
+    const RecordRow r = record_row(h, i, cfg, cigar_at, tag_strand);
+    if (r.stop_candidate) t.first_stop = min(t.first_stop, i);
+    if (r.in_region) { ++t.n_iter; t.last_in = i + 1; }
+    t.n_long += r.is_long ? 1u : 0u;
+    if (r.abort_read) atomicMin(cfg.abort_out, i);
+    if (r.odd_read) atomicAdd(cfg.odd_count, 1u);
+    soa.strand[i] = r.strand;
+    soa.n_ev[i] = r.nev;
+}
+// the wave's candidates of the end rule into ExtractCfg::stop_out
+__device__ __forceinline__ void stop_reduce(uint32_t *stop_out, uint32_t first_stop, uint32_t last_in) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { first_stop = min(first_stop, (uint32_t)__shfl_xor((int)first_stop, d, 64)); last_in = max(last_in, (uint32_t)__shfl_xor((int)last_in, d, 64)); }
+    // (segments are launched roughly in order: after the first few, the values in memory already beat most candidates)
+    if (threadIdx.x == 0) {
+        if (first_stop < *(volatile uint32_t *)&stop_out[0]) atomicMin(&stop_out[0], first_stop);
+        if (last_in > *(volatile uint32_t *)&stop_out[1]) atomicMax(&stop_out[1], last_in);
+    }
+}
 // STAGED = false is the form for long records (kilobytes of sequence and quality per record, two or three records per segment):
 // nothing is staged, heads / CIGAR / aux are read where they lie, and the 95 % of the stream that is sequence and quality never
 // leaves HBM.  The host picks it when the mean record is longer than kSparseRecordBytes.
@@ -846,8 +880,7 @@ __global__ __launch_bounds__(64) void k_decode_seg(const uint8_t *__restrict__ a
     }
     __syncthreads();
     const uint32_t base = seg_base[s];
-    uint32_t n_iter = 0, n_long = 0;
-    uint32_t first_stop = 0xffffffffu, last_in = 0;
+    DecodeTally t;
     for (uint32_t k = lane; k < cnt; k += 64) {
         const uint32_t ro = s_off[k];
         const uint64_t o = w0 + ro;
@@ -867,176 +900,55 @@ __global__ __launch_bounds__(64) void k_decode_seg(const uint8_t *__restrict__ a
 #pragma unroll
                 for (int q = 0; q < 8; ++q) x[q] = ld32(arena + o + 4 * q);
             }
-            h.block_len = (int32_t)x[0]; h.tid = (int32_t)x[1]; h.pos = (int32_t)x[2];
-            h.l_qname = x[3] & 0xff; h.n_cigar = x[4] & 0xffff; h.flag = x[4] >> 16;
-            h.l_qseq = (int32_t)x[5]; h.mtid = (int32_t)x[6];
-            h.aux_off = (int64_t)h.l_qname + 4 * (int64_t)h.n_cigar + (((int64_t)h.l_qseq + 1) >> 1) + h.l_qseq;
+            rec_head_words(x, h);
         }
-        // (the framing only looked at block_size: the call starts over with the full walk.  Until then the record is inert: its CIGAR count and its
-        //  aux offset are not to be believed -- a negative l_seq puts the aux walk in front of the arena, 65,535 operations run past its end)
-        if (cfg.insane_out && !rec_sane(h)) { cfg.insane_out[0] = 1; h.n_cigar = 0; }
         // body (CIGAR, aux) from the LDS window when the whole record is inside it, else straight from the arena
         const uint64_t rec_end = o + 4 + (uint64_t)(uint32_t)h.block_len;
         const bool in_win = STAGED && rec_end <= w1;
         const uint32_t cig_ro = ro + 36 + h.l_qname;
         const uint8_t *g_data = arena + o + 36;
         auto cigar_at = [&](uint32_t q) -> uint32_t { return in_win ? lds32(cig_ro + 4 * q) : ld32(g_data + h.l_qname + 4 * (size_t)q); };
-        const uint32_t i = base + k;
-        soa.tid[i] = h.tid; soa.pos[i] = h.pos;
-        soa.flag_nc[i] = h.flag << 16 | h.n_cigar;
-        soa.cig_off[i] = o + 36 + h.l_qname;
-        if (soa.rec_off) soa.rec_off[i] = o;
-        bool in_region = true;
-        if (cfg.region_tid != -2) {
-            in_region = h.tid == cfg.region_tid && h.pos < cfg.region_end;
-            if (cfg.stop_out) {                                // hts_itr_next's end rule (hts.c:1946-1950), see ExtractCfg
-                if (i >= cfg.stop_index) in_region = false;
-                else if (!in_region) first_stop = min(first_stop, i);
-            }
-            if (in_region) {                                   // bam_endpos (sam.c:336-342)
-                int32_t endpos = h.pos + 1;
-                if (!(h.flag & 4) && h.n_cigar > 0) {
-                    int32_t l = 0;
-                    for (uint32_t q = 0; q < h.n_cigar; ++q) l += (int32_t)cig_ref_len(cigar_at(q));
-                    endpos = h.pos + l;
-                }
-                in_region = endpos > cfg.region_beg;
-            }
-        }
-        n_iter += in_region ? 1u : 0u;
-        if (in_region) last_in = i + 1;
-        uint32_t nev = 0;
-        char strand = '?';
-        uint8_t odd = 0;                                     // bit 7 of the row's strand byte: k_collect_odd_aux (identify)
-        if (in_region && h.n_cigar > 1 && h.tid >= 0 && h.tid < cfg.n_ref) {
-            if (cfg.bc0 && cfg.abort_out) {                   // -b: the barcode tag is asked for first (the walk is strand_from_tag's; what it finds is the barcode kernels' business)
-                const int64_t l_data = (int64_t)h.block_len - 32;
-                bool unknown = false;
-                if (in_win) { const uint8_t *body = s_buf + ro + 36; (void)strand_from_tag(body + h.aux_off, body + l_data, cfg.bc0, cfg.bc1, &unknown); }
-                else (void)strand_from_tag(g_data + h.aux_off, g_data + l_data, cfg.bc0, cfg.bc1, &unknown);
-                if (unknown) atomicMin(cfg.abort_out, i);
-            }
-            bool has_n = false;
-            for (uint32_t q = 0; q < h.n_cigar; ++q) {
-                const uint32_t c = cigar_at(q);
-                if (cig_is_N(c)) { const uint32_t len = c >> 4; nev += !(len < cfg.min_intron || len > cfg.max_intron); has_n = true; }
-            }
-            // (the tag is asked for by every junction the walk reaches, also one junction_qc then drops: any N operation, cc:415 / :447 / :467 / :490)
-            if (nev || (has_n && (cfg.abort_out || cfg.odd_count) && cfg.strandness == 0)) {
-                if (cfg.strandness == 0) {
-                    const int64_t l_data = (int64_t)h.block_len - 32;
-                    bool unknown = false;
-                    // two call sites on purpose: the LDS one compiles to ds_read_u8, the other to global loads (no flat/generic pointer)
-                    if (in_win) { const uint8_t *body = s_buf + ro + 36; strand = strand_from_tag(body + h.aux_off, body + l_data, cfg.tag0, cfg.tag1, &unknown); }
-                    else strand = strand_from_tag(g_data + h.aux_off, g_data + l_data, cfg.tag0, cfg.tag1, &unknown);
-                    if (unknown && cfg.abort_out) atomicMin(cfg.abort_out, i);
-                    if (unknown && cfg.odd_count) { atomicAdd(cfg.odd_count, 1u); odd = 0x80; }
-                } else strand = strand_from_flag(h.flag, cfg.strandness);
-                if (nev) n_long += h.n_cigar > cfg.long_threshold ? 1u : 0u;
-            }
-        }
-        soa.strand[i] = (uint8_t)strand | odd;
-        soa.n_ev[i] = nev;
+        auto tag_strand = [&](uint8_t t0, uint8_t t1, bool *unknown) -> char {
+            const int64_t l_data = (int64_t)h.block_len - 32;
+            // two call sites on purpose: the LDS one compiles to ds_read_u8, the other to global loads (no flat/generic pointer)
+            if (in_win) { const uint8_t *body = s_buf + ro + 36; return strand_from_tag(body + h.aux_off, body + l_data, t0, t1, unknown); }
+            return strand_from_tag(g_data + h.aux_off, g_data + l_data, t0, t1, unknown);
+        };
+        decode_record(h, base + k, o, cfg, soa, t, cigar_at, tag_strand);
     }
     // per-segment totals instead of global atomics: one hot address serialises at ~90 atomics/us
-    n_iter = wave_incl_scan(n_iter); n_long = wave_incl_scan(n_long);
+    const uint32_t n_iter = wave_incl_scan(t.n_iter), n_long = wave_incl_scan(t.n_long);
     if (lane == 63) { seg_iter[s] = n_iter; seg_long[s] = n_long; }
-    if (cfg.stop_out) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { first_stop = min(first_stop, (uint32_t)__shfl_xor((int)first_stop, d, 64)); last_in = max(last_in, (uint32_t)__shfl_xor((int)last_in, d, 64)); }
-        // (segments are launched roughly in order: after the first few, the values in memory already beat most candidates)
-        if (lane == 0) {
-            if (first_stop < *(volatile uint32_t *)&cfg.stop_out[0]) atomicMin(&cfg.stop_out[0], first_stop);
-            if (last_in > *(volatile uint32_t *)&cfg.stop_out[1]) atomicMax(&cfg.stop_out[1], last_in);
-        }
-    }
+    if (cfg.stop_out) stop_reduce(cfg.stop_out, t.first_stop, t.last_in);
 }
 
 // Long records (k_decode_seg<false>'s workload: two or three records per 16 KiB segment), one LANE per segment.  A wave per segment is a workgroup
 // per two records there -- 4 M workgroups of which one lane works, each a chain of dependent gathers (checkpoint, the records' lengths, head, CIGAR, aux):
 // 10.6 ms for config 5's 10 M records.  Here a lane follows its own segment's records from the verified start; sixty-four chains per wave.
-// Same rows, same counts: the per-record part restates k_decode_seg's with every read from the arena.
+// Same rows, same counts: decode_record with every read from the arena.
 __global__ __launch_bounds__(64) void k_decode_sparse(const uint8_t *__restrict__ arena, uint32_t n_seg, const uint64_t *__restrict__ seg_start,
                                                       const uint32_t *__restrict__ seg_base, const uint32_t *__restrict__ seg_cnt, ExtractCfg cfg, ReadSoA soa,
                                                       uint32_t *seg_iter, uint32_t *seg_long, uint32_t s_begin) {
     const uint32_t s = s_begin + blockIdx.x * 64 + threadIdx.x;
-    uint32_t first_stop = 0xffffffffu, last_in = 0;
+    DecodeTally t;
     if (s < n_seg) {
         const uint32_t cnt = seg_cnt[s];
-        uint32_t n_iter = 0, n_long = 0;
-        if (cnt) {
-            uint64_t o = seg_start[s];
-            const uint32_t base = seg_base[s];
-            for (uint32_t k = 0; k < cnt; ++k) {
-                RecHead h;
-                rec_head(arena + o, h);
-                if (cfg.insane_out && !rec_sane(h)) { cfg.insane_out[0] = 1; h.n_cigar = 0; }       // (inert until the full walk, as in k_decode_seg)
-                const uint8_t *g_data = arena + o + 36;
-                auto cigar_at = [&](uint32_t q) -> uint32_t { return ld32(g_data + h.l_qname + 4 * (size_t)q); };
-                const uint32_t i = base + k;
-                soa.tid[i] = h.tid; soa.pos[i] = h.pos;
-                soa.flag_nc[i] = h.flag << 16 | h.n_cigar;
-                soa.cig_off[i] = o + 36 + h.l_qname;
-                if (soa.rec_off) soa.rec_off[i] = o;
-                bool in_region = true;
-                if (cfg.region_tid != -2) {
-                    in_region = h.tid == cfg.region_tid && h.pos < cfg.region_end;
-                    if (cfg.stop_out) {                                // hts_itr_next's end rule (hts.c:1946-1950), see ExtractCfg
-                        if (i >= cfg.stop_index) in_region = false;
-                        else if (!in_region) first_stop = min(first_stop, i);
-                    }
-                    if (in_region) {                                   // bam_endpos (sam.c:336-342)
-                        int32_t endpos = h.pos + 1;
-                        if (!(h.flag & 4) && h.n_cigar > 0) {
-                            int32_t l = 0;
-                            for (uint32_t q = 0; q < h.n_cigar; ++q) l += (int32_t)cig_ref_len(cigar_at(q));
-                            endpos = h.pos + l;
-                        }
-                        in_region = endpos > cfg.region_beg;
-                    }
-                }
-                n_iter += in_region ? 1u : 0u;
-                if (in_region) last_in = i + 1;
-                uint32_t nev = 0;
-                char strand = '?';
-                uint8_t odd = 0;
-                if (in_region && h.n_cigar > 1 && h.tid >= 0 && h.tid < cfg.n_ref) {
-                    if (cfg.bc0 && cfg.abort_out) {
-                        bool unknown = false;
-                        (void)strand_from_tag(g_data + h.aux_off, g_data + ((int64_t)h.block_len - 32), cfg.bc0, cfg.bc1, &unknown);
-                        if (unknown) atomicMin(cfg.abort_out, i);
-                    }
-                    bool has_n = false;
-                    for (uint32_t q = 0; q < h.n_cigar; ++q) {
-                        const uint32_t c = cigar_at(q);
-                        if (cig_is_N(c)) { const uint32_t len = c >> 4; nev += !(len < cfg.min_intron || len > cfg.max_intron); has_n = true; }
-                    }
-                    if (nev || (has_n && (cfg.abort_out || cfg.odd_count) && cfg.strandness == 0)) {
-                        if (cfg.strandness == 0) {
-                            const int64_t l_data = (int64_t)h.block_len - 32;
-                            bool unknown = false;
-                            strand = strand_from_tag(g_data + h.aux_off, g_data + l_data, cfg.tag0, cfg.tag1, &unknown);
-                            if (unknown && cfg.abort_out) atomicMin(cfg.abort_out, i);
-                            if (unknown && cfg.odd_count) { atomicAdd(cfg.odd_count, 1u); odd = 0x80; }
-                        } else strand = strand_from_flag(h.flag, cfg.strandness);
-                        if (nev) n_long += h.n_cigar > cfg.long_threshold ? 1u : 0u;
-                    }
-                }
-                soa.strand[i] = (uint8_t)strand | odd;
-                soa.n_ev[i] = nev;
-                o += 4 + (uint64_t)(uint32_t)h.block_len;
-            }
+        uint64_t o = cnt ? seg_start[s] : 0;
+        const uint32_t base = cnt ? seg_base[s] : 0;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            RecHead h;
+            rec_head(arena + o, h);
+            const uint8_t *g_data = arena + o + 36;
+            auto cigar_at = [&](uint32_t q) -> uint32_t { return ld32(g_data + h.l_qname + 4 * (size_t)q); };
+            auto tag_strand = [&](uint8_t t0, uint8_t t1, bool *unknown) -> char {
+                return strand_from_tag(g_data + h.aux_off, g_data + ((int64_t)h.block_len - 32), t0, t1, unknown);
+            };
+            decode_record(h, base + k, o, cfg, soa, t, cigar_at, tag_strand);
+            o += 4 + (uint64_t)(uint32_t)h.block_len;
         }
-        seg_iter[s] = n_iter; seg_long[s] = n_long;
+        seg_iter[s] = t.n_iter; seg_long[s] = t.n_long;
     }
-    if (cfg.stop_out) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { first_stop = min(first_stop, (uint32_t)__shfl_xor((int)first_stop, d, 64)); last_in = max(last_in, (uint32_t)__shfl_xor((int)last_in, d, 64)); }
-        if (threadIdx.x == 0) {
-            if (first_stop < *(volatile uint32_t *)&cfg.stop_out[0]) atomicMin(&cfg.stop_out[0], first_stop);
-            if (last_in > *(volatile uint32_t *)&cfg.stop_out[1]) atomicMax(&cfg.stop_out[1], last_in);
-        }
-    }
+    if (cfg.stop_out) stop_reduce(cfg.stop_out, t.first_stop, t.last_in);
 }
 
 // list of the reads that go to the wave-per-read kernel, built without atomics: one wave per segment, positions from the

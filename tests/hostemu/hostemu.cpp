@@ -91,6 +91,33 @@ extern "C" int32_t emu_rec_endpos(const uint32_t *cigar, uint32_t n_cigar, uint3
     return rgx::rec_endpos(reinterpret_cast<const uint8_t *>(cigar), n_cigar, flag, pos);
 }
 
+// record_row over one record's bytes (from its block_size word), as the decode kernels call it: the scalar fields of ExtractCfg, and the three
+// optional outputs as on / off flags (the rule only tests those pointers for null).  Returns 0, or -1 for bytes that are not one whole sane record.
+struct emu_row_cfg {
+    int32_t n_ref, strandness; uint8_t tag0, tag1, bc0, bc1; uint32_t min_intron, max_intron; int32_t region_tid, region_beg, region_end;
+    uint32_t long_threshold, stop_index; int32_t stop_on, abort_on, odd_on;
+};
+struct emu_row { int32_t in_region, stop_candidate, is_long, abort_read, odd_read, strand; uint32_t nev; };
+extern "C" int emu_record_row(const uint8_t *rec, size_t len, uint32_t i, const emu_row_cfg *c, emu_row *out) {
+    rgx::RecHead h;
+    if (len < 36) return -1;
+    rgx::rec_head(rec, h);
+    if (!rgx::rec_sane(h) || 4 + (size_t)(uint32_t)h.block_len != len) return -1;
+    static uint32_t on[2];                                  // somewhere for the three pointers to point: never read, never written
+    rgx::ExtractCfg cfg = {};
+    cfg.n_ref = c->n_ref; cfg.strandness = c->strandness; cfg.tag0 = c->tag0; cfg.tag1 = c->tag1; cfg.bc0 = c->bc0; cfg.bc1 = c->bc1;
+    cfg.min_intron = c->min_intron; cfg.max_intron = c->max_intron;
+    cfg.region_tid = c->region_tid; cfg.region_beg = c->region_beg; cfg.region_end = c->region_end;
+    cfg.long_threshold = c->long_threshold; cfg.stop_index = c->stop_index;
+    cfg.stop_out = c->stop_on ? on : nullptr; cfg.abort_out = c->abort_on ? on : nullptr; cfg.odd_count = c->odd_on ? on : nullptr;
+    const uint8_t *data = rec + 36;
+    const rgx::RecordRow r = rgx::record_row(h, i, cfg,
+        [&](uint32_t q) { return rgx::ld32(data + h.l_qname + 4 * (size_t)q); },
+        [&](uint8_t t0, uint8_t t1, bool *unknown) { return rgx::strand_from_tag(data + h.aux_off, data + ((int64_t)h.block_len - 32), t0, t1, unknown); });
+    *out = emu_row{r.in_region, r.stop_candidate, r.is_long, r.abort_read, r.odd_read, r.strand, r.nev};
+    return 0;
+}
+
 // ---- index normalisation (host_io.cpp): BAI / CSI / BGZF-compressed -> what the pipeline reads from it ---------------------------------
 #include "../../regtools_amd/csrc/host_io.h"
 // out[0..4] = n_ref, have_start, start_voff, n_no_coor, n_anchors; got[k] = first listed record start >= targets[k].  0 = not an index

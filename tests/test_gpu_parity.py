@@ -635,6 +635,66 @@ def test_long_record_decode_lane_form_equals_the_wave_form(gpu_ctx, synth_dir):
     assert len(outs[0]) > 1000
 
 
+@pytest.fixture(scope="module")
+def rare_side_files(tmp_path_factory):
+    """The decode rule's rarely taken side in one small file, written twice: as it is (reads/short/rare.bam) and with every sequence padded to 3,000
+    bases (reads/padded/rare.bam: the mean record passes kSparseRecordBytes).  chrT:500-2000 holds spliced reads whose strand tag and barcode tag stand
+    in the clear, behind a B array, or are missing; chrT:2000-5000 the reads with an aux field of unknown type in front of either tag, behind it, or
+    instead of it; chrT:20000-25000 plain spliced reads with, in their middle, one read behind the region's end: the iterator ends there
+    (hts_itr_next's end rule), the reads of the region that follow it are not returned."""
+    from regtools_amd import synth
+    odd, arr = b"ZZq\x01\x02\x03", b"YBBS" + bytes([3, 0, 0, 0, 1, 0, 2, 0, 3, 0])
+    xs, cb = bamio.tagA("XS", "-"), bamio.tagZ("CB", "ACGT-1")
+    benign = [xs + cb, arr + xs + cb, cb, xs, xs + arr + cb, arr + xs]
+    unknown = [odd + xs + cb, xs + odd + cb, xs + cb + odd, cb + odd, xs + odd, odd, cb + odd + xs]
+    paths = {}
+    for name, l_seq in (("short", None), ("padded", 3000)):
+        recs = [bamio.record(0, 600 + 40 * k, "30M%dN30M" % (200 + k), qname="b%d" % k, aux=a, flag=0x53, l_seq=l_seq) for k, a in enumerate(benign * 2)]
+        recs += [bamio.record(0, 2500 + 40 * k, "30M%dN30M" % (300 + k), qname="u%d" % k, aux=a, flag=0x63, l_seq=l_seq) for k, a in enumerate(unknown)]
+        tail = [bamio.record(0, 20000 + 40 * k, "30M%dN30M" % (400 + k % 3), qname="g%d" % k, aux=xs, flag=0x53, l_seq=l_seq) for k in range(16)]
+        tail.insert(9, bamio.record(0, 30000, "30M500N30M", qname="far", aux=xs, l_seq=l_seq))
+        d = tmp_path_factory.mktemp(name)
+        paths[name] = os.path.join(str(d), "rare.bam")
+        bamio.write_bam(paths[name], [("chrT", 1000000), ("chrU", 1000)], recs + tail)
+        synth.index(paths[name])
+    return paths
+
+
+# (arguments, the reference abort()s) -- the first four are the decode rule's own; the last two put the barcode question alone through every form
+RARE_SIDE_RUNS = [(["-s", "XS"], True), (["-s", "XS", "-b", "@BC@"], True), (["-s", "RF", "-r", "chrT:500-5000"], False), (["-s", "XS", "-r", "chrT:20000-25000"], False),
+                  (["-s", "XS", "-b", "@BC@", "-r", "chrT:500-2000"], False), (["-s", "RF", "-b", "@BC@", "-r", "chrT:500-5000"], True)]
+
+
+@pytest.mark.parametrize("args,dies", RARE_SIDE_RUNS, ids=[" ".join(a) for a, _ in RARE_SIDE_RUNS])
+def test_rare_side_of_the_decode_rule_in_every_kernel_form(gpu_ctx, rare_side_files, args, dies):
+    """Abort reads, the barcode question and the end rule through k_decode_seg<true> (short records, the default), k_decode_sparse (short records in
+    128 KiB segments; long records) and k_decode_seg<false> (long records, REGTOOLS_AMD_DECODE=wave), through the CLI run inside the file's directory:
+    status, stdout, stderr and the -b file are the same in every form, and status, stdout and the -b file are the oracle's (which prints nothing on
+    stderr: the tool's is the reference's option echo, the same in every form)."""
+    exe = os.path.join(ROOT, "bin", "regtools-amd")
+    forms = [("short", None), ("short", "lane,131072"), ("padded", "lane,16384"), ("padded", "wave,16384")]
+    got = []
+    for which, knob in forms:
+        d = os.path.dirname(rare_side_files[which])
+        bc = os.path.join(d, "bc.txt")
+        if os.path.exists(bc):
+            os.remove(bc)
+        env = dict(os.environ)
+        env.pop("REGTOOLS_AMD_DECODE", None)
+        if knob:
+            env["REGTOOLS_AMD_DECODE"] = knob
+        r = subprocess.run([exe, "junctions", "extract"] + ["bc.txt" if a == "@BC@" else a for a in args] + ["rare.bam"], cwd=d, env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        got.append((r.returncode, r.stdout, r.stderr, open(bc, "rb").read() if r.returncode == 0 and os.path.exists(bc) else None))
+    assert got[0] == got[1] == got[2] == got[3], [(g[0], len(g[1]), g[2][-200:]) for g in got]
+    obc = os.path.join(os.path.dirname(rare_side_files["short"]), "oracle_bc.txt")
+    rc, out, _ = run_oracle([obc if a == "@BC@" else a for a in args] + [rare_side_files["short"]])
+    assert (rc, out) == got[0][:2]
+    assert rc == (-6 if dies else 0) and (dies or out.count(b"\n") >= 4)
+    if "-b" in args and not dies:
+        assert got[0][3] == open(obc, "rb").read() and len(got[0][3]) > 0
+
+
 def test_arena_placement_trials_leave_the_results_alone(gpu_ctx):
     """Opt-in since round 6 (REGTOOLS_AMD_ARENA=5): a context that is not one-shot times its first large DEFLATE launch into fresh arenas, one at a time, and
     keeps a faster one (rgx_ctx_arena_trials).  The call that calibrates, the calls behind it (on the kept arena, possibly another one than the
