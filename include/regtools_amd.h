@@ -734,6 +734,71 @@ void rgx_cohort_qtl_group_free(rgx_qtl_group_result *q);
 size_t rgx_cohort_format_qtl_group(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
                                    const rgx_qtl_group_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
 
+/* -----------------------------------------------------------------------------------------------------
+ * The trans-sQTL scan of the phenotype table: every table row against every usable variant, genome-wide, keeping only the pairs whose |r| reaches
+ * a threshold -- tensorQTL's map_trans, which is not available to this project: checked against a restatement in exact rationals.
+ *   input                 everything rgx_cohort_qtl_nominal takes except window, with the same errors; r_min in [0, 1] (NaN or a value outside
+ *                         is RGX_ERR_ARG); exclude_cis and exclude_window; max_hits (0: the result's own limit, 2^32 - 2^16)
+ *   basis .. variant v    the nominal scan's, unchanged and by the same code: basis, dot64, residuals, yy and the flat rows, gg and the verdicts,
+ *                         the usable variants in input order
+ *   pairs                 row k meets usable variant v unless the row is flat or -- with exclude_cis -- v is cis to k by the nominal scan's test
+ *                         with window = exclude_window (equal tids and start - min(start, exclude_window) <= pos <= end + exclude_window, the
+ *                         right side saturating at 2^32 - 1).  n_tested = the pairs that met
+ *   per pair              the nominal scan's: ONE chain acc = fma(Y[k][s], G[v][s], acc) in ascending s from +0.0, r = dot / sqrt(yy[k] * gg[v]),
+ *                         slope = dot / gg[v] -- for a pair both scans see, the same bits
+ *   hit                   a pair that met is a hit when bits(|r|) >= bits(r_min), an integer comparison of the two 64-bit patterns (r is never
+ *                         NaN: yy and gg passed their tests).  r_min == +0.0 makes every pair a hit.  No transcendental function runs on the device
+ *   result                the hits as a CSR by row: hit_begin[K + 1], hit_variant[H] (an index into the INPUT variants), r[H], slope[H]; a row's
+ *                         hits in ascending variant order.  H > max_hits is RGX_ERR_ARG with H in the message, known behind the counting pass
+ *                         and before the hit arrays are allocated
+ *   threshold             a p-value becomes r_min on the HOST: rgx_qtl_r_threshold below
+ *   limits                RGX_ERR_DEVICE when workspace cannot be had.  The device cuts K x V into tiles of 64 rows x 64 usable variants; more
+ *                         than 2^31 - 1 tiles is RGX_ERR_ARG
+ * ----------------------------------------------------------------------------------------------------- */
+/* Owned by the library (rgx_cohort_qtl_trans_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_variants;      /* V */
+    uint32_t   n_cov;
+    uint32_t   dof;             /* S - n_cov - 2 */
+    uint64_t   n_tested;        /* the pairs that met */
+    uint64_t   n_hits;          /* H */
+    uint8_t   *variant_verdict; /* V: 0 usable, 1 constant, 2 explained by the covariates */
+    double    *yy;              /* K */
+    double    *gg;              /* V */
+    uint32_t  *hit_begin;       /* K + 1 */
+    uint32_t  *hit_variant;     /* H */
+    double    *r, *slope;       /* H */
+    /* statistics */
+    uint64_t   n_constant, n_explained, n_flat_rows;
+    uint64_t   n_tiles;         /* the device's tiles of 64 rows x 64 variants (the twin: 0) */
+    uint64_t   n_hit_tiles;     /* those with a hit, which the device computes twice (the twin: 0) */
+    double     ms_trans;        /* this call, wall */
+    double     ms_residual;     /* device time from the first upload to the sample-major residuals (the twin: its residual loops, wall) */
+    double     ms_count;        /* device time of the counting pass over every tile up to its totals (the twin: its pair loops, wall) */
+    double     ms_emit;         /* device time from the hit tiles' products to the hits in order (the twin: 0) */
+} rgx_qtl_trans_result;
+/* On the cohort's device and stream: the nominal scan's stages up to the sample-major residuals, one workgroup per (64 rows, 64 usable variants)
+ * that counts its hits, 64-bit totals and two scans, ONE host wait for H, then one workgroup per tile with hits, a stable sort on the row and
+ * the copies back. */
+int  rgx_cohort_qtl_trans(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                          const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, double r_min, int exclude_cis,
+                          uint32_t exclude_window, uint64_t max_hits, rgx_qtl_trans_result **out, char *err, size_t errlen);
+/* Host twin: the same chains in plain C++ (std::fma), rows shared among threads, no device.  NOT a fallback. */
+int  rgx_cohort_qtl_trans_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                               const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, double r_min,
+                               int exclude_cis, uint32_t exclude_window, uint64_t max_hits, rgx_qtl_trans_result **out, char *err, size_t errlen);
+void rgx_cohort_qtl_trans_free(rgx_qtl_trans_result *q);
+/* The smallest double r in [0, 1] with rgx_qtl_pvalue(rgx_qtl_tstat(r, dof), dof) <= p, by bisection on the 64-bit patterns between +0.0 and 1.0:
+ * the low end fails, the high end passes, the high end is returned -- the definition is this algorithm.  p >= 1 gives +0.0; p < 0, a NaN p and
+ * dof == 0 give NaN. */
+double rgx_qtl_r_threshold(double p, uint32_t dof);
+/* "phenotype_id\tvariant_id\tr\tslope\tslope_se\ttstat\tpval" and one line per hit in CSR order; IDs and number formats of rgx_cohort_format_qtl.
+ * q == NULL writes the header line alone; 0 when the arguments do not fit together.  Buffer protocol of rgx_cohort_format_counts. */
+size_t rgx_cohort_format_qtl_trans(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
+                                   const rgx_qtl_trans_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
+
 /* The genotypes of a cohort's samples from a VCF (plain, gzip, bgzip) or a BCF, as rgx_cohort_qtl_nominal takes them.  Samples are matched to
  * m->sample_name BY NAME; a cohort sample the file does not have is RGX_ERR_ARG, "Sample <name> has no genotypes in <file>".  A record is
  * skipped, and counted, when it is multi-allelic (anything but one ALT), carries no GT, or lies on a contig m does not know.  The dosage is the

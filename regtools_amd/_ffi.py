@@ -65,6 +65,7 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm",
            "rgx_cohort_pheno_groups", "rgx_cohort_qtl_permute_grouped", "rgx_cohort_qtl_permute_grouped_host", "rgx_cohort_qtl_group_free",
            "rgx_cohort_format_qtl_group",
+           "rgx_cohort_qtl_trans", "rgx_cohort_qtl_trans_host", "rgx_cohort_qtl_trans_free", "rgx_qtl_r_threshold", "rgx_cohort_format_qtl_trans",
            "rgx_gtf_bin_index", "rgx_k_junction_scan", "rgx_junction_items_free", "rgx_pair_list_free", "rgx_k_window_pairs", "rgx_k_assoc_pairs"]
 
 
@@ -132,6 +133,16 @@ class QtlResult(C.Structure):
                 ("slope", C.POINTER(C.c_double)), ("best", C.POINTER(C.c_uint32)),
                 ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
                 ("ms_qtl", C.c_double), ("ms_residual", C.c_double), ("ms_pairs", C.c_double)]
+
+
+class QtlTransResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("dof", C.c_uint32),
+                ("n_tested", C.c_uint64), ("n_hits", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)), ("yy", C.POINTER(C.c_double)),
+                ("gg", C.POINTER(C.c_double)), ("hit_begin", C.POINTER(C.c_uint32)), ("hit_variant", C.POINTER(C.c_uint32)),
+                ("r", C.POINTER(C.c_double)), ("slope", C.POINTER(C.c_double)),
+                ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("n_hit_tiles", C.c_uint64), ("ms_trans", C.c_double), ("ms_residual", C.c_double), ("ms_count", C.c_double),
+                ("ms_emit", C.c_double)]
 
 
 class QtlPermResult(C.Structure):
@@ -382,6 +393,15 @@ def lib():
         L.rgx_cohort_format_qtl_group.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlGroupResult), C.c_void_p, P(C.c_char_p),
                                                   C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_qtl_group.restype = C.c_size_t
+        trans_in = qtl_in[:8] + [C.c_double, C.c_int, C.c_uint32, C.c_uint64, P(P(QtlTransResult)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_trans.argtypes = [C.c_void_p] + trans_in
+        L.rgx_cohort_qtl_trans_host.argtypes = trans_in
+        L.rgx_cohort_qtl_trans_free.argtypes = [P(QtlTransResult)]
+        L.rgx_qtl_r_threshold.argtypes = [C.c_double, C.c_uint32]
+        L.rgx_qtl_r_threshold.restype = C.c_double
+        L.rgx_cohort_format_qtl_trans.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlTransResult), C.c_void_p, P(C.c_char_p),
+                                                  C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_qtl_trans.restype = C.c_size_t
         L.rgx_k_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib

@@ -503,6 +503,66 @@ def qtl_permute_grouped_host(ph, regions, groups, n_groups, var_tid, var_pos, do
                           seed, perms, groups, n_groups)
 
 
+class CohortQTLTrans(_Owned):
+    """rgx_qtl_trans_result: the trans-sQTL scan of a phenotype table -- per variant its verdict and gg, per row yy, and the hits (the pairs whose
+    |r| reaches r_min) as a CSR by row (hit_begin, hit_variant: an index into the input variants) with r and slope, a row's hits in ascending
+    variant order; n_tested is the number of pairs that met.  The array attributes are numpy VIEWS of memory this object owns."""
+    _free = "rgx_cohort_qtl_trans_free"
+
+    def __init__(self, handle):
+        import numpy as np
+        _Owned.__init__(self, handle)
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.dof, self.n_tested, self.n_hits = int(p.n_cov), int(p.dof), int(p.n_tested), int(p.n_hits)
+        self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
+        self.n_tiles, self.n_hit_tiles = int(p.n_tiles), int(p.n_hit_tiles)
+        self.ms_trans, self.ms_residual, self.ms_count, self.ms_emit = p.ms_trans, p.ms_residual, p.ms_count, p.ms_emit
+        view = self._view
+        K, V, n = self.n_rows, self.n_variants, self.n_hits
+        self.variant_verdict = view(p.variant_verdict, V, np.uint8)
+        self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
+        self.hit_begin, self.hit_variant = view(p.hit_begin, K + 1, np.uint32), view(p.hit_variant, n, np.uint32)
+        self.r, self.slope = view(p.r, n, np.float64), view(p.slope, n, np.float64)
+
+    def text(self, matrix, clusters, ph, var_pos, variant_ids):
+        """The hits as text: phenotype_id, variant_id, r, slope, slope_se, tstat, pval; one line per hit.  Arguments as CohortQTL.text."""
+        return _qtl_text(self._lib.rgx_cohort_format_qtl_trans, self, matrix, clusters, ph, var_pos, variant_ids)
+
+
+def qtl_r_threshold(pval, dof):
+    """rgx_qtl_r_threshold: the smallest |r| whose two-sided p with dof degrees of freedom is at most pval, by bisection on the host."""
+    return _ffi.lib().rgx_qtl_r_threshold(pval, dof)
+
+
+def _qtl_trans_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, r_min, pval, exclude_window, max_hits):
+    import numpy as np
+    S = ph.n_samples
+    reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1, 3)
+    tid, pos = np.ascontiguousarray(var_tid, dtype=np.uint32), np.ascontiguousarray(var_pos, dtype=np.uint32)
+    dos = np.ascontiguousarray(dosage, dtype=np.int8).reshape(-1, S) if S else np.zeros((0, 0), np.int8)
+    cov = np.ascontiguousarray(covariates, dtype=np.float64).reshape(-1, S) if covariates is not None and len(covariates) else np.zeros((0, S))
+    if len(reg) != ph.n_rows or len(pos) != len(tid) or len(dos) != len(tid):
+        raise ValueError("one region per table row, one position and one row of dosages per variant")
+    if exclude_window is not None and not 0 <= int(exclude_window) <= 0xffffffff:
+        raise ValueError("exclude_window must fit 32 bits")
+    if not 0 <= int(max_hits) < 1 << 64:
+        raise ValueError("max_hits must fit 64 bits")
+    if r_min is None:
+        r_min = qtl_r_threshold(pval, max(S - len(cov) - 2, 0)) if S >= len(cov) + 3 else 0.0      # (too few samples: the call says so)
+    return _call(fn, _ffi.QtlTransResult, CohortQTLTrans, *(front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data,
+                 dos.ctypes.data, len(cov), cov.ctypes.data, float(r_min), 0 if exclude_window is None else 1,
+                 0 if exclude_window is None else int(exclude_window), int(max_hits))))
+
+
+def qtl_trans_host(ph, regions, var_tid, var_pos, dosage, covariates=None, r_min=None, pval=1e-5, exclude_window=5000000, max_hits=0):
+    """rgx_cohort_qtl_trans_host: the trans-sQTL scan by the library's plain C++ twin, no device involved.  The inputs are qtl_nominal_host's
+    without the window; r_min: the smallest |r| kept, None for qtl_r_threshold(pval, dof); exclude_window: pairs within it of the row's intron are
+    left out, None keeps them; max_hits: refuse more hits than this, 0 for the result's own limit."""
+    return _qtl_trans_call(_ffi.lib().rgx_cohort_qtl_trans_host, (), ph, regions, var_tid, var_pos, dosage, covariates, r_min, pval,
+                           exclude_window, max_hits)
+
+
 class PlantedPhenotypes(object):
     """A K x S uint32 array as the rgx_pheno_table the principal component calls read (n_rows, n_samples and rank2 alone are set).  The memory is
     the array's own (a C-contiguous copy when it is not one already), kept alive by this object."""
@@ -633,6 +693,12 @@ class Cohort(object):
         of the identity, and on the host the empirical p and its beta approximation.  The arguments are qtl_permute_grouped_host's."""
         return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute_grouped, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window,
                               n_perm, seed, perms, groups, n_groups)
+
+    def qtl_trans(self, ph, regions, var_tid, var_pos, dosage, covariates=None, r_min=None, pval=1e-5, exclude_window=5000000, max_hits=0):
+        """The trans-sQTL scan on this cohort's device (rgx_cohort_qtl_trans): every row against every usable variant, only the pairs whose |r|
+        reaches r_min kept.  Returns a CohortQTLTrans; the arguments are qtl_trans_host's."""
+        return _qtl_trans_call(self._lib.rgx_cohort_qtl_trans, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, r_min, pval,
+                               exclude_window, max_hits)
 
     def run(self, files, depth=2, **extract_kw):
         """Extracts `files` through a Pipeline of `depth` and adds each.  An item is a path, or (path, name), or (path, name, kw) with that file's own

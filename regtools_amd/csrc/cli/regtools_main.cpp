@@ -283,6 +283,10 @@ void cohort_usage(std::ostream &out) {
         << "\t\t\t Needs -g; everything else as for -R, beside which (and beside -Q) it may stand.\n"
         << "\t\t-B INT\tThe permutations of -R and -G, 1 to 65535. [1000]\n"
         << "\t\t-e INT\tThe seed of -R's and -G's permutations. [0]\n"
+        << "\t\t-X FILE\tThe trans-sQTL scan: every row of the -q table against EVERY variant of -g, with the model of -Q: one line per pair whose\n"
+        << "\t\t\t two-sided p is at most -u, with r, slope, its standard error, t and p. Needs -g; the table and the components are those of -Q.\n"
+        << "\t\t-u FLOAT\tThe p-value threshold of -X, above 0 and at most 1. [1e-5]\n"
+        << "\t\t-W INT\tLeave out of -X the variants within this distance of the row's intron; 'off' keeps them. [5000000]\n"
         << "\t\t-A\tTake every junction of a sample, not only those anchored on both sides.\n"
         << "\t\t-n INT\tKeep junctions seen in at least INT samples. [1]\n"
         << "\t\t-N INT\tKeep junctions with at least INT reads over all samples. [1]\n"
@@ -351,6 +355,10 @@ int junctions_cohort(int argc, char **argv) {
         std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA", perm = "NA", grouped = "NA";
         uint32_t n_components = 10, window = 100000, n_perm = 1000;
         uint64_t seed = 0;
+        std::string trans = "NA";
+        double trans_pval = 1e-5;
+        bool trans_exclude = true;
+        uint32_t trans_window = 5000000;
         rgx_pheno_params qp;
         rgx_pheno_params_default(&qp);
         rgx_cohort_params cp;
@@ -363,7 +371,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:G:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:G:X:u:W:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -399,6 +407,23 @@ int junctions_cohort(int argc, char **argv) {
                 }
                 case 'R': perm = optarg; break;
                 case 'G': grouped = optarg; break;
+                case 'X': trans = optarg; break;
+                case 'u': {
+                    char *end = nullptr;
+                    trans_pval = strtod(optarg, &end);
+                    if (end == optarg || *end || !(trans_pval > 0 && trans_pval <= 1)) throw std::runtime_error("Unrecognized threshold argument!\n\n");
+                    break;
+                }
+                case 'W': {
+                    if (std::string(optarg) == "off") { trans_exclude = false; break; }
+                    char *end = nullptr;
+                    errno = 0;
+                    const long long v = strtoll(optarg, &end, 10);
+                    if (end == optarg || *end || errno || v < 0 || v > 0xffffffffll || optarg[0] == ' ' || optarg[0] == '+' || optarg[0] == '-')
+                        throw std::runtime_error("Unrecognized exclusion argument!\n\n");
+                    trans_exclude = true; trans_window = (uint32_t)v;
+                    break;
+                }
                 case 'B': {
                     char *end = nullptr;
                     errno = 0;
@@ -463,7 +488,7 @@ int junctions_cohort(int argc, char **argv) {
         for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
         if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
         if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
-        if ((qtl != "NA" || perm != "NA" || grouped != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
+        if ((qtl != "NA" || perm != "NA" || grouped != "NA" || trans != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
         for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
         for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
             throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
@@ -510,7 +535,8 @@ int junctions_cohort(int argc, char **argv) {
         if (ok && rgx_cohort_finish(co, &m, err, sizeof err) != RGX_OK) { failure = err; ok = false; }
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
-        const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_group = grouped != "NA", want_scan = want_qtl || want_perm || want_group;
+        const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_group = grouped != "NA", want_trans = trans != "NA",
+                   want_scan = want_qtl || want_perm || want_group || want_trans;
         const bool want_pheno = phenotypes != "NA" || components != "NA" || want_scan;
         if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
@@ -529,6 +555,7 @@ int junctions_cohort(int argc, char **argv) {
         rgx_qtl_result *qr = nullptr;
         rgx_qtl_perm_result *pr = nullptr;
         rgx_qtl_group_result *gr = nullptr;
+        rgx_qtl_trans_result *tr = nullptr;
         if (ok && want_scan && ph->n_rows) {
             std::vector<rgx_qtl_region> regions((size_t)ph->n_rows);
             int rc = rgx_cohort_pheno_regions(m, ph, regions.data(), err, sizeof err);
@@ -548,9 +575,14 @@ int junctions_cohort(int argc, char **argv) {
                                                                           group.data(), &gr, err, sizeof err);
                 }
             }
+            // -X: the p-value threshold becomes the smallest |r| kept (too few samples for a degree of freedom: the call says so)
+            if (rc == RGX_OK && want_trans) rc = rgx_cohort_qtl_trans(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
+                pcs ? pcs->component : nullptr, ph->n_samples >= n_cov + 3 ? rgx_qtl_r_threshold(trans_pval, ph->n_samples - n_cov - 2) : 0.0,
+                trans_exclude ? 1 : 0, trans_window, 0, &tr, err, sizeof err);
             if (rc != RGX_OK) { failure = err; ok = false; }
         }
         if (!ok) {
+            rgx_cohort_qtl_trans_free(tr);
             rgx_cohort_qtl_group_free(gr);
             rgx_cohort_qtl_perm_free(pr);
             rgx_cohort_qtl_free(qr);
@@ -591,6 +623,10 @@ int junctions_cohort(int argc, char **argv) {
         if (want_group) {
             ng = rgx_cohort_format_qtl_group(m, cl, ph, gr, gt->pos, gt->id, nullptr, 0); gtx.reset(new char[ng + 1]);
             rgx_cohort_format_qtl_group(m, cl, ph, gr, gt->pos, gt->id, gtx.get(), ng); }
+        size_t nx = 0; std::unique_ptr<char[]> xtx;
+        if (want_trans) {
+            nx = rgx_cohort_format_qtl_trans(m, cl, ph, tr, gt->pos, gt->id, nullptr, 0); xtx.reset(new char[nx + 1]);
+            rgx_cohort_format_qtl_trans(m, cl, ph, tr, gt->pos, gt->id, xtx.get(), nx); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -629,6 +665,11 @@ int junctions_cohort(int argc, char **argv) {
             FILE *g = fopen(grouped.c_str(), "w");
             if (!g) throw std::runtime_error("Unable to write " + grouped + "\n\n");
             short_write |= fwrite(gtx.get(), 1, ng, g) != ng; short_write |= fclose(g) != 0;
+        }
+        if (want_trans) {
+            FILE *g = fopen(trans.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + trans + "\n\n");
+            short_write |= fwrite(xtx.get(), 1, nx, g) != nx; short_write |= fclose(g) != 0;
         }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
@@ -669,6 +710,13 @@ int junctions_cohort(int argc, char **argv) {
                     (unsigned long long)(gr ? gr->n_tiles : 0), gr ? gr->ms_perm : 0.0, gr ? gr->ms_residual : 0.0, gr ? gr->ms_products : 0.0,
                     gr ? gr->ms_beta : 0.0);
         }
+        if (want_trans && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] trans: p <= %g, exclusion %s, %u variants, %u covariates, %llu pairs tested, %llu hits written, %llu tiles, "
+                    "%llu with hits, %.3f ms (residuals %.3f ms, count %.3f ms, emit %.3f ms)\n", trans_pval,
+                    trans_exclude ? std::to_string(trans_window).c_str() : "off", gt->n_variants, n_cov, (unsigned long long)(tr ? tr->n_tested : 0),
+                    (unsigned long long)(tr ? tr->n_hits : 0), (unsigned long long)(tr ? tr->n_tiles : 0), (unsigned long long)(tr ? tr->n_hit_tiles : 0),
+                    tr ? tr->ms_trans : 0.0, tr ? tr->ms_residual : 0.0, tr ? tr->ms_count : 0.0, tr ? tr->ms_emit : 0.0);
+        rgx_cohort_qtl_trans_free(tr);
         rgx_cohort_qtl_group_free(gr);
         rgx_cohort_qtl_perm_free(pr);
         rgx_cohort_qtl_free(qr);

@@ -119,6 +119,8 @@ struct rgx_cohort {
     DevBuf qt_in, qt_rows, qt_t, qt_out;
     // rgx_cohort_qtl_permute (cohort_qtl_perm.cpp; the four above are shared with it): the sample-major permutations, perm_r with the best pairs
     DevBuf qp_in, qp_out;
+    // rgx_cohort_qtl_trans (cohort_qtl_trans.cpp; qt_in, qt_rows and qt_t are shared with it, qt_out holds its hits): the per-tile words
+    DevBuf qx_tiles;
 };
 
 // cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the

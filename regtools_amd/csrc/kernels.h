@@ -410,4 +410,29 @@ void launch_qtl_perm_best(const double *Y, const double *G, uint32_t n_series, u
                           const uint32_t *u_var, const double *yy, const double *gg, uint32_t *best_variant, double *best_r, double *best_slope,
                           hipStream_t st);
 
+// ---- the trans-sQTL scan (qtl_trans_kernels.hip; host side in cohort_qtl_trans.cpp) -----------------------------------------------------------------
+// What both product kernels read: the sample-major panels of launch_qtl_pairs, n_blocks x n_vt tiles of 64 rows x 64 usable variants (tile =
+// row block * n_vt + variant tile), the rows' regions (3 words each) and yy, the usable variants' keys and gg, their number on the device, and
+// the test: bits(|r|) >= r_min_bits, and with exclude_cis no pair inside exclude_window
+struct QtlTransTiles {
+    const double *Yt; size_t ldy; const double *Gt; size_t ldg; uint32_t S, K, n_blocks, n_vt;
+    const uint32_t *regions; const double *yy, *u_gg; const uint64_t *u_key; const uint32_t *n_usable;
+    uint64_t r_min_bits; uint32_t exclude_cis, exclude_window;
+};
+// per tile its hits, the pairs that met and hits != 0 as a word for the scan; tiles behind the last usable variant get zeros.  band: the row
+// blocks of a super-tile in the tile-to-workgroup mapping (speed alone; 0: workgroup b runs tile b)
+void launch_qtl_trans_count(const QtlTransTiles &t, uint32_t band, uint32_t *tile_hits, uint32_t *tile_tested, uint32_t *tile_flag, hipStream_t st);
+// out[0] = H and out[1] = the pairs that met as 64-bit sums, out[2] = *n_hit_tiles, out[3] = the two flag words, out[4] = *n_usable
+void launch_qtl_trans_totals(const uint32_t *tile_hits, const uint32_t *tile_tested, uint32_t n_tiles, const uint32_t *n_hit_tiles,
+                             const uint32_t *flag, const uint32_t *n_usable, unsigned long long *out, hipStream_t st);
+// hit_tile[place[t]] = t for the tiles with tile_flag[t]
+void launch_qtl_trans_hit_tiles(const uint32_t *tile_flag, const uint32_t *place, uint32_t n_tiles, uint32_t *hit_tile, hipStream_t st);
+// one workgroup per listed tile: its hits at tile_off[tile] + their rank inside the tile (rows, then variants): row, usable variant, r, slope
+void launch_qtl_trans_emit(const QtlTransTiles &t, const uint32_t *hit_tile, uint32_t n_hit_tiles, const uint32_t *tile_off, uint32_t *hit_row,
+                           uint32_t *hit_u, double *hit_r, double *hit_slope, hipStream_t st);
+// the hits in the order perm (null: as they are): their rows, input variants, r and slope; then hit_begin[k] = the first hit of a row >= k, k <= K
+void launch_qtl_trans_order(const uint32_t *perm, uint32_t H, const uint32_t *hit_row, const uint32_t *hit_u, const double *hit_r,
+                            const double *hit_slope, const uint32_t *u_var, uint32_t K, uint32_t *row_sorted, uint32_t *hit_variant, double *r,
+                            double *slope, uint32_t *hit_begin, hipStream_t st);
+
 }  // namespace rgx

@@ -39,6 +39,10 @@ RGX_HD uint64_t qtl_key_last(uint32_t tid, uint32_t end, uint32_t window) {
     const uint64_t e = (uint64_t)end + window;
     return qtl_key(tid, e > 0xffffffffull ? 0xffffffffu : (uint32_t)e);
 }
+// the same test for one variant's key: what the trans scan leaves out (a region whose last key lies in front of its first reaches nothing)
+RGX_HD bool qtl_key_is_cis(uint64_t key, uint32_t tid, uint32_t start, uint32_t end, uint32_t window) {
+    return key >= qtl_key_first(tid, start, window) && key <= qtl_key_last(tid, end, window);
+}
 // the first of the ascending keys[0 .. n) that is not below key (strict: above key)
 RGX_HD uint32_t qtl_bound(const uint64_t *keys, uint32_t n, uint64_t key, bool strict) {
     uint32_t lo = 0, hi = n;

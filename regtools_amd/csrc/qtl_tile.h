@@ -1,5 +1,6 @@
-// qtl_tile.h -- the one slab loop of the cis-sQTL product kernels (device only): k_qtl_pairs (qtl_kernels.hip) and k_qtl_perm
-// (qtl_perm_kernels.hip) run it; they differ in where an entry of the A panel comes from, which a small source type says.
+// qtl_tile.h -- the one slab loop of the sQTL product kernels (device only): k_qtl_pairs (qtl_kernels.hip), k_qtl_perm (qtl_perm_kernels.hip)
+// and k_qtl_trans_count / k_qtl_trans_emit (qtl_trans_kernels.hip) run it; they differ in where an entry of the A panel comes from, which a
+// small source type says.
 #pragma once
 #include "kernels.h"
 #include "qtl_core.h"

@@ -43,6 +43,11 @@
                     permutations (default 1000, seed 0): first and warm calls; P (B + 1) S fused multiply-adds of the contract over ms_products as
                     GFMA/s, the 4,096 S per tile that were issued, the tile fill; rgx_cohort_qtl_permute_host where its P (B + 1) S stay below
                     --host-fmas (default 2e11), identical as bit patterns; and ms_pairs of rgx_cohort_qtl_nominal on the same inputs beside it
+  --trans           rgx_cohort_qtl_trans (ms_trans, ms_residual, ms_count, ms_emit) on --qtl's planted tables at p <= --pval
+                    (default 1e-5) with the pairs inside --window left out: --reps calls with the tile mapping's super-tiles of --band row blocks
+                    (default 4) and --reps without the mapping; the 4,096 S fused multiply-adds issued per tile over ms_count as GFMA/s; beside it
+                    rgx_cohort_qtl_nominal under the widest window on the same inputs, whose tiles are all full, as the yardstick; the twin where
+                    its K U S stay below --host-fmas; every device run identical to the others and to the twin
 
 Kernel times come from a run of its own:  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_cohort.py --part finish --no-host"""
 import argparse
@@ -509,6 +514,77 @@ def part_qtl(a):
     co.close()
 
 
+TRANS_ARRAYS = ("variant_verdict", "yy", "gg", "hit_begin", "hit_variant", "r", "slope")
+
+
+def same_trans(a, b):
+    def bits(x):
+        x = np.ascontiguousarray(x)
+        return x.view(np.uint64) if x.dtype == np.float64 else x
+    return (a.n_hits, a.n_tested) == (b.n_hits, b.n_tested) and all(np.array_equal(bits(getattr(a, k)), bits(getattr(b, k))) for k in TRANS_ARRAYS)
+
+
+def part_trans(a):
+    """rgx_cohort_qtl_trans on --qtl's planted tables at p <= --pval, the cis pairs inside --window left out: --reps calls with the tile mapping's
+    super-tiles (--band row blocks) and --reps without the mapping, every one identical; the issued fused multiply-adds (4,096 S per tile of usable
+    variants) over the best warm ms_count; beside it, in the same process on the same inputs, rgx_cohort_qtl_nominal under the widest window, whose
+    tiles are all full: k_qtl_pairs, the same slab loop, as the yardstick.  The twin runs when its fused multiply-adds stay below --host-fmas."""
+    import regtools_amd
+    from regtools_amd import cohort
+    co = regtools_amd.Cohort(ctx=regtools_amd.Context(0))
+    for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
+        S, K, V = [int(x) for x in size.lower().split("x")]
+        t0 = time.time()
+        ph, regions, pos, dosage, pcs, n_cov = planted_qtl_inputs(a, co, S, K, V)
+        args = (ph, regions, np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None)
+        kw = dict(pval=a.pval, exclude_window=a.window)
+        line = {"part": "trans", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "pval": a.pval, "exclude_window": a.window,
+                "s_generate": round(time.time() - t0, 1)}
+        runs = {}
+        for band in (a.band, 0):
+            os.environ["REGTOOLS_AMD_TRANS_BAND"] = str(band)
+            runs[band] = [co.qtl_trans(*args, **kw) for _ in range(a.reps)]
+        del os.environ["REGTOOLS_AMD_TRANS_BAND"]
+        first = runs[a.band][0]
+        U = int((first.variant_verdict == 0).sum())
+        issued = 4096.0 * S * ((K + 63) // 64) * ((U + 63) // 64)
+        line.update({"usable_variants": U, "flat_rows": first.n_flat_rows, "tested": first.n_tested, "hits": first.n_hits, "tiles": first.n_tiles,
+                     "hit_tiles": first.n_hit_tiles, "fmas_issued": issued, "r_min": cohort.qtl_r_threshold(a.pval, first.dof)})
+        for band, name in ((a.band, "band%d" % a.band), (0, "unmapped")):
+            rs = runs[band]
+            best = min((rs[1:] or rs), key=lambda q: q.ms_count)
+            line.update({"ms_trans_" + name: [round(q.ms_trans, 3) for q in rs], "ms_count_" + name: [round(q.ms_count, 3) for q in rs],
+                         "ms_emit_" + name: [round(q.ms_emit, 3) for q in rs], "ms_residual_" + name: [round(q.ms_residual, 3) for q in rs],
+                         "GFMA_per_s_issued_count_" + name: round(issued / best.ms_count / 1e6, 1) if best.ms_count > 0 else None})
+        every = runs[a.band] + runs[0]
+        line["identical_every_time"] = bool(all(same_trans(every[0], q) for q in every[1:]))
+        assert line["identical_every_time"], "two device runs differ"
+        # the yardstick stores every pair (20 bytes each): on the same inputs up to 2^26 pairs, else on a table of fewer rows and the same variants
+        Kn = K if K * V <= 1 << 26 else max(64, (1 << 26) // V // 64 * 64)
+        if Kn * V <= 1 << 28:
+            n_args = args
+            if Kn != K:
+                ph_n, regions_n, pos_n, dosage_n, pcs_n, _ = planted_qtl_inputs(a, co, S, Kn, V)
+                n_args = (ph_n, regions_n, np.zeros(V, np.uint32), pos_n, dosage_n, pcs_n.component if pcs_n else None)
+            nominal = [co.qtl_nominal(*n_args, 0xffffffff) for _ in range(a.reps)]
+            best = min((nominal[1:] or nominal), key=lambda q: q.ms_pairs)
+            line.update({"nominal_rows": Kn, "nominal_pairs": nominal[0].n_pairs, "nominal_tiles": nominal[0].n_tiles,
+                         "nominal_tile_fill": round(nominal[0].n_pairs / (4096.0 * nominal[0].n_tiles), 3) if nominal[0].n_tiles else None,
+                         "nominal_ms_pairs": [round(q.ms_pairs, 3) for q in nominal],
+                         "GFMA_per_s_issued_nominal_pairs": round(4096.0 * nominal[0].n_tiles * S / best.ms_pairs / 1e6, 1) if best.ms_pairs > 0 else None})
+            for q in nominal:
+                q.close()
+        if not a.no_host and float(K) * U * S <= a.host_fmas:
+            h = cohort.qtl_trans_host(*args, **kw)
+            line.update({"ms_trans_host": round(h.ms_trans, 1), "ms_count_host": round(h.ms_count, 1), "identical_to_host": bool(same_trans(every[0], h))})
+            assert line["identical_to_host"], "the device's scan differs from the host twin's"
+            h.close()
+        for q in every:
+            q.close()
+        print(json.dumps(line), flush=True)
+    co.close()
+
+
 PERM_ARRAYS = ("variant_verdict", "yy", "gg", "n_cis", "perm_r", "best_variant", "best_r", "best_slope", "n_ge", "p_perm", "beta_shape1", "beta_shape2",
                "p_beta", "beta_status")
 
@@ -687,6 +763,9 @@ def main():
     ap.add_argument("--qtl", action="store_true", help="the sQTL scan part, alone")
     ap.add_argument("--perm", action="store_true", help="the sQTL permutation part, alone")
     ap.add_argument("--group", action="store_true", help="the grouped sQTL permutation part beside the ungrouped one, alone")
+    ap.add_argument("--trans", action="store_true", help="the trans sQTL scan part beside the nominal scan's product kernel, alone")
+    ap.add_argument("--pval", type=float, default=1e-5, help="--trans: the p-value threshold")
+    ap.add_argument("--band", type=int, default=4, help="--trans: row blocks of a super-tile in the tile mapping (beside 0: no mapping)")
     ap.add_argument("--perms", type=int, default=1000, help="--perm: permutations")
     ap.add_argument("--host-fmas", type=float, default=2e11, help="--perm: the twin runs when its fused multiply-adds stay below this")
     ap.add_argument("--n-cov", type=int, default=10, help="--qtl: principal components taken as covariates (clipped to the samples less three)")
@@ -711,6 +790,8 @@ def main():
         return part_pcs(a)
     if a.qtl:
         return part_qtl(a)
+    if a.trans:
+        return part_trans(a)
     if a.perm:
         return part_perm(a)
     if a.group:
