@@ -79,9 +79,8 @@ namespace {
 
 // One device run over a matrix, as the stages rgx_cohort_cluster and rgx_cohort_refine are made of.  The caller holds the cohort's lock and has checked
 // the limits; every stage enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
-struct ClusterRun {
-    rgx_cohort *co; const rgx_cohort_matrix *m; const char *name; char *err; size_t errlen;
-    double t0, t_last; bool trace = false; hipStream_t st = nullptr;
+struct ClusterRun : CohortRun {
+    const rgx_cohort_matrix *m;
     uint32_t n = 0, nnz = 0, max_start = 0, max_end = 0, max_tid = 0, n_ineligible = 0, n_rounds = 0;
     CohortImage in{};
     // the row workspace: cluster's arrays, and refine's two further permutation buffers, alive flags and compaction scratch
@@ -94,13 +93,7 @@ struct ClusterRun {
     const uint32_t *order[2] = {nullptr, nullptr}; uint32_t *order_spare[2] = {nullptr, nullptr};
 
     ClusterRun(rgx_cohort *co_, const rgx_cohort_matrix *m_, const char *name_, char *err_, size_t errlen_)
-        : co(co_), m(m_), name(name_), err(err_), errlen(errlen_), t0(now_ms()), t_last(t0) {}
-    void mark(const char *what) {
-        if (!trace) return;
-        (void)hipStreamSynchronize(st);
-        const double t = now_ms();
-        fprintf(stderr, "[rgx trace] %s: %-28s +%8.3f ms\n", name, what, t - t_last); t_last = t;
-    }
+        : CohortRun(co_, name_, err_, errlen_), m(m_) {}
     uint32_t site_bits(int side) const { return std::max<uint32_t>(1, bitlen(side ? max_end : max_start)); }
     uint32_t tid_bits() const { return std::max<uint32_t>(1, bitlen(max_tid)); }
 
@@ -110,22 +103,19 @@ struct ClusterRun {
         co->cluster_path = in_hbm ? 1 : 0;
         n = (uint32_t)m->n; nnz = (uint32_t)m->row_begin[m->n];
         if (!n) return RGX_OK;
-        HIP_ENTER(co->device);
-        st = co->stream;
-        trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+        if (int rc = enter()) return rc;
         // the pass counts come from the data
         for (uint32_t i = 0; i < n; ++i) {
             max_start = std::max(max_start, m->start[i]); max_end = std::max(max_end, m->end[i]); max_tid = std::max(max_tid, m->tid[i]);
             if (max_intron && m->end[i] - m->start[i] > max_intron) ++n_ineligible;
         }
-        const int rc_image = cohort_matrix_image(co, m, st, &in, err, errlen);
-        if (rc_image != RGX_OK) return rc_image;
+        if (int rc = cohort_matrix_image(co, m, st, &in, err, errlen)) return rc;
         mark("matrix in HBM");
 
         const size_t Nn = (size_t)n + 64;
         const size_t tmp_words = radix_tmp_words(n) + scan_tmp_words(n) + 64;
-        if (co->cl_rows.ensure((Nn * (8 + 13 + (refine ? 4 : 0)) + 8 + 64 + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err,
-            errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory to cluster %u rows\n", n); }
+        if (int rc = grow(co->cl_rows, (Nn * (8 + 13 + (refine ? 4 : 0)) + 8 + 64 + tmp_words) * 4 + 256,
+                          "regtools_amd: no device memory to cluster %u rows\n", n)) return rc;
         Carve w(co->cl_rows);
         tot = (unsigned long long *)w.u64(Nn); cl_total = (unsigned long long *)w.u64(Nn); o_cl_begin = (unsigned long long *)w.u64(Nn + 1);
         o_cs_begin = (unsigned long long *)w.u64(Nn + 1);
@@ -242,8 +232,7 @@ struct ClusterRun {
         if (M) {
             const size_t Mn = (size_t)M + 64;
             const size_t etmp_words = radix_tmp_words(M) + scan_tmp_words(M) + 64;
-            if (co->cl_entries.ensure((Mn * (2 + 7) + etmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
-                "regtools_amd: no device memory for the clusters' %u counts\n", M); }
+            if (int rc = grow(co->cl_entries, (Mn * (2 + 7) + etmp_words) * 4 + 256, "regtools_amd: no device memory for the clusters' %u counts\n", M)) return rc;
             Carve q(co->cl_entries);
             unsigned long long *sums = (unsigned long long *)q.u64(Mn);
             uint32_t *e_cluster = q.u32(Mn), *e_sample = q.u32(Mn), *e_count = q.u32(Mn), *eperm0 = q.u32(Mn), *eperm1 = q.u32(Mn), *ekey0 = q.u32(Mn),

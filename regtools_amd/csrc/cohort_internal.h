@@ -1,6 +1,7 @@
 // cohort_internal.h -- what the cohort's translation units (cohort*.cpp) share: the cohort itself with its contig table, the layout of a matrix's
-// block and the serial kept beside a matrix, CopyBack (the one way results come back from the device) and the ids the text formats print.  A result's
-// block: result_block.h; the two-pass text writer: text_out.h; what the sQTL calls share beyond this: qtl_run.h.
+// block and the serial kept beside a matrix, CopyBack (the one way results come back from the device), CohortRun (the base of every device run) with
+// Events, and the ids the text formats print.  A result's block: result_block.h; the two-pass text writer: text_out.h; what the sQTL calls share
+// beyond this: qtl_run.h.
 #pragma once
 #include "api_internal.h"
 #include "result_block.h"
@@ -114,13 +115,47 @@ struct rgx_cohort {
     DevBuf ph_in, ph_rows, ph_entries;
     // rgx_cohort_pheno_pcs (cohort_pcs.cpp): rank2 and the quantile table, the chunk partials, the Gram matrix with the column sums
     DevBuf pc_in, pc_part, pc_out;
-    // rgx_cohort_qtl_nominal (cohort_qtl.cpp): the uploaded inputs, the row-major residuals with the per-row and per-variant arrays, the
-    // sample-major panels, the pairs
-    DevBuf qt_in, qt_rows, qt_t, qt_out;
-    // rgx_cohort_qtl_permute (cohort_qtl_perm.cpp; the four above are shared with it): the sample-major permutations, perm_r with the best pairs
+    // the sQTL calls' shared stages (QtlPrep, qtl_prep.cpp): the uploaded inputs, the row-major residuals with the per-row and per-variant arrays
+    // (and the words the run asks for), the sample-major panels
+    DevBuf qt_in, qt_rows, qt_t;
+    // rgx_cohort_qtl_nominal (cohort_qtl.cpp): the pairs; rgx_cohort_qtl_trans (cohort_qtl_trans.cpp): the hits
+    DevBuf qt_out;
+    // rgx_cohort_qtl_permute and _grouped (cohort_qtl_perm.cpp): the sample-major permutations with the member lists, perm_r with the best pairs
     DevBuf qp_in, qp_out;
-    // rgx_cohort_qtl_trans (cohort_qtl_trans.cpp; qt_in, qt_rows and qt_t are shared with it, qt_out holds its hits): the per-tile words
+    // rgx_cohort_qtl_trans (cohort_qtl_trans.cpp): the per-tile words
     DevBuf qx_tiles;
+};
+
+// What every device run of a cohort call (ClusterRun, PhenoRun, PcsRun, the sQTL runs behind QtlPrep: qtl_run.h) is made of.  The caller holds the
+// cohort's lock; `err` and `errlen` are named as HIP_TRY and CARVE_TRY want them.
+struct CohortRun {
+    rgx_cohort *co; char *err; size_t errlen; const char *name;
+    double t0, t_last; bool trace = false; hipStream_t st = nullptr;
+    CohortRun(rgx_cohort *co_, const char *name_, char *err_, size_t errlen_)
+        : co(co_), err(err_), errlen(errlen_), name(name_), t0(now_ms()), t_last(t0) {}
+    // with REGTOOLS_AMD_TRACE set: waits for the stream and prints what the stage took
+    void mark(const char *what) {
+        if (!trace) return;
+        (void)hipStreamSynchronize(st);
+        const double t = now_ms();
+        fprintf(stderr, "[rgx trace] %s: %-28s +%8.3f ms\n", name, what, t - t_last); t_last = t;
+    }
+    // the cohort's device and stream, in front of the run's first device call
+    int enter() { HIP_ENTER(co->device); st = co->stream; trace = getenv("REGTOOLS_AMD_TRACE") != nullptr; return RGX_OK; }
+    // b holds `bytes` or the call fails with this message
+    int grow(DevBuf &b, size_t bytes, const char *fmt, ...) {
+        if (b.ensure(bytes) == hipSuccess) return RGX_OK;
+        (void)hipGetLastError();
+        if (err && errlen) { va_list ap; va_start(ap, fmt); vsnprintf(err, errlen, fmt, ap); va_end(ap); }
+        return RGX_ERR_DEVICE;
+    }
+};
+// a run's events: all created in front of their first record, all destroyed with the run
+template <size_t N> struct Events {
+    hipEvent_t e[N] = {};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipError_t create() { hipError_t rc = hipSuccess; for (hipEvent_t &x : e) if (rc == hipSuccess) rc = hipEventCreate(&x); return rc; }
+    hipEvent_t operator[](size_t i) const { return e[i]; }
 };
 
 // cohort_cluster.cpp: where the kernels read matrix m of n > 0 rows -- its image in HBM when m is the matrix of co's last finish, else the

@@ -125,36 +125,27 @@ int pcs_host_part(rgx_pheno_pcs *p, char *err, size_t errlen) {
 
 // One device run, as the stages rgx_cohort_pheno_pcs is made of.  The caller holds the cohort's lock and has checked the arguments; every stage
 // enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
-struct PcsRun {
-    rgx_cohort *co; const rgx_pheno_table *ph; uint32_t n_pcs; char *err; size_t errlen;
-    double t0, t_last, t_gram = 0; bool trace = false; hipStream_t st = nullptr;
+struct PcsRun : CohortRun {
+    const rgx_pheno_table *ph; uint32_t n_pcs; double t_gram = 0;
     uint64_t K; uint32_t S, n_tiles, n_chunks;
     std::vector<double> T;
     const uint32_t *rank2 = nullptr; const double *d_T = nullptr;
     double *part = nullptr, *col_part = nullptr, *gram = nullptr, *col_sum = nullptr; uint32_t *bad = nullptr;
 
     PcsRun(rgx_cohort *co_, const rgx_pheno_table *ph_, uint32_t n_pcs_, char *err_, size_t errlen_)
-        : co(co_), ph(ph_), n_pcs(n_pcs_), err(err_), errlen(errlen_), t0(now_ms()), t_last(t0), K(ph_->n_rows), S(ph_->n_samples),
+        : CohortRun(co_, "pheno pcs", err_, errlen_), ph(ph_), n_pcs(n_pcs_), K(ph_->n_rows), S(ph_->n_samples),
           n_tiles((ph_->n_samples + kPcaTile - 1) / kPcaTile), n_chunks(pca_n_chunks(ph_->n_rows)) {}
-    void mark(const char *what) {
-        if (!trace) return;
-        (void)hipStreamSynchronize(st);
-        const double t = now_ms();
-        fprintf(stderr, "[rgx trace] pheno pcs: %-28s +%8.3f ms\n", what, t - t_last); t_last = t;
-    }
 
     // 1. the quantile table (host), then rank2 and the table in HBM and the workspaces
     int open() {
-        HIP_ENTER(co->device);
-        st = co->stream;
-        trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+        if (int rc = enter()) return rc;
         try { quantile_table(K, T); }
         catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the %llu quantiles\n", (unsigned long long)(2 * K - 1)); }
         mark("quantile table");
         t_gram = now_ms();
         const size_t n_entries = (size_t)K * S, n_T = (size_t)(2 * K - 1);
-        if (co->pc_in.ensure(n_T * 8 + n_entries * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
-            "regtools_amd: no device memory for a table of %llu rows and %u samples\n", (unsigned long long)K, S); }
+        if (int rc = grow(co->pc_in, n_T * 8 + n_entries * 4 + 256, "regtools_amd: no device memory for a table of %llu rows and %u samples\n",
+                  (unsigned long long)K, S)) return rc;
         Carve u(co->pc_in);
         double *t_up = u.take<double>(n_T); uint32_t *r_up = u.u32(n_entries);
         CARVE_TRY(u, "principal component input");
@@ -162,13 +153,12 @@ struct PcsRun {
         HIP_TRY(hipMemcpyAsync(t_up, T.data(), n_T * 8, hipMemcpyHostToDevice, st));
         rank2 = r_up; d_T = t_up;
         const size_t n_pairs = (size_t)n_tiles * (n_tiles + 1) / 2, tile = (size_t)kPcaTile * kPcaTile, S_pad = (size_t)n_tiles * kPcaTile;
-        if (co->pc_part.ensure((n_pairs * n_chunks * tile + (size_t)n_chunks * S_pad) * 8 + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for the %u chunk partials of %u samples\n", n_chunks, S); }
+        if (int rc = grow(co->pc_part, (n_pairs * n_chunks * tile + (size_t)n_chunks * S_pad) * 8 + 256,
+                  "regtools_amd: no device memory for the %u chunk partials of %u samples\n", n_chunks, S)) return rc;
         Carve w(co->pc_part);
         part = w.take<double>(n_pairs * n_chunks * tile); col_part = w.take<double>((size_t)n_chunks * S_pad);
         CARVE_TRY(w, "principal component partials");
-        if (co->pc_out.ensure(((size_t)S * S + S + 1) * 8 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
-            "regtools_amd: no device memory for the Gram matrix of %u samples\n", S); }
+        if (int rc = grow(co->pc_out, ((size_t)S * S + S + 1) * 8 + 256, "regtools_amd: no device memory for the Gram matrix of %u samples\n", S)) return rc;
         Carve o(co->pc_out);                                 // (in the order of the result's block: one copy takes the three)
         gram = o.take<double>((size_t)S * S); col_sum = o.take<double>(S); bad = (uint32_t *)o.take<double>(1);
         CARVE_TRY(o, "principal component output");

@@ -49,9 +49,8 @@ struct PhenoScalars { uint32_t n_kept, n_drop_na, n_runs; };
 
 // One device run, as the stages rgx_cohort_phenotypes is made of.  The caller holds the cohort's lock and has checked the arguments; every stage
 // enqueues on the cohort's stream and returns RGX_OK or the failed call's code.
-struct PhenoRun {
-    rgx_cohort *co; const rgx_cohort_matrix *m; const rgx_cohort_clusters *cl; rgx_pheno_params prm; uint64_t n_clustered; char *err; size_t errlen;
-    double t0, t_last; bool trace = false; hipStream_t st = nullptr;
+struct PhenoRun : CohortRun {
+    const rgx_cohort_matrix *m; const rgx_cohort_clusters *cl; rgx_pheno_params prm; uint64_t n_clustered;
     uint32_t n = 0, S = 0, K = 0, n_drop_na = 0;
     PhenoIn in{};
     PhenoScalars *d_sc = nullptr;
@@ -61,28 +60,19 @@ struct PhenoRun {
 
     PhenoRun(rgx_cohort *co_, const rgx_cohort_matrix *m_, const rgx_cohort_clusters *cl_, const rgx_pheno_params &p_, uint64_t n_clustered_, char *err_,
              size_t errlen_)
-        : co(co_), m(m_), cl(cl_), prm(p_), n_clustered(n_clustered_), err(err_), errlen(errlen_), t0(now_ms()), t_last(t0) {}
-    void mark(const char *what) {
-        if (!trace) return;
-        (void)hipStreamSynchronize(st);
-        const double t = now_ms();
-        fprintf(stderr, "[rgx trace] phenotypes: %-28s +%8.3f ms\n", what, t - t_last); t_last = t;
-    }
+        : CohortRun(co_, "phenotypes", err_, errlen_), m(m_), cl(cl_), prm(p_), n_clustered(n_clustered_) {}
 
     // 1. the matrix where the kernels read it (its image in HBM, or uploaded), the cluster result beside it, the row workspace
     int open() {
         co->cluster_path = matrix_serial(m) == co->image_serial ? 1 : 0;
         n = (uint32_t)m->n; S = m->n_samples;
         if (!n_clustered || !S) return RGX_OK;
-        HIP_ENTER(co->device);
-        st = co->stream;
-        trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+        if (int rc = enter()) return rc;
         CohortImage img{};
-        const int rc = cohort_matrix_image(co, m, st, &img, err, errlen);
-        if (rc != RGX_OK) return rc;
+        if (int rc = cohort_matrix_image(co, m, st, &img, err, errlen)) return rc;
         const size_t C = (size_t)cl->n_clusters, n_cs = (size_t)cl->cs_begin[C];
-        if (co->ph_in.ensure((C + 1 + n_cs) * 8 + ((size_t)n + n_cs) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen,
-            RGX_ERR_DEVICE, "regtools_amd: no device memory to upload the clusters (%zu clusters, %zu denominators)\n", C, n_cs); }
+        if (int rc = grow(co->ph_in, (C + 1 + n_cs) * 8 + ((size_t)n + n_cs) * 4 + 256,
+                  "regtools_amd: no device memory to upload the clusters (%zu clusters, %zu denominators)\n", C, n_cs)) return rc;
         Carve u(co->ph_in);
         unsigned long long *cs_begin = (unsigned long long *)u.u64(C + 1), *cs_total = (unsigned long long *)u.u64(n_cs);
         uint32_t *cluster = u.u32(n), *cs_sample = u.u32(n_cs);
@@ -98,8 +88,7 @@ struct PhenoRun {
         mark("matrix + clusters in HBM");
 
         const size_t Nn = (size_t)n + 64, tmp_words = scan_tmp_words(n) + 64;
-        if (co->ph_rows.ensure((Nn * (4 * 2 + 6) + 64 + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen,
-            RGX_ERR_DEVICE, "regtools_amd: no device memory for the statistics of %u rows\n", n); }
+        if (int rc = grow(co->ph_rows, (Nn * (4 * 2 + 6) + 64 + tmp_words) * 4 + 256, "regtools_amd: no device memory for the statistics of %u rows\n", n)) return rc;
         Carve w(co->ph_rows);
         mean = w.take<double>(Nn); sd = w.take<double>(Nn); o_mean = w.take<double>(Nn); o_sd = w.take<double>(Nn);
         d_sc = (PhenoScalars *)w.u32(64);
@@ -126,8 +115,7 @@ struct PhenoRun {
     int ranks() {
         const uint32_t N = K * S;                                        // (at most n_clustered * S: checked)
         const size_t Nn = (size_t)N + 64, tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;
-        if (co->ph_entries.ensure((Nn * 7 + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
-            "regtools_amd: no device memory to rank %u rows of %u samples\n", K, S); }
+        if (int rc = grow(co->ph_entries, (Nn * 7 + tmp_words) * 4 + 256, "regtools_amd: no device memory to rank %u rows of %u samples\n", K, S)) return rc;
         Carve q(co->ph_entries);
         uint32_t *z_lo = q.u32(Nn), *z_hi = q.u32(Nn), *e_sample = q.u32(Nn), *perm0 = q.u32(Nn), *perm1 = q.u32(Nn), *key0 = q.u32(Nn), *key1 = q.u32(Nn),
                  *etmp = q.u32(tmp_words);

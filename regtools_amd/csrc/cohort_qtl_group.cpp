@@ -1,9 +1,9 @@
 // cohort_qtl_group.cpp -- the grouped permutation pass of the cohort's cis-sQTL scan: rgx_cohort_qtl_permute_grouped (device), its host twin
 // rgx_cohort_qtl_permute_grouped_host, rgx_cohort_pheno_groups and the text (contract in include/regtools_amd.h; FastQTL's --grp and tensorQTL's
 // group_s, which the reference does not contain).  What is about groups is here: their checks, the member lists, the result and the text.  The
-// device run (PermRun over qtl_perm_kernels.hip, behind QtlRun's shared stages: qtl_run.h), the twin's products of one series, the permutation
+// device run (PermRun over qtl_perm_kernels.hip, behind QtlPrep's shared stages: qtl_run.h), the twin's products of one series, the permutation
 // checks and the finish over series are cohort_qtl_perm.cpp's, where a series without lists is a table row; arithmetic: qtl_core.h.
-//   QtlRun: inputs in HBM -> residuals -> the usable variants compacted -> Gt sample-major -> per row its range
+//   QtlPrep: inputs in HBM -> residuals -> the usable variants compacted -> Gt sample-major -> per row its range
 //   -> the groups' member lists (host, counting sort) and the permutations sample-major in HBM -> one workgroup per (group, 64 permutations): perm_r
 //   -> a thread per group: the best pair of permutation 0 -> ONE wait, the copies back -> on the host: n_ge, p_perm, the beta approximation
 #include "qtl_run.h"
@@ -21,7 +21,7 @@ rgx_qtl_group_result *group_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n
         take(r.beta_status, G);
     });
     if (!q) return nullptr;
-    q->n_rows = K; q->n_samples = S; q->n_variants = V; q->n_cov = n_cov; q->dof = S - n_cov - 2; q->n_perm = B; q->n_groups = G;
+    qtl_result_head(q, K, S, V, n_cov); q->n_perm = B; q->n_groups = G;
     memcpy(q->grp_begin, mem.begin.data(), ((size_t)G + 1) * 4);
     if (!mem.row.empty()) memcpy(q->grp_row, mem.row.data(), mem.row.size() * 4);
     return q;
@@ -81,8 +81,7 @@ extern "C" int rgx_cohort_qtl_permute_grouped(rgx_cohort *co, const rgx_pheno_ta
     if (!co || !ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_permute_grouped needs a cohort and a phenotype table\n");
     *out = nullptr;
     std::lock_guard<std::mutex> lock(co->mu);
-    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
-    int rc = check_qtl(a, err, errlen);
+    QtlArgs a; int rc = qtl_args(a, ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window, err, errlen);
     if (rc == RGX_OK) rc = check_groups(ph->n_rows, n_groups, group, err, errlen);
     if (rc == RGX_OK) rc = check_perm(n_groups, "groups", ph->n_samples, n_perm, perm, err, errlen);
     Members mem;
@@ -93,11 +92,7 @@ extern "C" int rgx_cohort_qtl_permute_grouped(rgx_cohort *co, const rgx_pheno_ta
     rgx_qtl_group_result *q = nullptr;
     if (rc == RGX_OK && !(q = group_alloc(ph->n_rows, ph->n_samples, n_variants, n_cov, n_perm, n_groups, mem, /*pinned=*/true))) rc = p.no_result();
     if (rc == RGX_OK) rc = p.finish(q);
-    if (rc != RGX_OK) {
-        if (p.run.st) (void)hipStreamSynchronize(p.run.st);   // (the copies read the caller's arrays and this run's T, Q, permT and members, and write q)
-        rgx_cohort_qtl_group_free(q);
-        return rc;
-    }
+    if (p.done(rc) != RGX_OK) { rgx_cohort_qtl_group_free(q); return rc; }
     *out = q;
     return RGX_OK;
 }
@@ -109,8 +104,7 @@ extern "C" int rgx_cohort_qtl_permute_grouped_host(const rgx_pheno_table *ph, co
     if (!ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_permute_grouped_host needs a phenotype table\n");
     *out = nullptr;
     const double t0 = now_ms();
-    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window};
-    int rc = check_qtl(a, err, errlen);
+    QtlArgs a; int rc = qtl_args(a, ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, window, err, errlen);
     if (rc == RGX_OK) rc = check_groups(ph->n_rows, n_groups, group, err, errlen);
     if (rc == RGX_OK) rc = check_perm(n_groups, "groups", ph->n_samples, n_perm, perm, err, errlen);
     Members mem;
@@ -122,9 +116,8 @@ extern "C" int rgx_cohort_qtl_permute_grouped_host(const rgx_pheno_table *ph, co
     const uint64_t K = ph->n_rows; const uint32_t S = ph->n_samples, V = n_variants, B = n_perm, G = n_groups;
     rgx_qtl_group_result *q = group_alloc(K, S, V, n_cov, B, G, mem, false);
     if (!q) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the result of %u groups and %u permutations\n", G, B);
-    memcpy(q->yy, h.yy.data(), K * 8);
+    qtl_result_fill(q, h);
     memcpy(q->n_cis, h.cnt.data(), K * 4);
-    if (V) { memcpy(q->gg, h.gg.data(), (size_t)V * 8); memcpy(q->variant_verdict, h.verdict.data(), V); }
     try {
         uint64_t P = 0;
         for (uint32_t k : mem.row) P += h.cnt[k];

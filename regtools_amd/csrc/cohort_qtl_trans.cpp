@@ -1,7 +1,8 @@
 // cohort_qtl_trans.cpp -- the trans-sQTL scan of the cohort's phenotype table: rgx_cohort_qtl_trans (device), its host twin
-// rgx_cohort_qtl_trans_host, rgx_qtl_r_threshold and the text (contract in include/regtools_amd.h; tensorQTL's map_trans, which the reference does
-// not contain).  Device side: qtl_trans_kernels.hip behind QtlRun's shared stages (qtl_run.h); arithmetic: qtl_core.h.
-//   QtlRun: inputs in HBM -> residuals Y, G with yy, gg and the verdicts -> the usable variants compacted -> Yt, Gt sample-major
+// rgx_cohort_qtl_trans_host and the text (contract in include/regtools_amd.h; tensorQTL's map_trans, which the reference does not contain).
+// Device side: qtl_trans_kernels.hip behind QtlPrep's shared stages (qtl_run.h, qtl_prep.cpp); arithmetic: qtl_core.h; rgx_qtl_r_threshold:
+// qtl_stats.cpp.
+//   QtlPrep: inputs in HBM -> residuals Y, G with yy, gg and the verdicts -> the usable variants compacted -> Yt, Gt sample-major
 //   -> one workgroup per tile of 64 rows x 64 usable variants, ALL of them: its hits and its pairs that met -> the scans of the hits and of the
 //   tiles with hits, H and n_tested as 64-bit sums -> ONE wait for H, n_tested, the hit tiles and the flags -> one workgroup per tile with hits:
 //   (row, usable variant, r, slope) tile-major -> a stable sort on the row -> the hits in order, hit_begin -> the copies back
@@ -17,8 +18,7 @@ rgx_qtl_trans_result *trans_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n
     rgx_qtl_trans_result *q = result_alloc<rgx_qtl_trans_result>(pinned, [&](rgx_qtl_trans_result &r, BlockTake &take) {
         take(r.yy, K); take(r.gg, V); take(r.r, H); take(r.slope, H); take(r.hit_begin, K + 1); take(r.hit_variant, H); take(r.variant_verdict, V);
     });
-    if (!q) return nullptr;
-    q->n_rows = K; q->n_samples = S; q->n_variants = V; q->n_cov = n_cov; q->dof = S - n_cov - 2; q->n_hits = H;
+    if (q) { qtl_result_head(q, K, S, V, n_cov); q->n_hits = H; }
     return q;
 }
 
@@ -33,67 +33,64 @@ int too_many_hits(uint64_t H, uint64_t limit, char *err, size_t errlen) {
                 (unsigned long long)H, (unsigned long long)limit);
 }
 
-// The device run: QtlRun's shared stages with the trans scan's own behind them.
-struct TransRun {
-    QtlRun run; TransArgs x;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // totals done, emit begins, hits in order
+// The device run: QtlPrep's shared stages with the trans scan's own behind them.
+struct TransRun : QtlPrep {
+    TransArgs x;
+    Events<3> ev_hits;                                         // totals done, emit begins, hits in order
     uint32_t n_vt = 0, n_tiles = 0, n_hit_tiles = 0, band = 4;
     uint64_t H = 0, n_tested = 0;
     QtlTransTiles tiles{};
     unsigned long long *totals = nullptr;
-    uint32_t *tile_hits = nullptr, *tile_tested = nullptr, *tile_flag = nullptr, *tile_off = nullptr, *place = nullptr, *hit_tile = nullptr,
-             *n_hit = nullptr, *tmp = nullptr;
+    uint32_t *tile_hits = nullptr, *tile_tested = nullptr, *tile_flag = nullptr, *tile_off = nullptr, *tile_place = nullptr, *hit_tile = nullptr,
+             *n_hit = nullptr, *tile_tmp = nullptr;
     double *r = nullptr, *slope = nullptr; uint32_t *hit_variant = nullptr, *hit_begin = nullptr;
 
-    TransRun(rgx_cohort *co, const QtlArgs &a, const TransArgs &x_, char *err, size_t errlen) : run(co, a, err, errlen), x(x_) {}
-    ~TransRun() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    TransRun(rgx_cohort *co, const QtlArgs &a, const TransArgs &x_, char *err, size_t errlen)
+        : QtlPrep(co, "qtl trans", a, /*want_Yt=*/true, 0, err, errlen), x(x_) {}
 
     // 4. every tile's hits, the scans and the totals; the call's one wait in front of its results
     int count() {
-        rgx_cohort *co = run.co; char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
-        n_vt = (run.V + kQtlTile - 1) / kQtlTile;
-        if ((uint64_t)run.n_blocks * n_vt > kQtlMaxTiles) return fail(err, errlen, RGX_ERR_ARG,
-            "regtools_amd: %llu tiles of 64 rows and 64 variants; the trans scan takes at most 2^31 - 1\n", (unsigned long long)run.n_blocks * n_vt);
-        n_tiles = run.n_blocks * n_vt;
+        n_vt = (V + kQtlTile - 1) / kQtlTile;
+        if ((uint64_t)n_blocks * n_vt > kQtlMaxTiles) return fail(err, errlen, RGX_ERR_ARG,
+            "regtools_amd: %llu tiles of 64 rows and 64 variants; the trans scan takes at most 2^31 - 1\n", (unsigned long long)n_blocks * n_vt);
+        n_tiles = n_blocks * n_vt;
         if (const char *b = getenv("REGTOOLS_AMD_TRANS_BAND")) band = (uint32_t)std::min(64l, std::max(0l, atol(b)));
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(ev_hits.create());
         const size_t n_tmp = scan_tmp_words(n_tiles);
-        if (co->qx_tiles.ensure(64 + (6 * (size_t)n_tiles + 2 + n_tmp) * 4 + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %u tiles of the trans scan\n", n_tiles); }
+        if (int rc = grow(co->qx_tiles, 64 + (6 * (size_t)n_tiles + 2 + n_tmp) * 4 + 256,
+                          "regtools_amd: no device memory for %u tiles of the trans scan\n", n_tiles)) return rc;
         Carve w(co->qx_tiles);
         totals = (unsigned long long *)w.u64(8);
-        tile_hits = w.u32(n_tiles); tile_tested = w.u32(n_tiles); tile_flag = w.u32(n_tiles); tile_off = w.u32(n_tiles); place = w.u32(n_tiles);
-        hit_tile = w.u32(n_tiles); n_hit = w.u32(2); tmp = w.u32(n_tmp);
+        tile_hits = w.u32(n_tiles); tile_tested = w.u32(n_tiles); tile_flag = w.u32(n_tiles); tile_off = w.u32(n_tiles); tile_place = w.u32(n_tiles);
+        hit_tile = w.u32(n_tiles); n_hit = w.u32(2); tile_tmp = w.u32(n_tmp);
         CARVE_TRY(w, "trans sQTL tile");
         uint64_t r_min_bits = qtl_abs_bits(x.r_min);
-        tiles = QtlTransTiles{run.Yt, run.ldy, run.Gt, run.ldg, run.S, run.K, run.n_blocks, n_vt, run.regions, run.yy, run.u_gg, run.u_key,
-                              run.n_usable(), r_min_bits, x.exclude_cis ? 1u : 0u, x.exclude_window};
+        tiles = QtlTransTiles{Yt, ldy, Gt, ldg, S, K, n_blocks, n_vt, regions, yy, u_gg, u_key,
+                              n_usable(), r_min_bits, x.exclude_cis ? 1u : 0u, x.exclude_window};
         launch_qtl_trans_count(tiles, band, tile_hits, tile_tested, tile_flag, st);
-        run.mark("tile counts");
-        launch_scan_u32(tile_flag, place, n_tiles, n_hit, tmp, st);
-        launch_qtl_trans_hit_tiles(tile_flag, place, n_tiles, hit_tile, st);
-        launch_scan_u32(tile_hits, tile_off, n_tiles, nullptr, tmp, st);
-        launch_qtl_trans_totals(tile_hits, tile_tested, n_tiles, n_hit, run.flag(), run.n_usable(), totals, st);
-        HIP_TRY(hipEventRecord(ev[0], st));
+        mark("tile counts");
+        launch_scan_u32(tile_flag, tile_place, n_tiles, n_hit, tile_tmp, st);
+        launch_qtl_trans_hit_tiles(tile_flag, tile_place, n_tiles, hit_tile, st);
+        launch_scan_u32(tile_hits, tile_off, n_tiles, nullptr, tile_tmp, st);
+        launch_qtl_trans_totals(tile_hits, tile_tested, n_tiles, n_hit, flag(), n_usable(), totals, st);
+        HIP_TRY(hipEventRecord(ev_hits[0], st));
         uint64_t h[5];
         HIP_TRY(hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        run.mark("scans + totals");
-        const int rc = bad_flags((const uint32_t *)(h + 3), run.K, err, errlen);
-        if (rc != RGX_OK) return rc;
+        mark("scans + totals");
+        if (int rc = bad_flags((const uint32_t *)(h + 3), K, err, errlen)) return rc;
         H = h[0]; n_tested = h[1]; n_hit_tiles = (uint32_t)h[2];
         if (H > hit_limit(x)) return too_many_hits(H, hit_limit(x), err, errlen);
         return RGX_OK;
     }
     // 5. the tiles with hits again, then the hits in the contract's order
     int emit() {
-        rgx_cohort *co = run.co; char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
-        const uint32_t K = run.K, n = (uint32_t)H;
+        const uint32_t n = (uint32_t)H;
         uint32_t row_bits = 0;
         while (row_bits < 32 && (K - 1) >> row_bits) ++row_bits;
         const size_t n_rtmp = row_bits ? radix_tmp_words(n) : 0;
-        if (co->qt_out.ensure((size_t)H * (4 * 8 + 6 * 4) + ((size_t)K + 1 + n_rtmp) * 4 + 256) != hipSuccess) { (void)hipGetLastError();
-            return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no device memory for %llu hits\n", (unsigned long long)H); }
+        if (int rc = grow(co->qt_out, (size_t)H * (4 * 8 + 6 * 4) + ((size_t)K + 1 + n_rtmp) * 4 + 256, "regtools_amd: no device memory for %llu hits\n",
+                            (unsigned long long)H)) return rc;
         Carve o(co->qt_out);
         double *hit_r = o.take<double>(H), *hit_slope = o.take<double>(H);
         r = o.take<double>(H); slope = o.take<double>(H);
@@ -101,42 +98,35 @@ struct TransRun {
         hit_variant = o.u32(H); hit_begin = o.u32((size_t)K + 1);
         uint32_t *rtmp = o.u32(n_rtmp);
         CARVE_TRY(o, "trans sQTL hit");
-        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipEventRecord(ev_hits[1], st));
         launch_qtl_trans_emit(tiles, hit_tile, n_hit_tiles, tile_off, hit_row, hit_u, hit_r, hit_slope, st);
-        run.mark("hit tiles");
+        mark("hit tiles");
         // tile-major, and inside a row the tiles come in ascending variant order: a stable sort on the row alone gives the contract's order
         const uint32_t *order = nullptr;
         for (uint32_t shift = 0, pass = 0; shift < row_bits; shift += 8, ++pass) {
             launch_radix_pass(hit_row, shift, std::min(8u, row_bits - shift), order, perm[pass & 1], n, rtmp, st);
             order = perm[pass & 1];
         }
-        launch_qtl_trans_order(order, n, hit_row, hit_u, hit_r, hit_slope, run.u_var, K, row_sorted, hit_variant, r, slope, hit_begin, st);
-        HIP_TRY(hipEventRecord(ev[2], st));
-        run.mark("hits in order");
+        launch_qtl_trans_order(order, n, hit_row, hit_u, hit_r, hit_slope, u_var, K, row_sorted, hit_variant, r, slope, hit_begin, st);
+        HIP_TRY(hipEventRecord(ev_hits[2], st));
+        mark("hits in order");
         return RGX_OK;
     }
     // 6. the copies back, one wait
     int finish(rgx_qtl_trans_result **out) {
-        char *err = run.err; const size_t errlen = run.errlen; hipStream_t st = run.st;
-        const uint32_t K = run.K, V = run.V;
-        rgx_qtl_trans_result *q = trans_alloc(K, run.S, V, run.a.n_cov, H, /*pinned=*/true);
+        rgx_qtl_trans_result *q = trans_alloc(K, S, V, a.n_cov, H, /*pinned=*/true);
         if (!q) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the result of %llu hits\n",
             (unsigned long long)H); }
         CopyBack back{st};
-        back(q->yy, run.yy, (size_t)K * 8); back(q->gg, run.gg, (size_t)V * 8); back(q->variant_verdict, run.verdict, V);
+        copy_back(back, q);
         back(q->hit_begin, hit_begin, ((size_t)K + 1) * 4); back(q->hit_variant, hit_variant, (size_t)H * 4); back(q->r, r, (size_t)H * 8);
         back(q->slope, slope, (size_t)H * 8);
-        hipError_t e_ = back.wait();
         float ms_res = 0, ms_count = 0, ms_emit = 0;
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_res, run.ev[0], run.ev[1]);
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_count, run.ev[1], ev[0]);
-        if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms_emit, ev[1], ev[2]);
-        if (e_ != hipSuccess) { rgx_cohort_qtl_trans_free(q); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the trans sQTL scan\n",
-            hipGetErrorString(e_)); }
-        run.mark("copies");
+        const int rc = wait(back, {{ev[0], ev[1], &ms_res}, {ev[1], ev_hits[0], &ms_count}, {ev_hits[1], ev_hits[2], &ms_emit}}, "trans sQTL scan");
+        if (rc != RGX_OK) { rgx_cohort_qtl_trans_free(q); return rc; }
         count_verdicts(q);
         q->n_tested = n_tested; q->n_tiles = n_tiles; q->n_hit_tiles = n_hit_tiles;
-        q->ms_residual = ms_res; q->ms_count = ms_count; q->ms_emit = ms_emit; q->ms_trans = now_ms() - run.t0;
+        q->ms_residual = ms_res; q->ms_count = ms_count; q->ms_emit = ms_emit; q->ms_trans = now_ms() - t0;
         *out = q;
         return RGX_OK;
     }
@@ -153,20 +143,16 @@ extern "C" int rgx_cohort_qtl_trans(rgx_cohort *co, const rgx_pheno_table *ph, c
     if (!co || !ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_trans needs a cohort and a phenotype table\n");
     *out = nullptr;
     std::lock_guard<std::mutex> lock(co->mu);
-    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, exclude_window};
-    const TransArgs x{r_min, exclude_cis, exclude_window, max_hits};
-    int rc = check_qtl(a, err, errlen);
+    QtlArgs a; const TransArgs x{r_min, exclude_cis, exclude_window, max_hits};
+    int rc = qtl_args(a, ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, exclude_window, err, errlen);
     if (rc == RGX_OK) rc = check_trans(x, err, errlen);
     if (rc != RGX_OK) return rc;
     TransRun t(co, a, x, err, errlen);
-    rc = t.run.open();
-    if (rc == RGX_OK) rc = t.run.residuals();
-    if (rc == RGX_OK) rc = t.run.compact();
+    rc = t.prepare();
     if (rc == RGX_OK) rc = t.count();
     if (rc == RGX_OK) rc = t.emit();
     if (rc == RGX_OK) rc = t.finish(out);
-    if (rc != RGX_OK && t.run.st) (void)hipStreamSynchronize(t.run.st);   // (the uploads read the caller's arrays and this run's T and Q)
-    return rc;
+    return t.done(rc);
 }
 
 extern "C" int rgx_cohort_qtl_trans_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
@@ -176,9 +162,8 @@ extern "C" int rgx_cohort_qtl_trans_host(const rgx_pheno_table *ph, const rgx_qt
     if (!ph || !out) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: rgx_cohort_qtl_trans_host needs a phenotype table\n");
     *out = nullptr;
     const double t0 = now_ms();
-    const QtlArgs a{ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, exclude_window};
-    const TransArgs x{r_min, exclude_cis, exclude_window, max_hits};
-    int rc = check_qtl(a, err, errlen);
+    QtlArgs a; const TransArgs x{r_min, exclude_cis, exclude_window, max_hits};
+    int rc = qtl_args(a, ph, regions, n_variants, var_tid, var_pos, dosage, n_cov, covariates, exclude_window, err, errlen);
     if (rc == RGX_OK) rc = check_trans(x, err, errlen);
     if (rc != RGX_OK) return rc;
     QtlHost h;
@@ -217,8 +202,7 @@ extern "C" int rgx_cohort_qtl_trans_host(const rgx_pheno_table *ph, const rgx_qt
     if (H > hit_limit(x)) return too_many_hits(H, hit_limit(x), err, errlen);
     rgx_qtl_trans_result *q = trans_alloc(K, S, V, n_cov, H, false);
     if (!q) return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for the result of %llu hits\n", (unsigned long long)H);
-    memcpy(q->yy, h.yy.data(), K * 8);
-    if (V) { memcpy(q->gg, h.gg.data(), (size_t)V * 8); memcpy(q->variant_verdict, h.verdict.data(), V); }
+    qtl_result_fill(q, h);
     uint32_t p = 0;
     for (uint64_t k = 0; k < K; ++k) {
         q->hit_begin[k] = p;
@@ -231,20 +215,6 @@ extern "C" int rgx_cohort_qtl_trans_host(const rgx_pheno_table *ph, const rgx_qt
     q->ms_residual = h.t_pairs - h.t_res; q->ms_count = t1 - h.t_pairs; q->ms_trans = t1 - t0;
     *out = q;
     return RGX_OK;
-}
-
-extern "C" double rgx_qtl_r_threshold(double p, uint32_t dof) {
-    if (!(p >= 0.0) || !dof) return NAN;
-    if (p >= 1.0) return 0.0;
-    auto at = [](uint64_t bits) { double r; memcpy(&r, &bits, 8); return r; };
-    const double one = 1.0;
-    uint64_t lo = 0, hi;                                                // +0.0 fails (its p is 1), 1.0 passes (its p is 0)
-    memcpy(&hi, &one, 8);
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (rgx_qtl_pvalue(rgx_qtl_tstat(at(mid), dof), dof) <= p) hi = mid; else lo = mid;
-    }
-    return at(hi);
 }
 
 // ---- text ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -168,12 +168,7 @@ __global__ __launch_bounds__(256) void k_qtl_totals(const uint32_t *__restrict__
     unsigned long long a = 0, b = 0;
     for (uint64_t i = threadIdx.x; i < K; i += 256) a += count[i];
     for (uint64_t i = threadIdx.x; i < n_blocks; i += 256) b += tile_count[i];
-    part[0][threadIdx.x] = a; part[1][threadIdx.x] = b;
-    __syncthreads();
-    for (uint32_t off = 128; off; off >>= 1) {
-        if (threadIdx.x < off) { part[0][threadIdx.x] += part[0][threadIdx.x + off]; part[1][threadIdx.x] += part[1][threadIdx.x + off]; }
-        __syncthreads();
-    }
+    qtl_sum2_256(part, a, b);
     if (!threadIdx.x) { totals[0] = part[0][0]; totals[1] = part[1][0]; }
 }
 
@@ -195,14 +190,14 @@ __global__ __launch_bounds__(256) void k_qtl_pairs(const double *__restrict__ Yt
 
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t k = k0 + (i < 2 ? 0 : 32) + 2 * ty + (i & 1);
+        const uint32_t k = k0 + qtl_tile_at(i, ty);
         if (k >= K) continue;
         const uint32_t first = lo[k], n = count[k];
         if (!n) continue;
         const uint32_t base = pair_begin[k]; const double y2 = yy[k];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t u = v0 + (j < 2 ? 0 : 32) + 2 * tx + (j & 1);
+            const uint32_t u = v0 + qtl_tile_at(j, tx);
             if (u < first || u - first >= n) continue;
             const uint32_t p = base + (u - first); const double g2 = u_gg[u];
             r[p] = qtl_r(acc[i][j], y2, g2); slope[p] = qtl_slope(acc[i][j], g2); pair_variant[p] = u_var[u];

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_qtl_perm(const double *__restrict__ Y, 
             // equals stays
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j) {
-                const uint32_t u = v0 + (j < 2 ? 0 : 32) + 2 * tx + (j & 1);
+                const uint32_t u = v0 + qtl_tile_at(j, tx);
                 if (u - first >= n) continue;
                 const double g2 = u_gg[u];
 #pragma unroll
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_qtl_perm(const double *__restrict__ Y, 
             const unsigned long long ob = __shfl_xor(top[i], off, 64), oa = __shfl_xor(top_at[i], off, 64);
             if (oa != kNoPlace && (top_at[i] == kNoPlace || ob > top[i] || (ob == top[i] && oa < top_at[i]))) { top[i] = ob; top_at[i] = oa; }
         }
-        const uint32_t b = b0 + (i < 2 ? 0 : 32) + 2 * ty + (i & 1);
+        const uint32_t b = b0 + qtl_tile_at(i, ty);
         if (tx || b >= n_perm1) continue;
         double v; const unsigned long long bits = top[i];
         memcpy(&v, &bits, 8);

@@ -1,4 +1,4 @@
-// qtl_tile.h -- the one slab loop of the sQTL product kernels (device only): k_qtl_pairs (qtl_kernels.hip), k_qtl_perm (qtl_perm_kernels.hip)
+// qtl_tile.h -- the one slab loop of the sQTL product kernels, with a thread's place in a tile and the totals' block sum (device only): k_qtl_pairs (qtl_kernels.hip), k_qtl_perm (qtl_perm_kernels.hip)
 // and k_qtl_trans_count / k_qtl_trans_emit (qtl_trans_kernels.hip) run it; they differ in where an entry of the A panel comes from, which a
 // small source type says.
 #pragma once
@@ -25,8 +25,21 @@ struct QtlTilePerms {                        // a column of the sample-major per
     __device__ __forceinline__ double stage(Raw i) const { return y[i]; }
 };
 
-// acc[i][j] = the contract's chain over s = 0 .. S - 1 from +0.0 of A[s][a(i)] * B[s][b(j)], a(i) = (i < 2 ? 0 : 32) + 2 * ty + (i & 1) with
-// ty = tid / 16 and b(j) the same of tx = tid % 16, for one tile of 64 x 64: 4 x 4 chains per thread in registers, one thread per chain.  The B
+// where a thread's chains lie in the tile: the i-th of its four rows (t = ty = tid / 16) or columns (t = tx = tid % 16)
+__device__ __forceinline__ uint32_t qtl_tile_at(uint32_t i, uint32_t t) { return (i < 2 ? 0 : 32) + 2 * t + (i & 1); }
+
+// Two 64-bit sums over the 256 threads of one workgroup: a and b are this thread's shares; behind the return part[0][0] and part[1][0] hold the sums.
+__device__ __forceinline__ void qtl_sum2_256(unsigned long long (&part)[2][256], unsigned long long a, unsigned long long b) {
+    part[0][threadIdx.x] = a; part[1][threadIdx.x] = b;
+    __syncthreads();
+    for (uint32_t off = 128; off; off >>= 1) {
+        if (threadIdx.x < off) { part[0][threadIdx.x] += part[0][threadIdx.x + off]; part[1][threadIdx.x] += part[1][threadIdx.x + off]; }
+        __syncthreads();
+    }
+}
+
+// acc[i][j] = the contract's chain over s = 0 .. S - 1 from +0.0 of A[s][a(i)] * B[s][b(j)], a(i) = qtl_tile_at(i, ty) with
+// ty = tid / 16 and b(j) = qtl_tile_at(j, tx) with tx = tid % 16, for one tile of 64 x 64: 4 x 4 chains per thread in registers, one thread per chain.  The B
 // panel is gb[s * ldg] (gb: this thread's column of Gt).  The samples come in slabs of 16 through two LDS panels (16,384 B static), the next
 // slab's loads in flight under the current slab's FMAs.  Called by the whole workgroup of 256; it ends behind a barrier, so nothing of the
 // panels -- or of what a_src.stage() reads -- is read once it has returned.

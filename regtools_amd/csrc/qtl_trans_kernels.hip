@@ -32,9 +32,6 @@ __device__ __forceinline__ uint32_t trans_tile_of(uint32_t b, uint32_t n, uint32
     return (g * band + in % rows_here) * n_vt + in / rows_here;
 }
 
-// acc's row i and column j inside the tile (qtl_tile.h)
-__device__ __forceinline__ uint32_t trans_at(uint32_t i, uint32_t t) { return (i < 2 ? 0 : 32) + 2 * t + (i & 1); }
-
 // This thread's 4 x 4 values of tile (k0, v0): on_hit(i, j, k, u) for every hit; returns its pairs that met.
 template <class F>
 __device__ __forceinline__ uint32_t trans_visit(const QtlTransTiles &t, uint32_t k0, uint32_t v0, const double (&acc)[4][4], F on_hit) {
@@ -42,20 +39,20 @@ __device__ __forceinline__ uint32_t trans_visit(const QtlTransTiles &t, uint32_t
     uint64_t key[4]; double g2[4];
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t u = v0 + trans_at(j, tx);
+        const uint32_t u = v0 + qtl_tile_at(j, tx);
         key[j] = u < U ? t.u_key[u] : 0; g2[j] = u < U ? t.u_gg[u] : 0.0;
     }
     uint32_t met = 0;
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t k = k0 + trans_at(i, ty);
+        const uint32_t k = k0 + qtl_tile_at(i, ty);
         if (k >= t.K) continue;
         const double y2 = t.yy[k];
         if (!qtl_enough(y2, t.S)) continue;
         const uint32_t tid = t.regions[3 * (size_t)k], start = t.regions[3 * (size_t)k + 1], end = t.regions[3 * (size_t)k + 2];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t u = v0 + trans_at(j, tx);
+            const uint32_t u = v0 + qtl_tile_at(j, tx);
             if (u >= U || (t.exclude_cis && qtl_key_is_cis(key[j], tid, start, end, t.exclude_window))) continue;
             ++met;
             if (qtl_abs_bits(qtl_r(acc[i][j], y2, g2[j])) >= t.r_min_bits) on_hit(i, j, k, u);
@@ -100,12 +97,7 @@ __global__ __launch_bounds__(256) void k_qtl_trans_totals(const uint32_t *__rest
     __shared__ unsigned long long part[2][256];
     unsigned long long a = 0, b = 0;
     for (uint64_t i = threadIdx.x; i < n_tiles; i += 256) { a += tile_hits[i]; b += tile_tested[i]; }
-    part[0][threadIdx.x] = a; part[1][threadIdx.x] = b;
-    __syncthreads();
-    for (uint32_t off = 128; off; off >>= 1) {
-        if (threadIdx.x < off) { part[0][threadIdx.x] += part[0][threadIdx.x + off]; part[1][threadIdx.x] += part[1][threadIdx.x + off]; }
-        __syncthreads();
-    }
+    qtl_sum2_256(part, a, b);
     if (!threadIdx.x) {
         out[0] = part[0][0]; out[1] = part[1][0]; out[2] = *n_hit_tiles;
         out[3] = (unsigned long long)flag[0] | (unsigned long long)flag[1] << 32; out[4] = *n_usable;
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(256) void k_qtl_trans_emit(QtlTransTiles t, const u
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
             if (!(mine >> (4 * i + j) & 1u)) continue;
-            const uint32_t row = trans_at(i, ty), col = trans_at(j, tx), k = k0 + row, u = v0 + col;
+            const uint32_t row = qtl_tile_at(i, ty), col = qtl_tile_at(j, tx), k = k0 + row, u = v0 + col;
             const uint32_t p = base + before[row] + (uint32_t)__popcll(bits[row] & ((1ull << col) - 1));
             const double g2 = t.u_gg[u];
             hit_row[p] = k; hit_u[p] = u; hit_r[p] = qtl_r(acc[i][j], t.yy[k], g2); hit_slope[p] = qtl_slope(acc[i][j], g2);
