@@ -23,7 +23,7 @@ int EventsRun::run() {
     { const int rc = stage_decode(); if (rc != kGoOn) return rc; }
     const int rc_emit = stage_emit();
     if (rc_emit == RGX_OK) { const int rc = calibrate_arena(); if (rc != RGX_OK) return rc; }
-    P.d_file = rc_emit == RGX_OK && p->n_shards <= 1 && (!p->region || !strcmp(p->region, ".")) ? d_bam : nullptr;      // (every byte of the file went up)
+    P.d_file = rc_emit == RGX_OK && p->n_shards <= 1 && region_kind(p->region) == RegionKind::whole ? d_bam : nullptr;      // (every byte of the file went up)
     return rc_emit;
 }
 
@@ -130,30 +130,25 @@ int EventsRun::stage_upload() {
             if (c->copy_stream) copy_q = c->copy_stream;
             mark("upload streams");
             // A shard of a file whose members the caller scanned: only the bytes this shard reads go up -- the header's members and the
-            // range between its two cuts (the same cuts as below, from the index) -- N shards then move the file once, not N times.
-            size_t up_lo = 0, up_hi = bam_len, hdr_hi = 0;
+            // range between its two cuts (stage_members' cuts: shard_cut_targets, from the index) -- N shards then move the file once, not N times.
+            UploadRange ur{0, bam_len, 0};
             if (shared && p->n_shards > 1 && p->shard >= 0 && p->shard < p->n_shards) {
                 if (bai_thread.joinable()) bai_thread.join();
                 BamHeader hh; size_t hb = 0;
                 if (bai_ok && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hh, &hb)) {
-                    const bool rest0 = p->region && !strcmp(p->region, "*"), whole0 = rest0 || !strcmp(p->region ? p->region : ".", ".");
+                    const RegionKind kind = region_kind(p->region);
                     uint64_t sv = 0;
-                    if (rest0 && bi.have_nocoor) sv = bi.nocoor_voff; else if (whole0 && !rest0 && bi.have_start) sv = bi.start_voff;
+                    if (kind == RegionKind::rest && bi.have_nocoor) sv = bi.nocoor_voff; else if (kind == RegionKind::whole && bi.have_start) sv = bi.start_voff;
                     uint64_t tgt[2], got[2];
-                    for (int k = 0; k < 2; ++k) tgt[k] = std::max<uint64_t>((uint64_t)((double)bam_len * (p->shard + k) / p->n_shards) << 16, sv ? sv : 1);
+                    shard_cut_targets(bam_len, p->shard, p->n_shards, sv ? sv : 1, tgt);
                     bai_first_anchor_ge(bai, bai_len, tgt, 2, got);
-                    if (p->shard > 0 && got[0] != UINT64_MAX) up_lo = std::min<size_t>(bam_len, (size_t)(got[0] >> 16));
-                    else if (p->shard > 0) up_lo = bam_len;
-                    if (p->shard + 1 < p->n_shards && got[1] != UINT64_MAX) up_hi = std::min<size_t>(bam_len, (size_t)(got[1] >> 16) + 2 * kBgzfMaxBlock + 64);
-                    if (up_hi < up_lo) up_hi = up_lo;
-                    // (the header's members, and at least the four the device-side header read starts with)
                     const std::vector<Member> &sm = *shared->members;
-                    if (!sm.empty()) { const Member &m4 = sm[std::min<size_t>(sm.size(), 4) - 1]; hb = std::max<size_t>(hb, (size_t)m4.cpos + m4.clen + 8); }
-                    hdr_hi = std::min(up_lo, hb + 64);
-                    up_lo &= ~(size_t)4095;
-                    if (up_lo < hdr_hi) { up_lo = 0; hdr_hi = 0; }
+                    size_t m4_end = 0;
+                    if (!sm.empty()) { const Member &m4 = sm[std::min<size_t>(sm.size(), 4) - 1]; m4_end = (size_t)m4.cpos + m4.clen + 8; }
+                    ur = shard_upload_range(bam_len, p->shard, p->n_shards, got, hb, m4_end);
                 }
             }
+            const size_t up_lo = ur.lo, up_hi = ur.hi, hdr_hi = ur.hdr_hi;
             // Round 4: ONE inflate launch for the whole range, its waves gated by the arrival of their upload chunk (kernels.h InflateGate):
             // the file goes up in kGateChunks equal chunks, a 4-byte copy of this call's epoch into the chunk's flag word queued right behind each.
             // The members of the early chunks start ~0.6 ms into the upload; only those of the last chunk pay the lane-serial floor behind it
@@ -162,38 +157,16 @@ int EventsRun::stage_upload() {
             const unsigned gate_chunks = overlap_knobs().chunks;
             gated = !c->gate_distrust && !c->one_shot && up_hi - up_lo >= std::min(overlap_min, (size_t)8 << 20) &&
                 up_hi - up_lo >= 2 * 4096 * (size_t)gate_chunks;
+            // ... for payloads whose inflate is of the upload's order, judged by the file's first members
+            if (gated) gated = payload_takes_gate(h_bam, bam_len);
+            // (ungated: three pieces, each its own launch on its own hardware queue -- two side streams + the pipeline's own)
+            UploadChunks uc = plan_upload_chunks(up_lo, up_hi, gated, gate_chunks, c->one_shot);
             if (gated) {
-                // ... for payloads whose inflate is of the upload's order (measured: bench payload 27.5 -> 26.5 ms, random bases + qualities 98.2 ->
-                // 93.7); run-length payloads (long reads: 1 GB of file, 65 GB inflated, five rounds of waves) lose 5-6 ms of 158 to it and keep
-                // the pieces.  The class comes from the file's first members (BSIZE / ISIZE of up to 64 of them: what the host scan will find).
-                uint64_t cb = 0, ub = 0; size_t o = 0;
-                for (int k = 0; k < 64 && o + 28 <= bam_len; ++k) {
-                    if (!(h_bam[o] == 0x1f && h_bam[o + 1] == 0x8b && h_bam[o + 12] == 'B' && h_bam[o + 13] == 'C')) break;
-                    const size_t bl = (size_t)(h_bam[o + 16] | h_bam[o + 17] << 8) + 1;
-                    if (bl < 26 || o + bl > bam_len) break;
-                    uint32_t isz; memcpy(&isz, h_bam + o + bl - 4, 4);
-                    cb += bl; ub += isz; o += bl;
-                }
-                if (cb && !(inflate_plan_for(cb, ub) & 1)) gated = false;
-            }
-            // three pieces, each its own launch on its own hardware queue (two side streams + the pipeline's own; a launch takes ~8 ms however
-            // small -- one lane per member).  Equal thirds measured best: 31.6 ms per step against 32.4-33.3 ms for pieces that shrink towards
-            // the end, and 30.9-31.5 ms for four to six equal pieces on side streams of other priorities (= other queue pools), 32.6 for seven
-            // (tools/lab/pieces.sh): the concurrent launches share the chip, finer pieces do not end sooner.
-            std::vector<unsigned> cuts = {33, 67};
-            if (c->one_shot) cuts.clear();                            // (one stream: pieces would only take turns on it)
-            if (gated) {
-                gate_chunk = (((up_hi - up_lo) + gate_chunks - 1) / gate_chunks + 4095) & ~(size_t)4095;
-                for (size_t e = up_lo + gate_chunk; e < up_hi; e += gate_chunk) up.end.push_back(e);
                 DevBuf &bg = c->buf(Buf::gate_flags);
                 if (!bg.p) { HIP_TRY(bg.ensure(4 * 64)); HIP_TRY(hipMemset(bg.p, 0, 4 * 64)); c->gate_epoch = 0; }
                 ++c->gate_epoch;
-            } else
-            for (unsigned pc : cuts) {
-                const size_t e = (up_lo + (size_t)((double)(up_hi - up_lo) * pc / 100.0) + 4095) & ~(size_t)4095;
-                if (e < up_hi && e > up_lo && (up.end.empty() || e > up.end.back())) up.end.push_back(e);
             }
-            up.end.push_back(up_hi);
+            gate_chunk = uc.gate_chunk; up.end = std::move(uc.end);
             up.lo = up_lo; up.hi = up_hi; up.hdr_hi = hdr_hi;
             while (c->chunk_ev.size() < up.end.size()) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->chunk_ev.push_back(e); }
             uint8_t *dst = b.as<uint8_t>();
@@ -293,10 +266,9 @@ int EventsRun::stage_members() {
     if (bai_thread.joinable()) bai_thread.join();
     if (!bai_ok) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_INDEX, "%s", kMsgIndex);
     mark("parse_bai");
-    // "." = every record from the first one on; "*" = every record behind the last reference's reads (hts_itr_querys, hts.c:1901-1904:
-    // HTS_IDX_START / HTS_IDX_NOCOOR; both read to the end of the file without a predicate)
-    const bool rest = p->region && !strcmp(p->region, "*");
-    whole = rest || !strcmp(p->region ? p->region : ".", ".");
+    // (whole and rest both read to the end of the file without a predicate)
+    const bool rest = region_kind(p->region) == RegionKind::rest;
+    whole = region_kind(p->region) != RegionKind::query;
     // where the record stream starts (hts.c:1721-1741)
     seek = false; seek_voff = 0;
     if (rest) {
@@ -313,10 +285,7 @@ int EventsRun::stage_members() {
         if (p->shard < 0 || p->shard >= p->n_shards) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_ARG, "regtools_amd: shard %d of %d\n",
             p->shard, p->n_shards);
         uint64_t tgt[2], got[2];
-        for (int k = 0; k < 2; ++k) {
-            const int g = p->shard + k;
-            tgt[k] = std::max<uint64_t>((uint64_t)((double)bam_len * g / p->n_shards) << 16, seek ? seek_voff : 1);
-        }
+        shard_cut_targets(bam_len, p->shard, p->n_shards, seek ? seek_voff : 1, tgt);
         bai_first_anchor_ge(bai, bai_len, tgt, 2, got);
         if (p->shard > 0) cut_lo = got[0];
         if (p->shard + 1 < p->n_shards) cut_hi = got[1];
@@ -374,15 +343,9 @@ int EventsRun::stage_members() {
         if (overlap) {
             // the member list is on the host (scan_members_parallel): what k_member_query / k_member_stop would answer, without a round trip
             const uint32_t nm = (uint32_t)hm.size();
-            for (int k = 0; k < 3; ++k) {
-                uint32_t lo_ = 0, hi_ = nm;
-                while (lo_ < hi_) { const uint32_t mid = lo_ + (hi_ - lo_) / 2; if (hm[mid].cpos < q[k] + 18) lo_ = mid + 1; else hi_ = mid; }
-                const bool hit = lo_ < nm && hm[lo_].cpos == q[k] + 18;
-                h_sc->q_index[k] = hit ? lo_ : nm; h_sc->q_upos[k] = hit ? hm[lo_].upos : ~0ull;
-            }
-            uint32_t stop_ = 0xffffffffu;
-            for (uint32_t i = h_sc->q_index[0]; i < nm; ++i) if (hm[i].isize == 0 || hm[i].isize > kBgzfMaxBlock) { stop_ = i; break; }
-            h_sc->stop = stop_; h_sc->n_members = nm; h_sc->total_inflated = hm_total;
+            const MemberQuery mq = host_member_query(hm.data(), nm, q);
+            memcpy(h_sc->q_index, mq.q_index, sizeof mq.q_index); memcpy(h_sc->q_upos, mq.q_upos, sizeof mq.q_upos);
+            h_sc->stop = mq.stop; h_sc->n_members = nm; h_sc->total_inflated = hm_total;
             return hipSuccess;
         }
         return disc.query(q);
@@ -427,22 +390,10 @@ int EventsRun::stage_range_and_inflate() {
     // -- member range of this call ---------------------------------------------------------------------------------------------
     std::vector<Member> &hm = c->hm_scratch;
     DevBuf &b_arena = c->buf(Buf::arena);
-    m_lo = cut_lo ? h_sc->q_index[1] : 0;
-    if (m_lo <= 4) m_lo = 0;        // keep the file head (BAM header) in the same launch: a lone lane needs milliseconds per member
-    m_hi = stop;                                                  // exclusive
-    if (cut_hi != UINT64_MAX) {
-        const uint32_t mh = h_sc->q_index[2];
-        const uint32_t hi_m = (mh < n_members_all && (cut_hi & 0xffff)) ? mh + 1 : mh;
-        // a region's chunks: each is a seek of its own, so an empty member between two of them ends nothing (the chunks' own limits do
-        // that, below); two members more than the index asks for, for the records of a stale index that run past their chunk's end
-        if (chunked) m_hi = region_to_file_end ? n_members_all : (uint32_t)std::min<uint64_t>(n_members_all, (uint64_t)hi_m + 2);
-        else m_hi = std::min(stop, hi_m);
-    }
-    if (m_lo > m_hi) m_lo = m_hi;
+    member_range(cut_lo, cut_hi, h_sc->q_index, stop, n_members_all, chunked, region_to_file_end, m_lo, m_hi);
     if (overlap && (up.lo || up.hi < bam_len) && m_hi > m_lo) {
         // only a byte range of the file went up (a shard of a shared scan): it must hold every member of this call's range
-        const uint64_t need_lo = hm[m_lo].cpos - 18, need_hi = hm[m_hi - 1].cpos + hm[m_hi - 1].clen + 16;
-        if (need_lo < up.lo || need_hi > up.hi) {
+        if (!upload_covers_members(hm.data(), m_lo, m_hi, up.lo, up.hi)) {
             mark("shard range does not cover its members: whole-file upload");
             up.th.join();
             HIP_TRY(hipStreamSynchronize(copy_q));
@@ -494,7 +445,7 @@ int EventsRun::stage_range_and_inflate() {
         HIP_TRY(b_lens.ensure(inflate_scratch_bytes(std::max<uint32_t>(n_range, 64)) + up.end.size() * inflate_scratch_bytes(64)));
         HIP_TRY(hipEventRecord(c->ev_ready, st));
         for (auto &q : c->side) if (q) HIP_TRY(hipStreamWaitEvent(q, c->ev_ready, 0));
-        uint32_t g_lo = m_lo; unsigned used_side = 0;
+        unsigned used_side = 0;
         Carve w_lens(b_lens);                                   // (every per-chunk launch below takes its own scratch)
         if (gated) {
             // one launch on the pipeline's stream, now: its waves wait for their chunk's flag themselves (k_inflate_coop; a range the wave form
@@ -508,30 +459,9 @@ int EventsRun::stage_range_and_inflate() {
                 // (launch_wait_done) and frames, verifies and decodes the part of the arena behind it while the waves of the later parts still
                 // run -- what is left behind the launch's end is the last part's framing and decode, not the whole file's.  (A member's own
                 // chain puts the end of the launch 6-9 ms behind the last chunk's arrival, whatever the chip does meanwhile.)
-                // REGTOOLS_AMD_EARLY_TAIL="6,9,12,14" = the cuts in sixteenths of the upload (up to seven; the default since round 5: 23.5 ms per step where
-                // "8,12,14" gives 24.5 -- the tail
-                // under the launch is the critical path from the first part on, so it starts earlier and in smaller parts;
-                // profiles/r05_step_early_tail_four_cuts_ab.txt), "0" = off.
-                static const std::vector<unsigned> env_cuts = [] {
-                    std::vector<unsigned> v; const char *e = getenv("REGTOOLS_AMD_EARLY_TAIL");
-                    unsigned x7[7] = {0, 0, 0, 0, 0, 0, 0};
-                    const int n = sscanf(e ? e : "6,9,12,14", "%u,%u,%u,%u,%u,%u,%u", &x7[0], &x7[1], &x7[2], &x7[3], &x7[4], &x7[5], &x7[6]);
-                    for (unsigned x : x7) if ((int)v.size() < n && x > 0 && x < 16 && (v.empty() || x > v.back())) v.push_back(x);
-                    return v;
-                }();
-                const uint32_t early_min = overlap_knobs().early_min;
-                if (!env_cuts.empty() && !c->early_distrust && c->side[1] && up.end.size() >= 8 && !d_bad && !d_true_sizes) {
-                    const uint32_t align = kInflateSortGroup;          // (a wave's members all come from one group of that many)
-                    for (unsigned cut : env_cuts) {
-                        const size_t kA = std::max<size_t>(1, up.end.size() * (size_t)cut / 16);
-                        const uint64_t lim_b = up.end[kA - 1];
-                        uint32_t lo = m_lo, hi = m_hi;             // first member that reads bytes behind chunk kA - 1 (k_inflate_coop's own rule)
-                        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (hm[mid].cpos + hm[mid].clen + 24 <= lim_b) lo = mid + 1; else hi = mid; }
-                        uint32_t k = (lo - m_lo) / align * align;     // members of the range in front of the cut
-                        const uint32_t prev = early_parts.empty() ? 0u : early_parts.back().members;
-                        if (k >= prev + early_min && n_range - k >= early_min) early_parts.push_back(EarlyPart{k, k / 64, hm[m_lo + k].upos - upos_lo});
-                    }
-                }
+                if (!early_cuts().empty() && !c->early_distrust && c->side[1] && up.end.size() >= 8 && !d_bad && !d_true_sizes)
+                    early_parts = plan_early_parts(hm.data(), m_lo, m_hi, upos_lo, up.end.data(), up.end.size(), early_cuts(), overlap_knobs().early_min,
+                        kInflateSortGroup);
                 if (!early_parts.empty()) {
                     DevBuf &bd = c->buf(Buf::gate_done);
                     HIP_TRY(bd.ensure(64));
@@ -550,17 +480,11 @@ int EventsRun::stage_range_and_inflate() {
                 HIP_TRY(hipStreamWaitEvent(st, c->chunk_ev[up.end.size() - 1], 0));
                 timed_launch(st, false, InflateGate());
             }
-            g_lo = m_hi;
         }
-        for (size_t j = 0; j < up.end.size() && g_lo < m_hi; ++j) {
-            uint32_t g_hi = m_hi;
-            if (j + 1 < up.end.size()) {     // first member of [g_lo, m_hi) that needs bytes beyond this chunk
-                const uint64_t lim_b = up.end[j];
-                uint32_t lo = g_lo, hi = m_hi;
-                while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (hm[mid].cpos + hm[mid].clen + 16 <= lim_b) lo = mid + 1; else hi = mid; }
-                g_hi = lo;
-            }
-            if (g_hi == g_lo) continue;
+        // (the gated launch took the whole range: no pieces)
+        for (const Piece &pc : gated ? std::vector<Piece>() : plan_pieces(hm.data(), m_lo, m_hi, up.end.data(), up.end.size())) {
+            const size_t j = pc.chunk;
+            const uint32_t g_lo = pc.g_lo, g_hi = pc.g_hi;
             // (an event must have been recorded before a stream can wait on it)
             while (up.recorded.load(std::memory_order_acquire) <= j) std::this_thread::yield();
             if (up.err) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: upload failed\n");
@@ -573,7 +497,6 @@ int EventsRun::stage_range_and_inflate() {
             HIP_TRY(hipStreamWaitEvent(q, c->chunk_ev[j], 0));
             launch_inflate(d_bam, d_members + g_lo, g_hi - g_lo, b_arena.as<uint8_t>(), upos_lo, lens,
                 &d_sc->inflate.first_bad, q, ignore_below, g_lo - m_lo, /*piece=*/true, 0, d_bad, pairs);
-            g_lo = g_hi;
         }
         up.th.join();
         // (gated waves give up after ~2 s)

@@ -2,7 +2,7 @@
 // context's are named by enum Buf and cut into arrays with carve.h's Carve), the radix-sort helper, one call's state (EventsRun) and the functions one unit
 // calls in another.  Round 6: api.cpp (2,600 lines, with cse_api.inc included into it) split along its stages --
 //   api_ctx.cpp      contexts, streams, result tables and their text
-//   api_front.cpp    EventsRun: upload, member list, the DEFLATE launch (+ the opt-in arena placement trials)
+//   api_front.cpp    EventsRun: upload, member list, the DEFLATE launch (+ the opt-in arena placement trials); what they decide: front_plan.h (no HIP)
 //   api_records.cpp  EventsRun: footers and header, record framing, decode, emit
 //   api_reduce.cpp   group-by, output order, barcodes, the finished table
 //   api_entry.cpp    the extract entry points, packing and merging of tables
@@ -307,6 +307,13 @@ inline const OverlapKnobs &overlap_knobs() {
     }();
     return k;
 }
+// REGTOOLS_AMD_EARLY_TAIL="6,9,12,14" = the early tail's cuts in sixteenths of the upload (parse_early_cuts: up to seven; the default since round 5: 23.5 ms
+// per step where "8,12,14" gives 24.5 -- the tail under the launch is the critical path from the first part on, so it starts earlier and in smaller
+// parts; profiles/r05_step_early_tail_four_cuts_ab.txt), "0" = off.
+inline const std::vector<unsigned> &early_cuts() {
+    static const std::vector<unsigned> v = parse_early_cuts(getenv("REGTOOLS_AMD_EARLY_TAIL"));
+    return v;
+}
 // Two things the contexts of one pipeline (pipeline.cpp) take in turns, first come first served:
 //   wire -- the host link: a call's upload starts when the call before it has ITS file on the device (two uploads at once halve the link between them);
 //   chip -- the DEFLATE launch: a call's launch is enqueued when the launch before it has finished.  One launch is 2,647 of the chip's 3,072 wave slots and all
@@ -571,9 +578,7 @@ struct EventsRun {
         out_v = m.upos;
         return e;
     }
-    // a part ends in front of member `members` of the range = workgroup `waves` = arena offset `upos`
-    struct EarlyPart { uint32_t members, waves; uint64_t upos; };
-    std::vector<EarlyPart> early_parts;
+    std::vector<EarlyPart> early_parts;                       // (front_plan.h plan_early_parts)
     // early tail: the gated launch still runs on a side stream; whoever reads its part of the arena waits for it
     bool split_B = false; hipEvent_t split_ev = nullptr;
     hipError_t join_B() {

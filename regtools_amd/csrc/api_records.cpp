@@ -251,8 +251,7 @@ int EventsRun::stage_framing() {
     span = lim - pos0;
     n_seg = (uint32_t)((span + seg_bytes - 1) / seg_bytes);
     geom.pos0 = pos0; geom.lim = lim; geom.data_end = lim; geom.seg_bytes = seg_bytes;
-    const int env_lite = 1;
-    lite_walk = env_lite && !c->walk_strict;
+    lite_walk = !c->walk_strict;
     geom.lite_walk = lite_walk ? 1u : 0u;
     if (geom.chunks) {
         span = 0;
@@ -287,14 +286,12 @@ int EventsRun::stage_framing() {
         seg_iter_e = q.u32(per); seg_long_e = q.u32(per); seg_long_base_e = q.u32(per); CARVE_TRY(q, "seg");
         HIP_TRY(b_tmp.ensure(scan_tmp_words(n_seg) * 4 + 64));
         bool early = split_B && spec && !geom.chunks && seg_bytes == kSegBytes && cut_hi == UINT64_MAX && !empty_stream && lim == total;
-        const bool env_early_emit = true;
         const bool small_ok = overlap_knobs().early_small;
         uint32_t waves_done = 0;
         for (size_t j = 0; early && j < early_parts.size(); ++j) {
             const EarlyPart &ep = early_parts[j];
-            if (ep.upos <= pos0 + 2 * (uint64_t)kBgzfMaxBlock) continue;
-            uint32_t sJ = (uint32_t)std::min<uint64_t>(n_seg, (ep.upos - kBgzfMaxBlock - pos0) / seg_bytes);
-            if (small_ok ? (sJ < sA + 2 || n_seg - sJ < 1) : (sJ < sA + 1024 || n_seg - sJ < 64)) continue;
+            const uint32_t sJ = early_prefix_segments(ep.upos, pos0, seg_bytes, n_seg, sA, small_ok);
+            if (!sJ) continue;                                 // (too little in front of the part to be worth the wait)
             // the stream waits until every wave of parts 0..j has finished (the counters of the parts are waited for in turn)
             HIP_TRY(hipMemsetAsync(&d_sc->wait_timed_out, 0, 4, st));
             for (size_t i = 0; i <= j; ++i) {
@@ -340,7 +337,7 @@ int EventsRun::stage_framing() {
             if (!sA) {
                 DevBuf &b_ev0 = c->buf(Buf::events);
                 ev_lay = b_ev0.cap > 256 ? (b_ev0.cap - 256) / kEventRowBytes : 0;
-                emit_parts_ok = env_early_emit && ev_lay >= 4096;
+                emit_parts_ok = ev_lay >= 4096;
                 if (emit_parts_ok) { HIP_TRY(b_tmp.ensure(scan_tmp_words((uint32_t)std::min<size_t>(soa_cap, 0xffffffffu)) * 4 + 64));
                     Carve w(b_ev0); ev_e = ev_layout(w, ev_lay); CARVE_TRY(w, "events"); }
             }

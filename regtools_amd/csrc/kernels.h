@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "bam_core.h"
+#include "front_plan.h"
 
 namespace rgx {
 
@@ -42,7 +43,8 @@ void launch_inflate(const uint8_t *comp, const Member *members, uint32_t n_membe
                     uint32_t *status /* [0]=first bad member (min), [1]=its status */, hipStream_t stream, uint32_t ignore_below = 0 /* failures of members below this index are not reported */,
                     uint32_t index_bias = 0 /* added to the launch's member index in status[] and in the ignore_below test: a range launched in pieces */,
                     bool piece = false /* one of several concurrent launches over a range (own kernel symbol, same code) */,
-                    int form = 0 /* 0 = chosen by member count / REGTOOLS_AMD_INFLATE; 1 = k_inflate, 2 = k_inflate_wave, 3 = k_inflate_ring */,
+                    int form = 0 /* 0 = chosen by member count / REGTOOLS_AMD_INFLATE; 1 = k_inflate, 2 = k_inflate_wave, 3 = k_inflate_ring, 4 = k_inflate_coop,
+                                     5 = k_inflate with four literals per trip */,
                     uint8_t *bad_flags = nullptr /* optional, zeroed by the caller: [index in the caller's range] = 1 for every member that did not inflate */,
                     int plan = 1 /* inflate_plan_for */,
                     bool check_layout = false /* a caller's own member list (stage entry point): k_inflate_coop only runs when the list's layout suits it */,
@@ -52,21 +54,7 @@ bool inflate_takes_coop(uint32_t n_members);
 // the host scan's member list (page-locked host memory, n_members + 1 members long) into a device block of the same length
 void launch_members_fetch(const Member *host_members, Member *dst, uint32_t n_members, hipStream_t stream);
 void launch_gate_set(uint32_t *flag, uint32_t epoch, hipStream_t stream);      // flags[k] = epoch, in stream order behind chunk k's copy
-// Which options suit a payload, from how well the file compresses (round 4, 50 M-read files / 10 M long reads on one box, ms, all byte-equal to zlib;
-// tools/lab/forms_r4.sh, profiles/r04_inflate_forms.txt):
-//   inflated / compressed > 32  (long reads: run-length copies)        k_inflate_coop, windowed bit reader, one symbol per trip, lanes in file order:
-//                                                                      117.5-118.7 (round 3's choice -- plain reader -- 120.7-122.2; pairs + sorted lanes 122; k_inflate 131)
-//   <= 32                       (the bench payload: 21;                 k_inflate_coop, windowed bit reader, literal pairs, lanes sorted by compressed length
-//                                random bases + binned qualities: 3.6)  per 1024 members: bench payload 14.5-15.2 (k_inflate 19.9-21.3); random bases 44.9-47.5
-//                                                                      (k_inflate with four literals per trip, round 3's choice for them: 53.1-54.1)
-// bit 0 = literal pairs + sorted lanes.  (k_inflate stays selectable: REGTOOLS_AMD_INFLATE=lane, form 1 / 5 of the stage entry point.)
-// Second half of round 4 (k_inflate_coop's mode word, launch_inflate): runs at distances of 16 bytes or less are written from registers, 64 bytes a
-// trip, for every class (long reads 121.2 -> 79.8 ms: half their trips were such runs growing 1, 2, 4 ... bytes a trip, each with a partial-chunk
-// store); up to 32 x also a literal pair and the match behind it in one trip, bits counted exactly (bench payload 2,030 -> 1,463 trips per
-// member, 15.2 -> 14.1-15.0 ms: the launch follows its memory requests, not its trips).
-inline int inflate_plan_for(uint64_t compressed_bytes, uint64_t inflated_bytes) {
-    return compressed_bytes * 32 > inflated_bytes ? 1 : 0;
-}
+// (inflate_plan_for -- which options suit a payload -- is front_plan.h's)
 
 // ---- a1 (container): BGZF member discovery on the device --------------------------------------------------
 // The member chain (bgzf.c:525: next = this + BSIZE + 1) is serial on a CPU (one dependent cache miss per member).

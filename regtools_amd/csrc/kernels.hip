@@ -373,9 +373,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         // the upload chunk with the last byte any lane of this wave reads (payload + footer + the bit reader's look-ahead); one lane polls,
         // seldom (every waiting wave's poll is a request to the fabric the running waves share), an acquire then drops what this CU's L1 may
         // hold.  A chunk that never comes (the host gave up): after ~2 s the wave's members are reported as not inflated.
-        uint64_t end_b = mb.cpos + mb.clen + 24;
-        end_b = end_b > gate.lo ? end_b - gate.lo : 0;
-        uint32_t need = (uint32_t)min((uint64_t)(gate.n_chunks - 1), end_b / gate.chunk_bytes);
+        uint32_t need = gate_chunk_needed(mb.cpos, mb.clen, gate.lo, gate.chunk_bytes, gate.n_chunks);
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) need = max(need, (uint32_t)__shfl_xor((int)need, d, 64));
         bool arrived = true;

@@ -390,3 +390,65 @@ extern "C" long emu_variant_scan(const void *h, uint32_t n, const int32_t *conti
     hit_off[n] = (uint32_t)k;
     return (long)k;
 }
+
+// front_plan.h on its own: the plan of an extract call's front (upload range and chunks, the gate, member ranges, pieces, early-tail parts).  Member lists
+// are arrays of rgx::Member (cpos, upos: u64; clen, isize: u32); lists come back in the caller's arrays, the function's value is their length.
+#include "../../regtools_amd/csrc/front_plan.h"
+extern "C" int emu_front_region_kind(const char *region) { return (int)rgx::region_kind(region); }       // 0 whole, 1 rest, 2 query
+extern "C" void emu_front_shard_cut_targets(size_t bam_len, int shard, int n_shards, uint64_t floor_voff, uint64_t *tgt) {
+    rgx::shard_cut_targets(bam_len, shard, n_shards, floor_voff, tgt);
+}
+extern "C" void emu_front_shard_upload_range(size_t bam_len, int shard, int n_shards, const uint64_t *got, size_t header_bytes, size_t fourth_member_end,
+                                             size_t *out3) {
+    const rgx::UploadRange r = rgx::shard_upload_range(bam_len, shard, n_shards, got, header_bytes, fourth_member_end);
+    out3[0] = r.lo; out3[1] = r.hi; out3[2] = r.hdr_hi;
+}
+extern "C" int emu_front_payload_takes_gate(const uint8_t *bam, size_t n) { return rgx::payload_takes_gate(bam, n) ? 1 : 0; }
+extern "C" int emu_front_inflate_plan_for(uint64_t compressed, uint64_t inflated) { return rgx::inflate_plan_for(compressed, inflated); }
+extern "C" size_t emu_front_upload_chunks(size_t up_lo, size_t up_hi, int gated, unsigned gate_chunks, int one_shot, size_t *gate_chunk, size_t *end,
+                                          size_t cap) {
+    const rgx::UploadChunks u = rgx::plan_upload_chunks(up_lo, up_hi, gated != 0, gate_chunks, one_shot != 0);
+    *gate_chunk = u.gate_chunk;
+    for (size_t k = 0; k < u.end.size() && k < cap; ++k) end[k] = u.end[k];
+    return u.end.size();
+}
+extern "C" void emu_front_member_query(const rgx::Member *hm, uint32_t n, const uint64_t *q, uint32_t *q_index, uint64_t *q_upos, uint32_t *stop) {
+    const rgx::MemberQuery r = rgx::host_member_query(hm, n, q);
+    for (int k = 0; k < 3; ++k) { q_index[k] = r.q_index[k]; q_upos[k] = r.q_upos[k]; }
+    *stop = r.stop;
+}
+extern "C" void emu_front_member_range(uint64_t cut_lo, uint64_t cut_hi, const uint32_t *q_index, uint32_t stop, uint32_t n_members_all, int chunked,
+                                       int region_to_file_end, uint32_t *out2) {
+    rgx::member_range(cut_lo, cut_hi, q_index, stop, n_members_all, chunked != 0, region_to_file_end != 0, out2[0], out2[1]);
+}
+extern "C" uint32_t emu_front_lookahead(int gate) { return gate ? rgx::kGateLookahead : rgx::kPieceLookahead; }
+extern "C" uint32_t emu_front_first_member_reading_past(const rgx::Member *hm, uint32_t lo, uint32_t hi, uint64_t lim_b, uint32_t lookahead) {
+    return rgx::first_member_reading_past(hm, lo, hi, lim_b, lookahead);
+}
+extern "C" uint32_t emu_front_gate_chunk_needed(uint64_t cpos, uint32_t clen, uint64_t gate_lo, uint64_t chunk_bytes, uint32_t n_chunks) {
+    return rgx::gate_chunk_needed(cpos, clen, gate_lo, chunk_bytes, n_chunks);
+}
+extern "C" int emu_front_upload_covers_members(const rgx::Member *hm, uint32_t m_lo, uint32_t m_hi, size_t up_lo, size_t up_hi) {
+    return rgx::upload_covers_members(hm, m_lo, m_hi, up_lo, up_hi) ? 1 : 0;
+}
+extern "C" size_t emu_front_pieces(const rgx::Member *hm, uint32_t m_lo, uint32_t m_hi, const size_t *end, size_t n_end, uint32_t *out3, size_t cap) {
+    const std::vector<rgx::Piece> v = rgx::plan_pieces(hm, m_lo, m_hi, end, n_end);
+    for (size_t k = 0; k < v.size() && k < cap; ++k) { out3[3 * k] = v[k].chunk; out3[3 * k + 1] = v[k].g_lo; out3[3 * k + 2] = v[k].g_hi; }
+    return v.size();
+}
+extern "C" size_t emu_front_early_cuts(const char *env_text, unsigned *out, size_t cap) {
+    const std::vector<unsigned> v = rgx::parse_early_cuts(env_text);
+    for (size_t k = 0; k < v.size() && k < cap; ++k) out[k] = v[k];
+    return v.size();
+}
+extern "C" size_t emu_front_early_parts(const rgx::Member *hm, uint32_t m_lo, uint32_t m_hi, uint64_t upos_lo, const size_t *end, size_t n_end,
+                                        const unsigned *cuts, size_t n_cuts, uint32_t early_min, uint32_t align, uint32_t *members, uint32_t *waves,
+                                        uint64_t *upos, size_t cap) {
+    const std::vector<rgx::EarlyPart> v = rgx::plan_early_parts(hm, m_lo, m_hi, upos_lo, end, n_end, std::vector<unsigned>(cuts, cuts + n_cuts), early_min,
+                                                                align);
+    for (size_t k = 0; k < v.size() && k < cap; ++k) { members[k] = v[k].members; waves[k] = v[k].waves; upos[k] = v[k].upos; }
+    return v.size();
+}
+extern "C" uint32_t emu_front_early_prefix_segments(uint64_t part_upos, uint64_t pos0, uint32_t seg_bytes, uint32_t n_seg, uint32_t s_done, int small_ok) {
+    return rgx::early_prefix_segments(part_upos, pos0, seg_bytes, n_seg, s_done, small_ok != 0);
+}
