@@ -735,6 +735,161 @@ size_t rgx_cohort_format_qtl_group(const rgx_cohort_matrix *m, const rgx_cohort_
                                    const rgx_qtl_group_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
 
 /* -----------------------------------------------------------------------------------------------------
+ * The CONDITIONAL permutation pass: the permutation pass of a table row with further variants of its window in the model -- the primitive under
+ * tensorQTL's map_independent and QTLtools' conditional pass, neither of which is available to this project: checked against a restatement in
+ * exact rationals and against least squares of the full model y ~ 1 + covariates + conditioning variants + g.  In the space the nominal contract
+ * has residualised, conditioning on m variants is a rank-m correction of the permutation pass's product:
+ *   y'_p . g' = y'_p . g - sum_j (y'_p . z_j)(g . z_j),   z_0 .. z_(m-1) an orthonormal basis of the conditioning residuals.
+ * DELIBERATE DEVIATIONS: those of the permutation pass; there is no grouped conditional pass.
+ *   input                 everything rgx_cohort_qtl_permute takes; n_series = N conditional SERIES: series c is table row k = series_row[c]
+ *                         with the m_c = cond_begin[c + 1] - cond_begin[c] input variants cond_variant[cond_begin[c] ..], in the order given.  A
+ *                         row may stand in several series.  The result echoes the lists with cond_begin starting at 0
+ *   errors                RGX_ERR_ARG, before any launch: the nominal scan's and the permutations' (with N (B + 1) > 2^32 - 2^16 for the
+ *                         result's size); N == 0; a row >= K; m_c == 0 or m_c > RGX_QTL_MAX_COND; S < n_cov + 3 + m_c; a conditioning variant
+ *                         >= V, repeated within its series, or not cis to its row; more than 2^32 - 2^16 variants cis to the series' rows in
+ *                         all.  RGX_ERR_ARG also for a conditioning variant whose verdict is not 0: the device reports it through a flag word
+ *                         beside the nominal scan's two, the twin when it meets it
+ *   steps                 basis, dot64, residuals Y[k] with yy, G[v] with gg, verdicts, flat rows and cis ranges: the nominal contract's, unchanged
+ *   basis of series c     for j = 0 .. m - 1 in order: v = G[cond_variant_j]; TWICE for i = 0 .. j - 1 in order d = dot64(v, z_i) and v[s] =
+ *                         fma(-d, z_i[s], v[s]); nn = dot64(v, v); the series is COLLINEAR (cond_status 1: no pairs, yy_cond +0.0) when
+ *                         !(nn > 1e-12 * S) for any j; z_j[s] = v[s] / sqrt(nn), the root and the quotient rounded on their own
+ *   row of series c       y' = Y[k]; for j in order d = dot64(y', z_j), y'[s] = fma(-d, z_j[s], y'[s]); yy_cond[c] = dot64(y', y'); the
+ *                         series is FLAT (cond_status 2: no pairs) when !(yy_cond > 1e-12 * S)
+ *   per usable cis u      of row k (n_window[c] of them, the permutation pass's n_cis[k]): x = G[u]; for j in order beta[c][j][u] = d =
+ *                         dot64(x, z_j), x[s] = fma(-d, z_j[s], x[s]); gg'[c][u] = dot64(x, x), from the projected vector and not as gg -
+ *                         sum beta^2, which cancels under high LD.  u TAKES PART when gg' > 1e-12 * S: the conditioning variants themselves and
+ *                         whatever is in perfect LD with the set drop out here, with no rule of their own.  n_cis[c] = the variants that take part
+ *   per (c, b, j)         alpha[c][b][j] = ONE chain acc = fma(y'[perm[b][s]], z_j[s], acc) in ascending s from +0.0
+ *   per (c, b, u)         u taking part: dot = ONE chain acc = fma(y'[perm[b][s]], G[u][s], acc) in ascending s from +0.0, then for j = 0 .. m -
+ *                         1 in order dot = fma(-alpha[c][b][j], beta[c][j][u], dot); r = dot / sqrt(yy_cond[c] * gg'[c][u]); slope = dot /
+ *                         gg'[c][u]
+ *   perm_r, best, n_ge, p_perm, beta approximation    the permutation pass's rules per series, with dof[c] = S - n_cov - 2 - m_c: perm_r[c][b] the
+ *                         largest |r| as bit patterns, +0.0 throughout without pairs; the best of b = 0 the earliest on ties; beta_status 2
+ *                         for a series without pairs
+ * ----------------------------------------------------------------------------------------------------- */
+#define RGX_QTL_MAX_COND 8
+/* Owned by the library (rgx_cohort_qtl_cond_free), one block, page-locked on the device path. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_variants;      /* V */
+    uint32_t   n_cov;
+    uint32_t   n_perm;          /* B */
+    uint32_t   n_series;        /* N */
+    uint32_t   n_cond;          /* cond_begin[N]: the length of cond_variant */
+    uint64_t   n_pairs;         /* the sum of n_cis */
+    uint8_t   *variant_verdict; /* V: 0 usable, 1 constant, 2 explained by the covariates */
+    double    *yy;              /* K */
+    double    *gg;              /* V */
+    uint32_t  *series_row;      /* N */
+    uint32_t  *cond_begin;      /* N + 1, from 0 */
+    uint32_t  *cond_variant;    /* n_cond */
+    uint8_t   *cond_status;     /* N: 0, 1 collinear, 2 flat */
+    double    *yy_cond;         /* N */
+    uint32_t  *dof;             /* N: S - n_cov - 2 - m_c */
+    uint32_t  *n_window;        /* N: the row's usable cis variants */
+    uint32_t  *n_cis;           /* N: those of them that take part; 0 for a collinear or flat series */
+    double    *perm_r;          /* N x (B + 1), row-major */
+    uint32_t  *best_variant;    /* N: an input variant, or RGX_NO_PAIR */
+    double    *best_r, *best_slope;   /* N */
+    uint32_t  *n_ge;            /* N */
+    double    *p_perm;          /* N */
+    double    *beta_shape1, *beta_shape2, *p_beta;   /* N */
+    uint8_t   *beta_status;     /* N */
+    /* statistics */
+    uint64_t   n_constant, n_explained, n_flat_rows;
+    uint64_t   n_collinear, n_flat_series;
+    uint64_t   n_tiles;         /* the device's products of 64 permutations x 64 usable variants: per series with cond_status 0
+                                   ceil((B + 1) / 64) * ceil(n_window / 64) (the twin: 0) */
+    double     ms_cond;         /* this call, wall */
+    double     ms_residual;     /* device time from the first upload to the sample-major residuals (the twin: its residual loops, wall) */
+    double     ms_prepare;      /* device time of the bases, the rows, beta and gg' (the twin: 0, it prepares inside its product loops) */
+    double     ms_products;     /* device time of the conditioned products and the best pairs (the twin: its loops, wall) */
+    double     ms_beta;         /* the beta approximation, host wall */
+} rgx_qtl_cond_result;
+/* On the cohort's device and stream: the permutation pass's stages up to the permutations in HBM, then a wave per series for its basis and
+ * row, a wave per (series, usable cis variant) for beta and gg', one workgroup per (series, 64 permutations) over all the row's tiles of 64
+ * usable variants, a wave per series for n_cis and the best pair, ONE host wait in front of the copies back, the beta approximation on the
+ * host. */
+int  rgx_cohort_qtl_permute_conditional(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants,
+                                        const uint32_t *var_tid, const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov,
+                                        const double *covariates, uint32_t window, uint32_t n_perm, const uint16_t *perm, uint32_t n_series,
+                                        const uint32_t *series_row, const uint32_t *cond_begin, const uint32_t *cond_variant,
+                                        rgx_qtl_cond_result **out, char *err, size_t errlen);
+/* Host twin: the same chains in plain C++ (std::fma), the same beta function, no device.  NOT a fallback. */
+int  rgx_cohort_qtl_permute_conditional_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                                             const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates,
+                                             uint32_t window, uint32_t n_perm, const uint16_t *perm, uint32_t n_series, const uint32_t *series_row,
+                                             const uint32_t *cond_begin, const uint32_t *cond_variant, rgx_qtl_cond_result **out, char *err,
+                                             size_t errlen);
+void rgx_cohort_qtl_cond_free(rgx_qtl_cond_result *q);
+
+/* -----------------------------------------------------------------------------------------------------
+ * The conditionally independent cis-sQTL signals of every table row: a forward-backward search over the conditional pass -- tensorQTL's
+ * map_independent, QTLtools' conditional pass.  One preparation serves the whole call on the device; every round is one conditional pass and
+ * one host wait, since the beta fits decide the next round's series.  The decisions are one function for the device path and the twin.
+ * DELIBERATE DEVIATIONS: the permutation pass's (no adaptive permutations, no re-estimated dof); no q-values -- the threshold is ONE p for every
+ * row, where tensorQTL takes a per-phenotype threshold from the FDR step; no grouped conditional pass.
+ *   input                 everything rgx_cohort_qtl_permute takes; p_threshold in (0, 1]; max_signals in 1 .. RGX_QTL_MAX_COND.  RGX_ERR_ARG
+ *                         otherwise, and for every error of the two passes
+ *   OK(series)            the series (or round-0 row) has pairs (n_cis > 0), beta_status != 2 and p_beta <= p_threshold
+ *   round 0               the ungrouped permutation pass as it is.  A row ENTERS when OK; its signal 1 is best_variant
+ *   room                  a row with n signals goes another round when n < max_signals and n <= S - n_cov - 3 (the next series' degrees of
+ *                         freedom); else it leaves with capped set
+ *   forward               each round is ONE conditional pass over the rows still active, in row order, each conditioned on its signals so far
+ *                         in order of discovery.  A row whose series is OK appends that series' best variant and stays while it has room;
+ *                         otherwise it leaves
+ *   backward              ONE conditional pass: for every row with n >= 2 forward signals and every i < n, in (row, i) order, one series
+ *                         conditioned on the other n - 1 signals in forward order.  Signal i is KEPT with rank = i + 1 when its series is OK and
+ *                         that series' best variant has not been kept for this row by a smaller i; its record is the series'.  A row with
+ *                         one forward signal keeps its round-0 record with rank 1 and n_cond 0
+ *   result                the kept signals in (row, rank) order, CSR by table row
+ * ----------------------------------------------------------------------------------------------------- */
+/* Owned by the library (rgx_cohort_qtl_indep_free), one block. */
+typedef struct {
+    uint64_t   n_rows;          /* K */
+    uint32_t   n_samples;       /* S */
+    uint32_t   n_variants;      /* V */
+    uint32_t   n_cov;
+    uint32_t   n_perm;          /* B */
+    uint32_t   max_signals;
+    double     p_threshold;
+    uint64_t   n_signals;       /* sig_begin[K] */
+    uint32_t  *sig_begin;       /* K + 1 */
+    uint8_t   *capped;          /* K */
+    /* per kept signal */
+    uint32_t  *variant;         /* an input variant */
+    uint32_t  *rank;            /* 1-based place in the row's forward order */
+    uint32_t  *n_cond;          /* the variants its record is conditioned on */
+    uint32_t  *dof;             /* S - n_cov - 2 - n_cond */
+    uint32_t  *n_cis;           /* the variants that took part */
+    double    *r, *slope, *p_perm, *beta_shape1, *beta_shape2, *p_beta;
+    uint8_t   *beta_status;
+    /* statistics */
+    uint64_t   n_entered;       /* rows with a signal behind round 0 */
+    uint32_t   n_forward_rounds;/* conditional passes going forward */
+    uint64_t   n_series_total;  /* conditional series in all, forward and backward */
+    uint64_t   n_capped;
+    double     ms_indep;        /* this call, wall */
+    double     ms_round0, ms_forward, ms_backward;   /* wall, each with its host part */
+} rgx_qtl_indep_result;
+int  rgx_cohort_qtl_independent(rgx_cohort *co, const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants,
+                                const uint32_t *var_tid, const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates,
+                                uint32_t window, uint32_t n_perm, const uint16_t *perm, double p_threshold, uint32_t max_signals,
+                                rgx_qtl_indep_result **out, char *err, size_t errlen);
+/* Host twin: the same loop over the two host twins, each of which prepares for itself.  NOT a fallback. */
+int  rgx_cohort_qtl_independent_host(const rgx_pheno_table *ph, const rgx_qtl_region *regions, uint32_t n_variants, const uint32_t *var_tid,
+                                     const uint32_t *var_pos, const int8_t *dosage, uint32_t n_cov, const double *covariates, uint32_t window,
+                                     uint32_t n_perm, const uint16_t *perm, double p_threshold, uint32_t max_signals,
+                                     rgx_qtl_indep_result **out, char *err, size_t errlen);
+void rgx_cohort_qtl_indep_free(rgx_qtl_indep_result *q);
+/* rgx_cohort_format_qtl_perm's columns, then "\trank\tn_cond", and one line per kept signal in (row, rank) order: num_var = n_cis, doubles as
+ * %.17g, NaN as "nan".  q == NULL writes the header line alone; 0 when the arguments do not fit together.  Buffer protocol of
+ * rgx_cohort_format_counts. */
+size_t rgx_cohort_format_qtl_indep(const rgx_cohort_matrix *m, const rgx_cohort_clusters *cl, const rgx_pheno_table *ph,
+                                   const rgx_qtl_indep_result *q, const uint32_t *var_pos, const char *const *variant_id, char *buf, size_t cap);
+
+/* -----------------------------------------------------------------------------------------------------
  * The trans-sQTL scan of the phenotype table: every table row against every usable variant, genome-wide, keeping only the pairs whose |r| reaches
  * a threshold -- tensorQTL's map_trans, which is not available to this project: checked against a restatement in exact rationals.
  *   input                 everything rgx_cohort_qtl_nominal takes except window, with the same errors; r_min in [0, 1] (NaN or a value outside

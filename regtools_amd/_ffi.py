@@ -65,6 +65,8 @@ EXPORTS = ["rgx_extract_params_default", "rgx_ctx_create", "rgx_ctx_destroy", "r
            "rgx_qtl_trigamma", "rgx_qtl_betainc", "rgx_qtl_beta_fit", "rgx_cohort_format_qtl_perm",
            "rgx_cohort_pheno_groups", "rgx_cohort_qtl_permute_grouped", "rgx_cohort_qtl_permute_grouped_host", "rgx_cohort_qtl_group_free",
            "rgx_cohort_format_qtl_group",
+           "rgx_cohort_qtl_permute_conditional", "rgx_cohort_qtl_permute_conditional_host", "rgx_cohort_qtl_cond_free",
+           "rgx_cohort_qtl_independent", "rgx_cohort_qtl_independent_host", "rgx_cohort_qtl_indep_free", "rgx_cohort_format_qtl_indep",
            "rgx_cohort_qtl_trans", "rgx_cohort_qtl_trans_host", "rgx_cohort_qtl_trans_free", "rgx_qtl_r_threshold", "rgx_cohort_format_qtl_trans",
            "rgx_gtf_bin_index", "rgx_k_junction_scan", "rgx_junction_items_free", "rgx_pair_list_free", "rgx_k_window_pairs", "rgx_k_assoc_pairs"]
 
@@ -167,6 +169,34 @@ class QtlGroupResult(C.Structure):
                 ("beta_shape2", C.POINTER(C.c_double)), ("p_beta", C.POINTER(C.c_double)), ("beta_status", C.POINTER(C.c_uint8)),
                 ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_tiles", C.c_uint64),
                 ("ms_perm", C.c_double), ("ms_residual", C.c_double), ("ms_products", C.c_double), ("ms_beta", C.c_double)]
+
+
+class QtlCondResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("n_perm", C.c_uint32),
+                ("n_series", C.c_uint32), ("n_cond", C.c_uint32), ("n_pairs", C.c_uint64), ("variant_verdict", C.POINTER(C.c_uint8)),
+                ("yy", C.POINTER(C.c_double)), ("gg", C.POINTER(C.c_double)), ("series_row", C.POINTER(C.c_uint32)),
+                ("cond_begin", C.POINTER(C.c_uint32)), ("cond_variant", C.POINTER(C.c_uint32)), ("cond_status", C.POINTER(C.c_uint8)),
+                ("yy_cond", C.POINTER(C.c_double)), ("dof", C.POINTER(C.c_uint32)), ("n_window", C.POINTER(C.c_uint32)),
+                ("n_cis", C.POINTER(C.c_uint32)), ("perm_r", C.POINTER(C.c_double)), ("best_variant", C.POINTER(C.c_uint32)),
+                ("best_r", C.POINTER(C.c_double)), ("best_slope", C.POINTER(C.c_double)), ("n_ge", C.POINTER(C.c_uint32)),
+                ("p_perm", C.POINTER(C.c_double)), ("beta_shape1", C.POINTER(C.c_double)), ("beta_shape2", C.POINTER(C.c_double)),
+                ("p_beta", C.POINTER(C.c_double)), ("beta_status", C.POINTER(C.c_uint8)),
+                ("n_constant", C.c_uint64), ("n_explained", C.c_uint64), ("n_flat_rows", C.c_uint64), ("n_collinear", C.c_uint64),
+                ("n_flat_series", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("ms_cond", C.c_double), ("ms_residual", C.c_double), ("ms_prepare", C.c_double), ("ms_products", C.c_double),
+                ("ms_beta", C.c_double)]
+
+
+class QtlIndepResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint32), ("n_variants", C.c_uint32), ("n_cov", C.c_uint32), ("n_perm", C.c_uint32),
+                ("max_signals", C.c_uint32), ("p_threshold", C.c_double), ("n_signals", C.c_uint64), ("sig_begin", C.POINTER(C.c_uint32)),
+                ("capped", C.POINTER(C.c_uint8)), ("variant", C.POINTER(C.c_uint32)), ("rank", C.POINTER(C.c_uint32)),
+                ("n_cond", C.POINTER(C.c_uint32)), ("dof", C.POINTER(C.c_uint32)), ("n_cis", C.POINTER(C.c_uint32)),
+                ("r", C.POINTER(C.c_double)), ("slope", C.POINTER(C.c_double)), ("p_perm", C.POINTER(C.c_double)),
+                ("beta_shape1", C.POINTER(C.c_double)), ("beta_shape2", C.POINTER(C.c_double)), ("p_beta", C.POINTER(C.c_double)),
+                ("beta_status", C.POINTER(C.c_uint8)),
+                ("n_entered", C.c_uint64), ("n_forward_rounds", C.c_uint32), ("n_series_total", C.c_uint64), ("n_capped", C.c_uint64),
+                ("ms_indep", C.c_double), ("ms_round0", C.c_double), ("ms_forward", C.c_double), ("ms_backward", C.c_double)]
 
 
 class IdentifyParams(C.Structure):
@@ -389,6 +419,17 @@ def lib():
         L.rgx_cohort_qtl_permute_grouped.argtypes = [C.c_void_p] + group_in
         L.rgx_cohort_qtl_permute_grouped_host.argtypes = group_in
         L.rgx_cohort_qtl_group_free.argtypes = [P(QtlGroupResult)]
+        cond_in = perm_in[:11] + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(P(QtlCondResult)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_permute_conditional.argtypes = [C.c_void_p] + cond_in
+        L.rgx_cohort_qtl_permute_conditional_host.argtypes = cond_in
+        L.rgx_cohort_qtl_cond_free.argtypes = [P(QtlCondResult)]
+        indep_in = perm_in[:11] + [C.c_double, C.c_uint32, P(P(QtlIndepResult)), C.c_char_p, C.c_size_t]
+        L.rgx_cohort_qtl_independent.argtypes = [C.c_void_p] + indep_in
+        L.rgx_cohort_qtl_independent_host.argtypes = indep_in
+        L.rgx_cohort_qtl_indep_free.argtypes = [P(QtlIndepResult)]
+        L.rgx_cohort_format_qtl_indep.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlIndepResult), C.c_void_p, P(C.c_char_p),
+                                                  C.c_char_p, C.c_size_t]
+        L.rgx_cohort_format_qtl_indep.restype = C.c_size_t
         L.rgx_cohort_pheno_groups.argtypes = [P(CohortClusters), P(PhenoTable), C.c_void_p, P(C.c_uint32), C.c_char_p, C.c_size_t]
         L.rgx_cohort_format_qtl_group.argtypes = [P(CohortMatrix), P(CohortClusters), P(PhenoTable), P(QtlGroupResult), C.c_void_p, P(C.c_char_p),
                                                   C.c_char_p, C.c_size_t]

@@ -405,7 +405,8 @@ def qtl_beta_fit(p):
     return status, s1.value, s2.value
 
 
-def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms, groups=None, n_groups=None):
+def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed, perms, groups=None, n_groups=None,
+                   series=None, indep=None):
     import numpy as np
     S = ph.n_samples
     reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1, 3)
@@ -428,6 +429,14 @@ def _qtl_perm_call(fn, front, ph, regions, var_tid, var_pos, dosage, covariates,
             raise ValueError("perms needs the identity as its row 0")
     shared = front + (ph._h, reg.ctypes.data, len(tid), tid.ctypes.data, pos.ctypes.data, dos.ctypes.data, len(cov), cov.ctypes.data, int(window),
                       n_perm, pm.ctypes.data)
+    if indep is not None:
+        return _call(fn, _ffi.QtlIndepResult, CohortQTLIndep, *(shared + (float(indep[0]), int(indep[1]))))
+    if series is not None:
+        rows, begin, var = (np.ascontiguousarray(x, dtype=np.uint32) for x in series)
+        if rows.ndim != 1 or begin.shape != (len(rows) + 1,) or var.ndim != 1 or (len(begin) and len(var) < int(begin.max())):
+            raise ValueError("series_row (N), cond_begin (N + 1) and the cond_variant it indexes")
+        pad = var if len(var) else np.zeros(1, np.uint32)                # (an empty list still has an address)
+        return _call(fn, _ffi.QtlCondResult, CohortQTLCond, *(shared + (len(rows), rows.ctypes.data, begin.ctypes.data, pad.ctypes.data)))
     if groups is not None:
         grp = np.ascontiguousarray(groups, dtype=np.uint32)
         if grp.shape != (ph.n_rows,):
@@ -501,6 +510,96 @@ def qtl_permute_grouped_host(ph, regions, groups, n_groups, var_tid, var_pos, do
     row its group in [0, n_groups) or CohortQTLGroup.NO_GROUP; the other arguments are qtl_permute_host's."""
     return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_grouped_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
                           seed, perms, groups, n_groups)
+
+
+class CohortQTLCond(_Owned):
+    """rgx_qtl_cond_result: the conditional permutation pass -- per variant its verdict and gg, per row yy, the series' lists echoed (series_row,
+    cond_begin from 0, cond_variant), and per series cond_status (0, 1 collinear, 2 flat), yy_cond, dof, n_window (the row's usable cis variants),
+    n_cis (those that take part), perm_r (N x (B + 1)), the best pair of the identity (best_variant, an input variant or NO_PAIR; best_r,
+    best_slope), n_ge, p_perm and the beta approximation.  The array attributes are numpy VIEWS of memory this object owns."""
+    NO_PAIR = 0xffffffff
+    MAX_COND = 8
+    _free = "rgx_cohort_qtl_cond_free"
+
+    def __init__(self, handle):
+        import numpy as np
+        _Owned.__init__(self, handle)
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.n_perm, self.n_series, self.n_cond, self.n_pairs = int(p.n_cov), int(p.n_perm), int(p.n_series), int(p.n_cond), int(p.n_pairs)
+        self.n_constant, self.n_explained, self.n_flat_rows = int(p.n_constant), int(p.n_explained), int(p.n_flat_rows)
+        self.n_collinear, self.n_flat_series, self.n_tiles = int(p.n_collinear), int(p.n_flat_series), int(p.n_tiles)
+        self.ms_cond, self.ms_residual, self.ms_prepare, self.ms_products, self.ms_beta = (p.ms_cond, p.ms_residual, p.ms_prepare, p.ms_products,
+                                                                                            p.ms_beta)
+        view = self._view
+        K, V, N, B1 = self.n_rows, self.n_variants, self.n_series, self.n_perm + 1
+        self.variant_verdict = view(p.variant_verdict, V, np.uint8)
+        self.yy, self.gg = view(p.yy, K, np.float64), view(p.gg, V, np.float64)
+        self.series_row, self.cond_begin = view(p.series_row, N, np.uint32), view(p.cond_begin, N + 1, np.uint32)
+        self.cond_variant, self.cond_status = view(p.cond_variant, self.n_cond, np.uint32), view(p.cond_status, N, np.uint8)
+        self.yy_cond, self.dof = view(p.yy_cond, N, np.float64), view(p.dof, N, np.uint32)
+        self.n_window, self.n_cis = view(p.n_window, N, np.uint32), view(p.n_cis, N, np.uint32)
+        self.perm_r = view(p.perm_r, N * B1, np.float64).reshape(N, B1)
+        self.best_variant, self.best_r, self.best_slope = (view(p.best_variant, N, np.uint32), view(p.best_r, N, np.float64),
+                                                           view(p.best_slope, N, np.float64))
+        self.n_ge, self.p_perm = view(p.n_ge, N, np.uint32), view(p.p_perm, N, np.float64)
+        self.beta_shape1, self.beta_shape2 = view(p.beta_shape1, N, np.float64), view(p.beta_shape2, N, np.float64)
+        self.p_beta, self.beta_status = view(p.p_beta, N, np.float64), view(p.beta_status, N, np.uint8)
+
+
+def qtl_series(sets):
+    """(series_row, cond_begin, cond_variant) of a list of (row, [variants]) pairs, as the conditional pass takes them."""
+    import numpy as np
+    rows = np.array([k for k, _ in sets], np.uint32)
+    begin = np.concatenate([[0], np.cumsum([len(v) for _, v in sets])]).astype(np.uint32)
+    var = np.array([x for _, v in sets for x in v], np.uint32)
+    return rows, begin, var
+
+
+def qtl_permute_conditional_host(ph, regions, series_row, cond_begin, cond_variant, var_tid, var_pos, dosage, covariates=None, window=100000,
+                                 n_perm=1000, seed=0, perms=None):
+    """rgx_cohort_qtl_permute_conditional_host: the conditional permutation pass by the library's plain C++ twin, no device involved.  Series c
+    is table row series_row[c] conditioned on cond_variant[cond_begin[c]:cond_begin[c + 1]] (qtl_series builds the three); the other arguments are
+    qtl_permute_host's."""
+    return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_permute_conditional_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
+                          seed, perms, series=(series_row, cond_begin, cond_variant))
+
+
+class CohortQTLIndep(_Owned):
+    """rgx_qtl_indep_result: the conditionally independent signals of every table row, CSR by row (sig_begin, K + 1) in (row, rank) order -- per
+    signal variant, rank (its place in the row's forward order), n_cond, dof, n_cis, r, slope, p_perm, beta_shape1, beta_shape2, p_beta,
+    beta_status -- and per row capped.  The array attributes are numpy VIEWS of memory this object owns."""
+    _free = "rgx_cohort_qtl_indep_free"
+
+    def __init__(self, handle):
+        import numpy as np
+        _Owned.__init__(self, handle)
+        p = handle.contents
+        self.n_rows, self.n_samples, self.n_variants = int(p.n_rows), int(p.n_samples), int(p.n_variants)
+        self.n_cov, self.n_perm, self.max_signals, self.p_threshold = int(p.n_cov), int(p.n_perm), int(p.max_signals), p.p_threshold
+        self.n_signals, self.n_entered, self.n_forward_rounds = int(p.n_signals), int(p.n_entered), int(p.n_forward_rounds)
+        self.n_series_total, self.n_capped = int(p.n_series_total), int(p.n_capped)
+        self.ms_indep, self.ms_round0, self.ms_forward, self.ms_backward = p.ms_indep, p.ms_round0, p.ms_forward, p.ms_backward
+        view = self._view
+        K, n = self.n_rows, self.n_signals
+        self.sig_begin, self.capped = view(p.sig_begin, K + 1, np.uint32), view(p.capped, K, np.uint8)
+        self.variant, self.rank, self.n_cond = view(p.variant, n, np.uint32), view(p.rank, n, np.uint32), view(p.n_cond, n, np.uint32)
+        self.dof, self.n_cis = view(p.dof, n, np.uint32), view(p.n_cis, n, np.uint32)
+        self.r, self.slope, self.p_perm = view(p.r, n, np.float64), view(p.slope, n, np.float64), view(p.p_perm, n, np.float64)
+        self.beta_shape1, self.beta_shape2 = view(p.beta_shape1, n, np.float64), view(p.beta_shape2, n, np.float64)
+        self.p_beta, self.beta_status = view(p.p_beta, n, np.float64), view(p.beta_status, n, np.uint8)
+
+    def text(self, matrix, clusters, ph, var_pos, variant_ids):
+        """One line per kept signal in (row, rank) order: CohortQTLPerm.text's columns, then rank and n_cond."""
+        return _qtl_text(self._lib.rgx_cohort_format_qtl_indep, self, matrix, clusters, ph, var_pos, variant_ids)
+
+
+def qtl_independent_host(ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0, perms=None, p_threshold=0.05,
+                         max_signals=8):
+    """rgx_cohort_qtl_independent_host: the forward-backward search for conditionally independent signals by the library's host twins, no device
+    involved.  The arguments are qtl_permute_host's, then the threshold of p_beta and the most signals a row takes (1 to 8)."""
+    return _qtl_perm_call(_ffi.lib().rgx_cohort_qtl_independent_host, (), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm, seed,
+                          perms, indep=(p_threshold, max_signals))
 
 
 class CohortQTLTrans(_Owned):
@@ -693,6 +792,22 @@ class Cohort(object):
         of the identity, and on the host the empirical p and its beta approximation.  The arguments are qtl_permute_grouped_host's."""
         return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute_grouped, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window,
                               n_perm, seed, perms, groups, n_groups)
+
+    def qtl_permute_conditional(self, ph, regions, series_row, cond_begin, cond_variant, var_tid, var_pos, dosage, covariates=None, window=100000,
+                                n_perm=1000, seed=0, perms=None):
+        """The conditional permutation pass on this cohort's device (rgx_cohort_qtl_permute_conditional): the permutation pass of table row
+        series_row[c] with the variants cond_variant[cond_begin[c]:cond_begin[c + 1]] in the model, per series.  Returns a CohortQTLCond; the
+        arguments are qtl_permute_conditional_host's."""
+        return _qtl_perm_call(self._lib.rgx_cohort_qtl_permute_conditional, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window,
+                              n_perm, seed, perms, series=(series_row, cond_begin, cond_variant))
+
+    def qtl_independent(self, ph, regions, var_tid, var_pos, dosage, covariates=None, window=100000, n_perm=1000, seed=0, perms=None,
+                        p_threshold=0.05, max_signals=8):
+        """The conditionally independent signals of every row on this cohort's device (rgx_cohort_qtl_independent): round 0 is the permutation
+        pass, every further round one conditional pass behind the same preparation.  Returns a CohortQTLIndep; the arguments are
+        qtl_independent_host's."""
+        return _qtl_perm_call(self._lib.rgx_cohort_qtl_independent, (self._h,), ph, regions, var_tid, var_pos, dosage, covariates, window, n_perm,
+                              seed, perms, indep=(p_threshold, max_signals))
 
     def qtl_trans(self, ph, regions, var_tid, var_pos, dosage, covariates=None, r_min=None, pval=1e-5, exclude_window=5000000, max_hits=0):
         """The trans-sQTL scan on this cohort's device (rgx_cohort_qtl_trans): every row against every usable variant, only the pairs whose |r|

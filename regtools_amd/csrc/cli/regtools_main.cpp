@@ -274,15 +274,19 @@ void cohort_usage(std::ostream &out) {
         << "\t\t-Q FILE\tThe nominal cis-sQTL scan: every row of the -q table against every variant of -g within the window around its intron,\n"
         << "\t\t\t with an intercept and the first -C components (at most the samples less three) in the model: one line per pair with\n"
         << "\t\t\t r, slope, its standard error, t and the two-sided p. The table and the components are computed as for -q and -P.\n"
-        << "\t\t-w INT\tThe cis window of -Q and -R on either side of the intron. [100000]\n"
+        << "\t\t-w INT\tThe cis window of -Q, -R, -G and -I on either side of the intron. [100000]\n"
         << "\t\t-R FILE\tThe permutation pass of the cis-sQTL scan: one line per row of the -q table that has variants of -g in its window, with its\n"
         << "\t\t\t best variant, the empirical p of that variant's |r| among -B permutations of the samples and its beta approximation.\n"
         << "\t\t\t Needs -g; the table, the components and the window are those of -Q, beside which it may stand.\n"
         << "\t\t-G FILE\tThe grouped permutation pass: one line per cluster of the -q table whose introns have variants of -g in their windows, with\n"
         << "\t\t\t the cluster's best (intron, variant) and the empirical p and beta approximation of the largest |r| over ALL its introns.\n"
         << "\t\t\t Needs -g; everything else as for -R, beside which (and beside -Q) it may stand.\n"
-        << "\t\t-B INT\tThe permutations of -R and -G, 1 to 65535. [1000]\n"
-        << "\t\t-e INT\tThe seed of -R's and -G's permutations. [0]\n"
+        << "\t\t-I FILE\tThe conditionally independent signals: every row of the -q table whose corrected p of -R is at most -F is searched for\n"
+        << "\t\t\t further variants of its window that act beside those already found, forward and then backward: one line per signal, -R's\n"
+        << "\t\t\t columns, then its rank and the number of variants it is conditioned on. Needs -g; everything else as for -R.\n"
+        << "\t\t-F FLOAT\tThe threshold of -I on the beta-approximated p, above 0 and at most 1. [0.05]\n"
+        << "\t\t-B INT\tThe permutations of -R, -G and -I, 1 to 65535. [1000]\n"
+        << "\t\t-e INT\tThe seed of -R's, -G's and -I's permutations. [0]\n"
         << "\t\t-X FILE\tThe trans-sQTL scan: every row of the -q table against EVERY variant of -g, with the model of -Q: one line per pair whose\n"
         << "\t\t\t two-sided p is at most -u, with r, slope, its standard error, t and p. Needs -g; the table and the components are those of -Q.\n"
         << "\t\t-u FLOAT\tThe p-value threshold of -X, above 0 and at most 1. [1e-5]\n"
@@ -355,8 +359,8 @@ int junctions_cohort(int argc, char **argv) {
         std::string counts = "NA", clusters = "NA", phenotypes = "NA", components = "NA", genotypes = "NA", qtl = "NA", perm = "NA", grouped = "NA";
         uint32_t n_components = 10, window = 100000, n_perm = 1000;
         uint64_t seed = 0;
-        std::string trans = "NA";
-        double trans_pval = 1e-5;
+        std::string trans = "NA", indep = "NA";
+        double trans_pval = 1e-5, indep_pval = 0.05;
         bool trans_exclude = true;
         uint32_t trans_window = 5000000;
         rgx_pheno_params qp;
@@ -371,7 +375,7 @@ int junctions_cohort(int argc, char **argv) {
         std::vector<CohortInput> in;
         optind = 1;
         int c;
-        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:G:X:u:W:")) != -1) {
+        while ((c = getopt(argc, argv, "ha:m:M:r:s:t:o:c:An:N:L:k:K:T:l:J:p:q:x:d:P:C:g:Q:w:R:B:e:G:X:u:W:I:F:")) != -1) {
             switch (c) {
                 case 'h': cohort_usage(std::cout); return 0;
                 case 'a': o.min_anchor = (uint32_t)atoi(optarg); break;
@@ -408,10 +412,12 @@ int junctions_cohort(int argc, char **argv) {
                 case 'R': perm = optarg; break;
                 case 'G': grouped = optarg; break;
                 case 'X': trans = optarg; break;
-                case 'u': {
+                case 'I': indep = optarg; break;
+                case 'u': case 'F': {
                     char *end = nullptr;
-                    trans_pval = strtod(optarg, &end);
-                    if (end == optarg || *end || !(trans_pval > 0 && trans_pval <= 1)) throw std::runtime_error("Unrecognized threshold argument!\n\n");
+                    double &pval = c == 'u' ? trans_pval : indep_pval;
+                    pval = strtod(optarg, &end);
+                    if (end == optarg || *end || !(pval > 0 && pval <= 1)) throw std::runtime_error("Unrecognized threshold argument!\n\n");
                     break;
                 }
                 case 'W': {
@@ -488,7 +494,7 @@ int junctions_cohort(int argc, char **argv) {
         for (; optind < argc; ++optind) { CohortInput ci; ci.path = argv[optind]; in.push_back(ci); }
         if (in.empty()) { cohort_usage(std::cerr); throw std::runtime_error("Error parsing inputs!(2)\n\n"); }
         if (o.strandness == -1) { cohort_usage(std::cerr); throw std::runtime_error("Please supply strandness mode with '-s' option!\n\n"); }
-        if ((qtl != "NA" || perm != "NA" || grouped != "NA" || trans != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
+        if ((qtl != "NA" || perm != "NA" || grouped != "NA" || trans != "NA" || indep != "NA") && genotypes == "NA") { cohort_usage(std::cerr); throw std::runtime_error("Please supply the genotypes with '-g' option!\n\n"); }
         for (CohortInput &ci : in) if (ci.name.empty()) ci.name = cohort_default_name(ci.path);
         for (size_t a = 0; a < in.size(); ++a) for (size_t b = 0; b < a; ++b) if (in[a].name == in[b].name)
             throw std::runtime_error("Two samples are named " + in[a].name + " (" + in[b].path + ", " + in[a].path + "); name them in a list (-L)\n\n");
@@ -536,7 +542,7 @@ int junctions_cohort(int argc, char **argv) {
         rgx_cohort_clusters *cl = nullptr;                  // (straight behind the finish: the matrix is still in HBM)
         rp.min_rows = kp.min_rows; rp.min_total = kp.min_total;
         const bool want_qtl = qtl != "NA", want_perm = perm != "NA", want_group = grouped != "NA", want_trans = trans != "NA",
-                   want_scan = want_qtl || want_perm || want_group || want_trans;
+                   want_indep = indep != "NA", want_scan = want_qtl || want_perm || want_group || want_trans || want_indep;
         const bool want_pheno = phenotypes != "NA" || components != "NA" || want_scan;
         if (ok && (clusters != "NA" || want_pheno) && (refine ? rgx_cohort_refine(co, m, &rp, &cl, err, sizeof err) : rgx_cohort_cluster(co, m, &kp, &cl, err, sizeof err)) != RGX_OK) {
             failure = err; ok = false; }
@@ -556,12 +562,13 @@ int junctions_cohort(int argc, char **argv) {
         rgx_qtl_perm_result *pr = nullptr;
         rgx_qtl_group_result *gr = nullptr;
         rgx_qtl_trans_result *tr = nullptr;
+        rgx_qtl_indep_result *ir = nullptr;
         if (ok && want_scan && ph->n_rows) {
             std::vector<rgx_qtl_region> regions((size_t)ph->n_rows);
             int rc = rgx_cohort_pheno_regions(m, ph, regions.data(), err, sizeof err);
             if (rc == RGX_OK && want_qtl) rc = rgx_cohort_qtl_nominal(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
                                                                       pcs ? pcs->component : nullptr, window, &qr, err, sizeof err);
-            if (rc == RGX_OK && (want_perm || want_group)) {
+            if (rc == RGX_OK && (want_perm || want_group || want_indep)) {
                 std::vector<uint16_t> perms(((size_t)n_perm + 1) * ph->n_samples);
                 rc = rgx_qtl_permutations(ph->n_samples, n_perm, seed, perms.data(), err, sizeof err);
                 if (rc == RGX_OK && want_perm) rc = rgx_cohort_qtl_permute(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
@@ -574,6 +581,8 @@ int junctions_cohort(int argc, char **argv) {
                                                                           pcs ? pcs->component : nullptr, window, n_perm, perms.data(), n_groups,
                                                                           group.data(), &gr, err, sizeof err);
                 }
+                if (rc == RGX_OK && want_indep) rc = rgx_cohort_qtl_independent(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage,
+                    n_cov, pcs ? pcs->component : nullptr, window, n_perm, perms.data(), indep_pval, RGX_QTL_MAX_COND, &ir, err, sizeof err);
             }
             // -X: the p-value threshold becomes the smallest |r| kept (too few samples for a degree of freedom: the call says so)
             if (rc == RGX_OK && want_trans) rc = rgx_cohort_qtl_trans(co, ph, regions.data(), gt->n_variants, gt->tid, gt->pos, gt->dosage, n_cov,
@@ -582,6 +591,7 @@ int junctions_cohort(int argc, char **argv) {
             if (rc != RGX_OK) { failure = err; ok = false; }
         }
         if (!ok) {
+            rgx_cohort_qtl_indep_free(ir);
             rgx_cohort_qtl_trans_free(tr);
             rgx_cohort_qtl_group_free(gr);
             rgx_cohort_qtl_perm_free(pr);
@@ -627,6 +637,10 @@ int junctions_cohort(int argc, char **argv) {
         if (want_trans) {
             nx = rgx_cohort_format_qtl_trans(m, cl, ph, tr, gt->pos, gt->id, nullptr, 0); xtx.reset(new char[nx + 1]);
             rgx_cohort_format_qtl_trans(m, cl, ph, tr, gt->pos, gt->id, xtx.get(), nx); }
+        size_t ni = 0; std::unique_ptr<char[]> itx;
+        if (want_indep) {
+            ni = rgx_cohort_format_qtl_indep(m, cl, ph, ir, gt->pos, gt->id, nullptr, 0); itx.reset(new char[ni + 1]);
+            rgx_cohort_format_qtl_indep(m, cl, ph, ir, gt->pos, gt->id, itx.get(), ni); }
         bool short_write = false;
         FILE *f = o.output == "NA" ? stdout : fopen(o.output.c_str(), "w");
         if (!f) throw std::runtime_error("Unable to write " + o.output + "\n\n");
@@ -670,6 +684,11 @@ int junctions_cohort(int argc, char **argv) {
             FILE *g = fopen(trans.c_str(), "w");
             if (!g) throw std::runtime_error("Unable to write " + trans + "\n\n");
             short_write |= fwrite(xtx.get(), 1, nx, g) != nx; short_write |= fclose(g) != 0;
+        }
+        if (want_indep) {
+            FILE *g = fopen(indep.c_str(), "w");
+            if (!g) throw std::runtime_error("Unable to write " + indep + "\n\n");
+            short_write |= fwrite(itx.get(), 1, ni, g) != ni; short_write |= fclose(g) != 0;
         }
         if (short_write) { fprintf(stderr, "regtools-amd: writing the output failed (%s)\n", strerror(errno)); fflush(stderr); _exit(1); }
         if (getenv("REGTOOLS_AMD_STATS"))
@@ -716,6 +735,11 @@ int junctions_cohort(int argc, char **argv) {
                     trans_exclude ? std::to_string(trans_window).c_str() : "off", gt->n_variants, n_cov, (unsigned long long)(tr ? tr->n_tested : 0),
                     (unsigned long long)(tr ? tr->n_hits : 0), (unsigned long long)(tr ? tr->n_tiles : 0), (unsigned long long)(tr ? tr->n_hit_tiles : 0),
                     tr ? tr->ms_trans : 0.0, tr ? tr->ms_residual : 0.0, tr ? tr->ms_count : 0.0, tr ? tr->ms_emit : 0.0);
+        if (want_indep && getenv("REGTOOLS_AMD_STATS"))
+            fprintf(stderr, "[regtools_amd] indep: %llu rows entered, %u forward rounds, %llu conditional series, %llu signals written\n",
+                    (unsigned long long)(ir ? ir->n_entered : 0), ir ? ir->n_forward_rounds : 0u, (unsigned long long)(ir ? ir->n_series_total : 0),
+                    (unsigned long long)(ir ? ir->n_signals : 0));
+        rgx_cohort_qtl_indep_free(ir);
         rgx_cohort_qtl_trans_free(tr);
         rgx_cohort_qtl_group_free(gr);
         rgx_cohort_qtl_perm_free(pr);

@@ -77,7 +77,7 @@ extern "C" void rgx_cohort_destroy(rgx_cohort *co) {
     co->cl_in.release(); co->cl_rows.release(); co->cl_entries.release();
     co->ph_in.release(); co->ph_rows.release(); co->ph_entries.release();
     co->pc_in.release(); co->pc_part.release(); co->pc_out.release();
-    co->qt_in.release(); co->qt_rows.release(); co->qt_t.release(); co->qt_out.release(); co->qp_in.release(); co->qp_out.release(); co->qx_tiles.release();
+    co->qt_in.release(); co->qt_rows.release(); co->qt_t.release(); co->qt_out.release(); co->qp_in.release(); co->qp_out.release(); co->qx_tiles.release(); co->qc_in.release(); co->qc_ws.release();
     if (co->pinned_up) { if (co->pinned_up_locked) (void)hipHostFree(co->pinned_up); else free(co->pinned_up); }
     if (co->ev_src) (void)hipEventDestroy(co->ev_src);
     if (co->ev_done) (void)hipEventDestroy(co->ev_done);

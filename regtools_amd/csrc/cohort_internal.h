@@ -124,6 +124,8 @@ struct rgx_cohort {
     DevBuf qp_in, qp_out;
     // rgx_cohort_qtl_trans (cohort_qtl_trans.cpp): the per-tile words
     DevBuf qx_tiles;
+    // rgx_cohort_qtl_permute_conditional (cohort_qtl_cond.cpp): the series' lists; the bases, rows, betas and the result's arrays
+    DevBuf qc_in, qc_ws;
 };
 
 // What every device run of a cohort call (ClusterRun, PhenoRun, PcsRun, the sQTL runs behind QtlPrep: qtl_run.h) is made of.  The caller holds the

@@ -10,8 +10,6 @@
 
 #include <cmath>
 
-namespace {
-
 rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, uint32_t B, bool pinned) {
     rgx_qtl_perm_result *q = result_alloc<rgx_qtl_perm_result>(pinned, [&](rgx_qtl_perm_result &r, BlockTake &take) {
         take(r.yy, K); take(r.gg, V); take(r.perm_r, K * ((size_t)B + 1)); take(r.best_r, K); take(r.best_slope, K); take(r.p_perm, K);
@@ -21,8 +19,6 @@ rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_c
     if (q) { qtl_result_head(q, K, S, V, n_cov); q->n_perm = B; }
     return q;
 }
-
-}  // namespace
 
 // what the host can judge of the permutations, the same for the device and the twin; n_series of `series` (rows, groups) get B + 1 values each
 int check_perm(uint64_t n_series, const char *series, uint32_t S, uint32_t B, const uint16_t *perm, char *err, size_t errlen) {
@@ -77,6 +73,8 @@ void qtl_series_products(const QtlHost &h, uint32_t S, uint32_t B, const uint16_
     memcpy(series, top.data(), ((size_t)B + 1) * 8);
 }
 
+static const char *const kNoPermMemory = "regtools_amd: no device memory for %u permutations of %u %s\n";
+
 template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen) {
     const Series sr = series_of(q);
     const uint64_t N = sr.n; const uint32_t B = q->n_perm, dof = q->dof;
@@ -109,29 +107,34 @@ template <class R> int perm_finish(R *q, bool device, char *err, size_t errlen) 
 template int perm_finish(rgx_qtl_perm_result *, bool, char *, size_t);
 template int perm_finish(rgx_qtl_group_result *, bool, char *, size_t);
 
-int PermRun::products() {
+int PermRun::stage_perms() {
     const uint32_t N = n_series;
     if ((uint64_t)N * (ldp / kQtlTile) > 0x7fffffffull) return fail(err, errlen, RGX_ERR_ARG,
         "regtools_amd: %u %s x %zu blocks of 64 permutations are more than 2^31 - 1 workgroups\n", N, series, ldp / kQtlTile);
     try { permT.assign((size_t)S * ldp, 0); }
     catch (const std::bad_alloc &) { return fail(err, errlen, RGX_ERR_ARG, "regtools_amd: no memory for %u permutations of %u samples\n", B, S); }
     for (uint32_t b = 0; b <= B; ++b) for (uint32_t s = 0; s < S; ++s) permT[(size_t)s * ldp + b] = perm[(size_t)b * S + s];
-    const size_t n_out = (size_t)N * ((size_t)B + 1), n_begin = mem ? (size_t)N + 1 : 0, n_mem = mem ? mem->row.size() : 0;
-    const char *no_memory = "regtools_amd: no device memory for %u permutations of %u %s\n";
-    if (int rc = grow(co->qp_in, permT.size() * 2 + (n_begin + n_mem) * 4 + 256, no_memory, B, N, series)) return rc;
-    if (int rc = grow(co->qp_out, n_out * 8 + (size_t)N * (mem ? 28 : 24) + 256, no_memory, B, N, series)) return rc;
+    const size_t n_begin = mem ? (size_t)N + 1 : 0, n_mem = mem ? mem->row.size() : 0;
+    if (int rc = grow(co->qp_in, permT.size() * 2 + (n_begin + n_mem) * 4 + 256, kNoPermMemory, B, N, series)) return rc;
     Carve in(co->qp_in);
     d_permT = in.take<uint16_t>(permT.size());
     if (mem) { d_begin = in.u32(n_begin); d_row = in.u32(n_mem); }
     CARVE_TRY(in, mem ? "grouped sQTL permutation" : "sQTL permutation");
-    Carve o(co->qp_out);
-    perm_r = o.take<double>(n_out); best_r = o.take<double>(N); best_slope = o.take<double>(N); best_u = o.u32(N); best_variant = o.u32(N);
-    if (mem) best_row = o.u32(N);
-    CARVE_TRY(o, mem ? "grouped sQTL permutation result" : "sQTL permutation result");
     HIP_TRY(hipMemcpyAsync(d_permT, permT.data(), permT.size() * 2, hipMemcpyHostToDevice, st));
     if (mem) { HIP_TRY(hipMemcpyAsync(d_begin, mem->begin.data(), n_begin * 4, hipMemcpyHostToDevice, st)); }
     if (n_mem) { HIP_TRY(hipMemcpyAsync(d_row, mem->row.data(), n_mem * 4, hipMemcpyHostToDevice, st)); }
     mark(mem ? "members + permutations in HBM" : "permutations in HBM");
+    return RGX_OK;
+}
+
+int PermRun::series_products() {
+    const uint32_t N = n_series;
+    const size_t n_out = (size_t)N * ((size_t)B + 1);
+    if (int rc = grow(co->qp_out, n_out * 8 + (size_t)N * (mem ? 28 : 24) + 256, kNoPermMemory, B, N, series)) return rc;
+    Carve o(co->qp_out);
+    perm_r = o.take<double>(n_out); best_r = o.take<double>(N); best_slope = o.take<double>(N); best_u = o.u32(N); best_variant = o.u32(N);
+    if (mem) best_row = o.u32(N);
+    CARVE_TRY(o, mem ? "grouped sQTL permutation result" : "sQTL permutation result");
     HIP_TRY(ev_products.create());
     HIP_TRY(hipEventRecord(ev_products[0], st));
     // (without lists all three of d_begin, d_row and best_row are null: series g is table row g alone)

@@ -398,6 +398,26 @@ void launch_qtl_perm_best(const double *Y, const double *G, uint32_t n_series, u
                           const uint32_t *u_var, const double *yy, const double *gg, uint32_t *best_variant, double *best_r, double *best_slope,
                           hipStream_t st);
 
+// ---- the conditional cis-sQTL permutation pass (qtl_cond_kernels.hip; host side in cohort_qtl_cond.cpp) -------------------------------------------
+// What its kernels share.  N series: series_row (N), cond_begin (N + 1) and cond_variant, input variants; lo, count and u_var: the plan's; pb
+// (N + 1): the exclusive scan of count[series_row[c]], a series' places.  z: N x 8 x S unit vectors; yc (N x S), yyc and status per series; beta: 8
+// planes of cap doubles and ggc: cap doubles, per place; cap: at or above pb[N].
+struct QtlCond {
+    uint32_t N, S; const uint32_t *series_row, *cond_begin, *cond_variant, *lo, *count, *u_var, *pb;
+    double *z, *yc, *yyc, *beta, *ggc; uint8_t *status; size_t cap;
+};
+// cnt (N + 1 words, the last 0) = count[series_row[c]]
+void launch_qtl_cond_counts(const QtlCond &q, uint32_t *cnt, hipStream_t st);
+// z, yc, yyc and status per series, then beta and ggc per place.  Y, G: the row-major residuals; flag: one word, zeroed by the caller, raised for a
+// conditioning variant whose verdict is not 0
+void launch_qtl_cond_prepare(const QtlCond &q, const double *Y, const double *G, const uint8_t *verdict, uint32_t *flag, hipStream_t st);
+// perm_r (N x n_perm1) and best_u (N; all ones: none) as launch_qtl_perm writes them, over the places whose ggc is enough
+void launch_qtl_perm_cond(const QtlCond &q, const uint16_t *permT, size_t ldp, uint32_t n_perm1, const double *Gt, size_t ldg, double *perm_r,
+                          uint32_t *best_u, hipStream_t st);
+// the winning pair's chain and correction again; n_cis: the places that take part; n_window: count[series_row[c]]
+void launch_qtl_cond_best(const QtlCond &q, const double *G, const uint32_t *best_u, uint32_t *best_variant, double *best_r, double *best_slope,
+                          uint32_t *n_cis, uint32_t *n_window, hipStream_t st);
+
 // ---- the trans-sQTL scan (qtl_trans_kernels.hip; host side in cohort_qtl_trans.cpp) -----------------------------------------------------------------
 // What both product kernels read: the sample-major panels of launch_qtl_pairs, n_blocks x n_vt tiles of 64 rows x 64 usable variants (tile =
 // row block * n_vt + variant tile), the rows' regions (3 words each) and yy, the usable variants' keys and gg, their number on the device, and

@@ -11,6 +11,7 @@ constexpr uint32_t kQtlMaxSamples = kPcaMaxSamples;
 constexpr uint32_t kQtlTile = 64;            // the device's output tile (rows x usable variants); no part of the contract
 constexpr uint64_t kQtlMaxPairs = (1ull << 32) - (1ull << 16);
 constexpr uint64_t kQtlMaxTiles = 0x7fffffffull;
+constexpr uint32_t kQtlMaxCond = 8;          // RGX_QTL_MAX_COND: the most variants a conditional series is conditioned on
 constexpr uint32_t kQtlFlagDosage = 0, kQtlFlagRank = 1;     // the device's two flag words: a dosage outside the four values, a rank2 that is no rank
 
 // a step of a dot64 partial and of a pair's chain: one rounding
@@ -19,6 +20,9 @@ RGX_HD double qtl_fma(double a, double b, double acc) { return fma(a, b, acc); }
 RGX_HD double qtl_add(double a, double b) { RGX_FP_EXACT return a + b; }
 // x[s] behind the projection on a unit vector q with d = dot64(x, q)
 RGX_HD double qtl_project(double d, double q, double x) { return fma(-d, q, x); }
+
+// an entry of a unit vector of the conditional pass: v[s] / |v| with nn = dot64(v, v)
+RGX_HD double qtl_unit(double x, double nn) { RGX_FP_EXACT return x / sqrt(nn); }
 
 RGX_HD bool qtl_dosage_ok(int8_t d) { return d >= -1 && d <= 2; }
 RGX_HD double qtl_mean(uint32_t sum, uint32_t n_present) { RGX_FP_EXACT return (double)sum / (double)n_present; }

@@ -1,7 +1,7 @@
 // qtl_kernels.hip -- device half of the cohort's nominal cis-sQTL scan (rgx_cohort_qtl_nominal, cohort_qtl.cpp; contract in
 // include/regtools_amd.h; arithmetic in qtl_core.h, which the host twin runs too).  The reference has no counterpart.
 //   k_qtl_residual_pheno / _geno  a wave per table row / per variant: the vector sits in the wave's slice of LDS, where lane l alone touches the
-//                 entries s % 64 == l; dot64 is the lane's strided chain and a __shfl_down halving; the C projections run in order.  Written
+//                 entries s % 64 == l; dot64 is the lane's strided chain and a __shfl_down halving (qtl_tile.h); the C projections run in order.  Written
 //                 row-major, 512 contiguous bytes per wave and store.
 //   k_qtl_compact the usable variants side by side (their place: a scan of the usable flags): input index, (tid, pos) key, gg
 //   k_qtl_transpose  32 x 32 tiles through LDS: the row-major residuals to sample-major Yt[s][k] and Gt[s][u] (u: usable variants in order),
@@ -22,16 +22,6 @@ namespace rgx {
 
 namespace {
 
-__device__ __forceinline__ double qtl_halve(double p) {
-#pragma unroll
-    for (uint32_t off = 32; off; off >>= 1) p = qtl_add(p, __shfl_down(p, off, 64));
-    return __shfl(p, 0, 64);                                 // (lane 0 holds P[0]: every lane of the wave gets it)
-}
-__device__ __forceinline__ double qtl_dot64(const double *a, const double *b, uint32_t S, uint32_t l) {
-    double p = 0.0;
-    for (uint32_t s = l; s < S; s += 64) p = qtl_fma(a[s], b[s], p);
-    return qtl_halve(p);
-}
 // x (the wave's slice of LDS) -> its residual against the C unit vectors of Q, in place; returns ss
 __device__ __forceinline__ double qtl_residual(double *x, uint32_t S, const double *__restrict__ Q, uint32_t C, uint32_t l) {
     for (uint32_t j = 0; j < C; ++j) {

@@ -1,5 +1,5 @@
 // qtl_run.h -- what the four sQTL calls share: the nominal scan (cohort_qtl.cpp), the permutation pass (cohort_qtl_perm.cpp), the grouped pass
-// (cohort_qtl_group.cpp) and the trans scan (cohort_qtl_trans.cpp).  The arguments and their checks, the host half of the contract (the basis and
+// (cohort_qtl_group.cpp), the trans scan (cohort_qtl_trans.cpp) and the conditional pass with its forward-backward search (cohort_qtl_cond.cpp).  The arguments and their checks, the host half of the contract (the basis and
 // the twins' steps (1)-(6)) and QtlPrep, the device stages every call begins with, are defined in qtl_prep.cpp; the host's mathematics in
 // qtl_stats.cpp; what the permutation pass shares with the grouped pass, PermRun among it, in cohort_qtl_perm.cpp.  A run's base is CohortRun, the
 // results' blocks are result_block.h's, their copies back CopyBack's and their text text_out.h's (cohort_internal.h).
@@ -40,6 +40,9 @@ void qtl_series_finish(const double *row, uint32_t B, double best_r, uint32_t do
 // cis variants (+0.0 without pairs), and permutation 0's best pair, RGX_NO_PAIR and +0.0 without one.  best_row may be null.
 void qtl_series_products(const QtlHost &h, uint32_t S, uint32_t B, const uint16_t *perm, const uint32_t *rows, uint32_t n, double *series,
                          uint32_t *best_row, uint32_t &best_variant, double &best_r, double &best_slope);
+
+// the permutation pass's result with its head filled in (cohort_qtl_perm.cpp); null: no memory
+rgx_qtl_perm_result *perm_alloc(uint64_t K, uint32_t S, uint32_t V, uint32_t n_cov, uint32_t B, bool pinned);
 
 // The members of every group in ascending table row.
 struct Members { std::vector<uint32_t> begin, row; };
@@ -134,8 +137,12 @@ struct PermRun : QtlPrep {
           ldp(((size_t)B_ + 1 + kQtlTile - 1) / kQtlTile * kQtlTile), n_series(n_series_), series(series_), mem(mem_) {}
     // 1.-5. every stage up to the products and the best pairs, enqueued: no wait
     int launch() { int rc = prepare(); if (rc == RGX_OK) rc = plan_launch(); if (rc == RGX_OK) rc = products(); return rc; }
-    // 5. the member lists and the permutations sample-major in HBM, the products, the best pairs
-    int products();
+    // 5a. the member lists and the permutations sample-major in HBM (the conditional pass, cohort_qtl_cond.cpp, puts its own products behind them)
+    int stage_perms();
+    // 5b. the products and the best pairs
+    int series_products();
+    // 5. 5a, then 5b
+    int products() { int rc = stage_perms(); if (rc == RGX_OK) rc = series_products(); return rc; }
     // 6. the copies back into q behind the call's one wait, then the host's part (perm_finish); q stays the caller's
     template <class R> int finish(R *q);
     // RGX_ERR_DEVICE: q could not be had

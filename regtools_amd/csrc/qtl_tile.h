@@ -1,4 +1,4 @@
-// qtl_tile.h -- the one slab loop of the sQTL product kernels, with a thread's place in a tile and the totals' block sum (device only): k_qtl_pairs (qtl_kernels.hip), k_qtl_perm (qtl_perm_kernels.hip)
+// qtl_tile.h -- the one slab loop of the sQTL product kernels, with a thread's place in a tile and the totals' block sum (device only): k_qtl_pairs (qtl_kernels.hip), k_qtl_perm (qtl_perm_kernels.hip), k_qtl_perm_cond (qtl_cond_kernels.hip)
 // and k_qtl_trans_count / k_qtl_trans_emit (qtl_trans_kernels.hip) run it; they differ in where an entry of the A panel comes from, which a
 // small source type says.
 #pragma once
@@ -27,6 +27,18 @@ struct QtlTilePerms {                        // a column of the sample-major per
 
 // where a thread's chains lie in the tile: the i-th of its four rows (t = ty = tid / 16) or columns (t = tx = tid % 16)
 __device__ __forceinline__ uint32_t qtl_tile_at(uint32_t i, uint32_t t) { return (i < 2 ? 0 : 32) + 2 * t + (i & 1); }
+
+// The contract's dot64 as a wave runs it: lane l alone holds the partial of the entries s % 64 == l, then the halving adds.  Every lane gets P[0].
+__device__ __forceinline__ double qtl_halve(double p) {
+#pragma unroll
+    for (uint32_t off = 32; off; off >>= 1) p = qtl_add(p, __shfl_down(p, off, 64));
+    return __shfl(p, 0, 64);                                 // (lane 0 holds P[0]: every lane of the wave gets it)
+}
+__device__ __forceinline__ double qtl_dot64(const double *a, const double *b, uint32_t S, uint32_t l) {
+    double p = 0.0;
+    for (uint32_t s = l; s < S; s += 64) p = qtl_fma(a[s], b[s], p);
+    return qtl_halve(p);
+}
 
 // Two 64-bit sums over the 256 threads of one workgroup: a and b are this thread's shares; behind the return part[0][0] and part[1][0] hold the sums.
 __device__ __forceinline__ void qtl_sum2_256(unsigned long long (&part)[2][256], unsigned long long a, unsigned long long b) {

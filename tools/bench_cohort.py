@@ -43,6 +43,9 @@
                     permutations (default 1000, seed 0): first and warm calls; P (B + 1) S fused multiply-adds of the contract over ms_products as
                     GFMA/s, the 4,096 S per tile that were issued, the tile fill; rgx_cohort_qtl_permute_host where its P (B + 1) S stay below
                     --host-fmas (default 2e11), identical as bit patterns; and ms_pairs of rgx_cohort_qtl_nominal on the same inputs beside it
+  --indep           rgx_cohort_qtl_independent (DESIGN.md 4.5m) on --qtl's planted tables with --perms B permutations: ms per phase, rounds and series;
+                    then rgx_cohort_qtl_permute_conditional at m = 1 and m = 8 beside rgx_cohort_qtl_permute in the same process: ms_products per
+                    tile of each, and the host twin when its work stays below --host-fmas
   --trans           rgx_cohort_qtl_trans (ms_trans, ms_residual, ms_count, ms_emit) on --qtl's planted tables at p <= --pval
                     (default 1e-5) with the pairs inside --window left out: --reps calls with the tile mapping's super-tiles of --band row blocks
                     (default 4) and --reps without the mapping; the 4,096 S fused multiply-adds issued per tile over ms_count as GFMA/s; beside it
@@ -703,6 +706,65 @@ def part_group(a):
     co.close()
 
 
+def part_indep(a):
+    """rgx_cohort_qtl_independent on --qtl's planted tables with --perms B permutations at p_beta <= --pval-indep: --reps calls, ms per phase, the
+    rounds and the series; then the conditional pass alone at m = 1 and m = 8 over every row with at least nine cis variants, each conditioned on
+    its first m, beside the permutation pass in the same process on the same inputs: ms_products of each and per tile of 64 x 64 products, which
+    is what compares k_qtl_perm_cond with k_qtl_perm (the permutation pass walks every row's tiles, the conditional pass the series' rows')."""
+    import regtools_amd
+    from regtools_amd import cohort
+    co = regtools_amd.Cohort(ctx=regtools_amd.Context(0))
+    for size in [x for x in (a.planted or "64x4000x6000").split(",") if x]:
+        S, K, V = [int(x) for x in size.lower().split("x")]
+        t0 = time.time()
+        ph, regions, pos, dosage, pcs, n_cov = planted_qtl_inputs(a, co, S, K, V)
+        B = a.perms
+        perms = cohort.qtl_permutations(S, B, 0)
+        args = (ph, regions, np.zeros(V, np.uint32), pos, dosage, pcs.component if pcs else None, a.window)
+        line = {"part": "indep", "samples": S, "rows": K, "variants": V, "n_cov": n_cov, "window": a.window, "perms": B, "p_threshold": a.pval_indep,
+                "s_generate": round(time.time() - t0, 1)}
+        runs = [co.qtl_independent(*args, perms=perms, p_threshold=a.pval_indep, max_signals=8) for _ in range(a.reps)]
+        q = runs[0]
+        line.update({"entered": q.n_entered, "forward_rounds": q.n_forward_rounds, "series": q.n_series_total, "signals": q.n_signals,
+                     "capped": q.n_capped, "ms_indep": [round(r.ms_indep, 3) for r in runs], "ms_round0": [round(r.ms_round0, 3) for r in runs],
+                     "ms_forward": [round(r.ms_forward, 3) for r in runs], "ms_backward": [round(r.ms_backward, 3) for r in runs]})
+        nominal = co.qtl_nominal(*args)
+        begin = nominal.pair_begin.astype(np.int64)
+        rows = np.nonzero(np.diff(begin) >= 9)[0]
+        first = np.stack([nominal.pair_variant[begin[rows] + j] for j in range(8)], axis=1) if len(rows) else np.zeros((0, 8), np.uint32)
+        nominal.close()
+        plain = [co.qtl_permute(*args, perms=perms) for _ in range(a.reps)]
+        best = min(plain[1:] or plain, key=lambda r: r.ms_products)
+        line.update({"perm_ms_products": [round(r.ms_products, 3) for r in plain], "perm_tiles": plain[0].n_tiles,
+                     "perm_us_per_tile": round(1e3 * best.ms_products / max(plain[0].n_tiles, 1), 4)})
+        for m in (1, 8):
+            lists = (rows.astype(np.uint32), (np.arange(len(rows) + 1) * m).astype(np.uint32), np.ascontiguousarray(first[:, :m]).reshape(-1))
+            cond = [co.qtl_permute_conditional(args[0], args[1], *lists, *args[2:], perms=perms) for _ in range(a.reps)] if len(rows) else []
+            if not cond:
+                continue
+            cb = min(cond[1:] or cond, key=lambda r: r.ms_products)
+            per_tile = 1e3 * cb.ms_products / max(cond[0].n_tiles, 1)
+            line.update({"cond_m%d_series" % m: len(rows), "cond_m%d_ms_prepare" % m: [round(r.ms_prepare, 3) for r in cond],
+                         "cond_m%d_ms_products" % m: [round(r.ms_products, 3) for r in cond], "cond_m%d_tiles" % m: cond[0].n_tiles,
+                         "cond_m%d_us_per_tile" % m: round(per_tile, 4),
+                         "cond_m%d_per_tile_over_perm" % m: round(per_tile / (1e3 * best.ms_products / max(plain[0].n_tiles, 1)), 3)})
+            for r in cond:
+                r.close()
+        for r in plain:
+            r.close()
+        if not a.no_host and K * V * S * (B + 1) / 64 <= a.host_fmas:
+            h = cohort.qtl_independent_host(*args, perms=perms, p_threshold=a.pval_indep, max_signals=8)
+            same = (h.n_signals == q.n_signals and np.array_equal(h.sig_begin, q.sig_begin) and np.array_equal(h.variant, q.variant)
+                    and np.array_equal(h.p_beta.view(np.uint64), q.p_beta.view(np.uint64)) and np.array_equal(h.r.view(np.uint64), q.r.view(np.uint64)))
+            line.update({"ms_indep_host": round(h.ms_indep, 1), "identical_to_host": bool(same)})
+            assert same, "the device's independent signals differ from the host twin's"
+            h.close()
+        for r in runs:
+            r.close()
+        print(json.dumps(line), flush=True)
+    co.close()
+
+
 def part_pipeline(a):
     import regtools_amd
     from regtools_amd import synth
@@ -764,6 +826,8 @@ def main():
     ap.add_argument("--perm", action="store_true", help="the sQTL permutation part, alone")
     ap.add_argument("--group", action="store_true", help="the grouped sQTL permutation part beside the ungrouped one, alone")
     ap.add_argument("--trans", action="store_true", help="the trans sQTL scan part beside the nominal scan's product kernel, alone")
+    ap.add_argument("--indep", action="store_true", help="the conditionally independent signals beside the permutation pass, alone")
+    ap.add_argument("--pval-indep", type=float, default=0.05, help="--indep: the threshold on the beta-approximated p")
     ap.add_argument("--pval", type=float, default=1e-5, help="--trans: the p-value threshold")
     ap.add_argument("--band", type=int, default=4, help="--trans: row blocks of a super-tile in the tile mapping (beside 0: no mapping)")
     ap.add_argument("--perms", type=int, default=1000, help="--perm: permutations")
@@ -796,6 +860,8 @@ def main():
         return part_perm(a)
     if a.group:
         return part_group(a)
+    if a.indep:
+        return part_indep(a)
     if a.part in ("all", "pipeline"):
         part_pipeline(a)
     if a.part in ("all", "finish"):
