@@ -96,6 +96,13 @@ RGX_HD int build_code(Tab &T, uint32_t w0, uint32_t n, int kind, Code &C) {
     C.c[15] = (code >> 1) << 13;   // lim[15]: bound of all codes (15 bits wide already)
     if (left < 0) return INF_OVERSUBSCRIBED;
     if (left > 0 && !(offs == 0 || (offs == 1 && count[1] == 1))) return INF_INCOMPLETE;
+    // A legal incomplete set leaves bit patterns that no code owns.  The words of the lengths above its longest code (none, or 1 bit) carry the bound
+    // of all its codes AND a length field that is not 0: code_lookup would take such a pattern for a 15-bit code and hand back a list index that
+    // nothing filled -- whatever symbol an earlier block left there.  They become copies of c[15], "no such code".
+    if (left > 0) {
+#pragma unroll
+        for (int k = 0; k < 15; ++k) if ((uint32_t)k >= offs) C.c[k] = C.c[15];
+    }
     for (uint32_t w = 0; w * 8 < n; ++w) {
         uint32_t word = T.get_len_word(w0 + w);
 #pragma unroll

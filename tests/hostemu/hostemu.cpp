@@ -70,6 +70,21 @@ extern "C" int emu_inflate_wave(const uint8_t *in, uint32_t in_len, uint8_t *out
     return st;
 }
 
+// ---- the decoders IN PLACE: on the caller's own payload bytes, no copy of the input (inflate_inplace.h, shared with inflate_edges.cpp) ------------
+// The output goes to a private buffer at destination phase `phase`, 16 spare bytes or more on both sides: -100 / -101 if a byte in front of / behind
+// the member's [0, cap) was written.  What each decoder may READ around its payload is the contract written down in inflate_inplace.h.
+#include "inflate_inplace.h"
+extern "C" uint32_t emu_inflate_front_bytes(int variant) { return rgx_emu::front_bytes(variant); }
+extern "C" int emu_inflate_inplace(int variant, const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t cap, uint32_t *out_len, uint32_t phase) {
+    std::vector<uint8_t> obuf((size_t)cap + 128 + 128 + 128 + 16, 0xA5);      // alignment, front, phase, behind
+    uint8_t *dst = (uint8_t *)(((uintptr_t)obuf.data() + 127) & ~(uintptr_t)127) + 128 + (phase & 127u);
+    const int st = rgx_emu::run(variant, in, in_len, dst, cap, out_len);
+    for (uint8_t *q = obuf.data(); q < dst; ++q) if (*q != 0xA5) return -100;
+    for (uint8_t *q = dst + cap; q < obuf.data() + obuf.size(); ++q) if (*q != 0xA5) return -101;
+    memcpy(out, dst, *out_len <= cap ? *out_len : cap);
+    return st;
+}
+
 // ---- the per-alignment cores of bam_core.h / cse_core.h, as the kernels call them ---------------------------------------------
 #include "../../regtools_amd/csrc/bam_core.h"
 #include "../../regtools_amd/csrc/cse_core.h"
