@@ -438,7 +438,7 @@ int prepare_events(rgx_ctx *c, const uint8_t *d_bam_in, const uint8_t *h_bam, si
 
 constexpr int kGoOn = -1;                                  // a stage of EventsRun: nothing to report, the next one
 
-// BGZF member discovery over a file that lies in HBM (kernels.hip a1), in the form its two callers share: EventsRun::stage_members, and the stage entry
+// BGZF member discovery over a file that lies in HBM (members_kernels.hip), in the form its two callers share: EventsRun::stage_members, and the stage entry
 // rgx_k_members (api_stage.cpp) that hands it files no compressor writes.  candidates() costs one host wait (the candidate count sizes the buffers),
 // query() the other; chain() only enqueues.  `guarded` (the stage entry) puts kGuardWords behind the candidate list and behind the room of the member
 // list and arms them in front of the fill: the only launches the product's call does not make.

@@ -26,7 +26,7 @@ extern "C" int rgx_k_scan_u32(rgx_ctx *c, const uint32_t *d_in, uint32_t *d_out,
     return RGX_OK;
 }
 
-// BGZF member discovery (kernels.hip a1) on the caller's file in HBM (tests/test_gpu_member_discovery.py): MemberDiscovery is what stage_members runs, the
+// BGZF member discovery (members_kernels.hip) on the caller's file in HBM (tests/test_gpu_member_discovery.py): MemberDiscovery is what stage_members runs, the
 // scalar block is prepared the way stage_upload prepares it.  The candidate list and the member list have guard words behind them.
 extern "C" int rgx_k_members(rgx_ctx *c, const void *d_bam, uint64_t bam_len, uint64_t root2, const uint32_t *d_true_sizes, const uint64_t *q_coff,
                              rgx_members_result **out, char *err, size_t errlen) {

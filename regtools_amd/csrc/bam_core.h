@@ -204,7 +204,7 @@ RGX_HD int32_t rec_endpos(const uint8_t *cig, uint32_t n_cigar, uint32_t flag, i
 
 // The serial state machine of junctions_extractor.cc:377-497.  `emit(start,end,ts,te)` is
 // called once per N op, in order.  Used by the lane-per-read kernel and by the unit tests; the
-// wave-per-read kernel computes the same four numbers with prefix sums (see cigar_scan in kernels.hip).
+// wave-per-read kernel computes the same four numbers with prefix sums (see k_emit_long in emit_kernels.hip).
 template <class Emit>
 RGX_HD void cigar_walk(int32_t pos, const uint8_t *cig, uint32_t n_cigar, Emit &&emit) {
     uint32_t start = (uint32_t)pos, ts = (uint32_t)pos, end = 0, te = 0;

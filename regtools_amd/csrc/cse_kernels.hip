@@ -4,7 +4,7 @@
 //   a9   k_window_pairs   one wave per variant window: binary-search the event range, keep events whose READ overlaps it
 // All three are gather-dominated integer kernels (HBM/L2 latency bound); counts are produced first, offsets by the shared
 // scan, then a fill pass writes variable-length results -- deterministic, no atomics on the data path.
-#include "kernels.h"
+#include "wave_prims.h"
 
 #include "cse_core.h"
 
@@ -12,8 +12,6 @@
 #include <string.h>
 
 namespace rgx {
-
-__device__ __forceinline__ uint32_t lane_id2() { return threadIdx.x & 63u; }
 
 // exon records of the candidate transcripts (SURVEY 8d's E_v / E_j), one atomic per wave
 __device__ __forceinline__ void wave_add_visits(uint32_t v, unsigned long long *visits) {
@@ -69,11 +67,6 @@ __device__ __forceinline__ uint32_t wave_scan_or(uint32_t v, uint32_t lane) {
     for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= (uint32_t)d) v |= o; }
     return v;
 }
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= (uint32_t)d) v += o; }
-    return v;
-}
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_junction_scan_wave(GtfView g, uint32_t n, const int32_t *__restrict__ chrom, const uint32_t *__restrict__ js_, const uint32_t *__restrict__ je_,
                                      const uint8_t *__restrict__ strand_, uint32_t *count, const uint32_t *__restrict__ base, uint32_t *flags, uint32_t *item_kind,
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void k_junction_scan_wave(GtfView g, uint32_t 
             const uint32_t seen = wave_scan_or(own, lane) | acc;           // flags of everything visited up to and including this transcript
             const bool listed = reached && seen != 0;
             k += listed ? 1u : 0u;
-            const uint32_t incl = wave_scan_add(k, lane);
+            const uint32_t incl = wave_incl_scan(k);
             if (FILL && k) {
                 uint32_t w = out0 + n_items + incl - k;
                 if (k > (listed ? 1u : 0u)) {

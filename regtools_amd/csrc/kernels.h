@@ -1,4 +1,4 @@
-// kernels.h -- launchers of the gfx950 kernels (definitions in kernels.hip). All asynchronous on `stream`.
+// kernels.h -- launchers of the gfx950 kernels (definitions in the .hip file each section names). All asynchronous on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,7 @@ constexpr uint32_t kSegCpSlots = 64;     // checkpoints per segment: offset of e
 constexpr uint64_t kChainEnd = ~0ull;
 constexpr uint64_t kChainUnknown = ~0ull - 1;   // exit of a segment in which the guess found nothing: no claim at all (not "the chain ended")   // "the record chain ended before this point" (truncated/corrupt stream)
 
-// ---- a1: BGZF inflate (one lane per member) -----------------------------------------------------------
+// ---- a1: BGZF inflate (one lane per member; kernels.hip) ------------------------------------------------
 // member m writes its bytes at arena + (members[m].upos - upos_bias)
 // len_scratch: inflate_scratch_bytes(n_members) bytes of device memory (code-length scratch of the block headers)
 size_t inflate_scratch_bytes(uint32_t n_members);
@@ -56,7 +56,7 @@ void launch_members_fetch(const Member *host_members, Member *dst, uint32_t n_me
 void launch_gate_set(uint32_t *flag, uint32_t epoch, hipStream_t stream);      // flags[k] = epoch, in stream order behind chunk k's copy
 // (inflate_plan_for -- which options suit a payload -- is front_plan.h's)
 
-// ---- a1 (container): BGZF member discovery on the device --------------------------------------------------
+// ---- a1 (container): BGZF member discovery on the device (members_kernels.hip; launch_inflate_probe: kernels.hip) ----
 // The member chain (bgzf.c:525: next = this + BSIZE + 1) is serial on a CPU (one dependent cache miss per member).
 // Here: (1) every byte offset is tested against check_header's predicate (bgzf.c:348-355) -> sorted candidate list
 // (two passes: count per 4 KiB tile, scan, fill); (2) each candidate links to the candidate at off+BSIZE+1 (binary
@@ -89,7 +89,7 @@ void launch_member_fix(Member *members, uint32_t *isize_compact, uint32_t max_me
 void launch_member_stop(const Member *members, uint32_t max_members, const uint32_t *n_members /*device*/, const uint32_t *from /*device*/, uint32_t *stop,
                         hipStream_t stream);
 
-// ---- a2: record framing ---------------------------------------------------------------------------------
+// ---- a2: record framing (records_kernels.hip) -------------------------------------------------------------
 // Which bytes of the arena hold the record stream.  One chain (whole-file runs, shards): segment s covers arena [pos0 + s*kSegBytes,
 // +kSegBytes) clipped to lim, and only segment 0 starts at an exact offset.  Region queries: ONE CHAIN PER CHUNK the reference's iterator
 // reads (hts_itr_next, hts.c:1924-1965: a seek to the chunk's begin, then records as long as the position in front of the next one is
@@ -126,7 +126,7 @@ void launch_seg_verify(const uint8_t *arena, SegGeom g, uint32_t n_seg,
                        uint32_t *status /* [0] leftmost disagreeing segment, [1] leftmost chain end; both preset to ~0u */, uint16_t *seg_cp, hipStream_t stream);
 void launch_seg_truncate(SegGeom g, uint32_t n_seg, uint32_t last, uint64_t *seg_start, uint64_t *seg_exit, uint32_t *seg_cnt, hipStream_t stream);
 
-// ---- a2/a3/a5/a6: SoA decode + per-read event count ---------------------------------------------------------
+// ---- a2/a3/a5/a6: SoA decode + per-read event count (records_kernels.hip) ----------------------------------
 struct ReadSoA {
     int32_t  *tid, *pos;
     uint32_t *flag_nc;     // flag << 16 | n_cigar
@@ -147,7 +147,7 @@ void launch_decode_seg(const uint8_t *arena, SegGeom g, uint32_t n_seg, const ui
 void launch_long_fill(uint32_t n_seg, const uint32_t *seg_base, const uint32_t *seg_cnt, const uint32_t *seg_long_base, ExtractCfg cfg, ReadSoA soa,
                       uint32_t *long_list, hipStream_t stream);
 
-// ---- a4: CIGAR scan + junction emit ---------------------------------------------------------------------------
+// ---- a4: CIGAR scan + junction emit (emit_kernels.hip) ------------------------------------------------------
 struct EventSoA {
     uint32_t *tid, *start, *ilen_cls;   // key words: tid | start | (end-start) << 2 | strand class
     uint32_t *ts, *te;                  // thick_start / thick_end of this read's instance
@@ -162,7 +162,7 @@ void launch_emit_short(const uint8_t *arena, uint32_t n_rec, ExtractCfg cfg, Rea
 void launch_emit_long(const uint8_t *arena, const uint32_t *long_list, uint32_t n_long,
                       ExtractCfg cfg, ReadSoA soa, const uint32_t *ev_base, EventSoA ev, hipStream_t stream);
 
-// ---- primitives --------------------------------------------------------------------------------------------------
+// ---- primitives (prims_kernels.hip; the wave scans under them: wave_prims.h) ---------------------------------
 // exclusive scan of n uint32 (out may alias in); *total (device) receives the sum. tmp needs scan_tmp_words(n) words.
 size_t scan_tmp_words(uint32_t n);
 void launch_scan_u32(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total, uint32_t *tmp, hipStream_t stream);
@@ -176,7 +176,7 @@ void launch_radix_pass(const uint32_t *word, uint32_t shift, uint32_t bits, cons
 void launch_radix_pass_keyed(const uint32_t *key_in, uint32_t *key_out, uint32_t shift, uint32_t bits, const uint32_t *perm_in, uint32_t *perm_out,
                              uint32_t n, uint32_t *tmp, hipStream_t stream);
 
-// ---- a7: segmented reduce ------------------------------------------------------------------------------------------
+// ---- a7: segmented reduce, table writers (reduce_kernels.hip) ----------------------------------------------------
 struct UniqueSoA {
     uint32_t *tid, *start, *end, *ts_min, *te_max, *count, *first_seen, *last_seen, *name_rank;
     uint8_t  *strand;

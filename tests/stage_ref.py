@@ -69,7 +69,7 @@ def group_by(tid, start, ilen_cls, ts, te, strand, rank_of_group):
 
 
 def preagg_slot(tid, start, ilen_cls):
-    """The slot of k_preagg's LDS table (2048 slots for its 1024-event tiles) a key is first tried in.  RESTATED from kernels.hip (k_preagg): should
+    """The slot of k_preagg's LDS table (2048 slots for its 1024-event tiles) a key is first tried in.  RESTATED from reduce_kernels.hip (k_preagg): should
     the kernel's hash change, colliding_keys still returns distinct plausible keys -- they just no longer collide, and nothing fails."""
     h = (np.asarray(start, dtype=np.uint32) * np.uint32(0x9E3779B1)) ^ (np.asarray(ilen_cls, dtype=np.uint32) * np.uint32(0x85EBCA6B)) ^ \
         (np.asarray(tid, dtype=np.uint32) * np.uint32(0xC2B2AE35))

@@ -130,6 +130,86 @@ def test_product_seeks_like_the_oracle_on_damaged_files(gpu_ctx, tmp_path):
     assert n_rows > 200
 
 
+def unreadable_in_the_last_piece(tmp_path):
+    """One file of a few dozen members (contigs 1, 10, 2 in file order) in which a member of contig 2 does not inflate: its first DEFLATE block
+    claims the reserved type 3.  Host bytes of this size go up in three ungated pieces that end at 33 % and 67 % of the file (front_plan.h
+    plan_upload_chunks), and the members of a range are launched piece by piece (plan_pieces).  The range of `-r 2` begins in front of the second
+    cut, and the member that fails lies behind it: in a launch whose members count from the piece's begin, not from the range's."""
+    import zlib
+    src = str(tmp_path / "usrc.bam")
+    synth.write(src, 16000, shape="fuzz", seed=21)
+    bam, bai = open(src, "rb").read(), open(src + ".bai", "rb").read()
+    members = list(bamio.bgzf_members(bam))
+    assert 24 <= len(members) <= 48 and len(bam) < 2 * 4096 * 64          # (below that size REGTOOLS_AMD_OVERLAP="0,64" does not gate the launch)
+    inflated = bamio.inflate_all(src)
+    (l_text,) = struct.unpack_from("<i", inflated, 4)
+    (n_ref,) = struct.unpack_from("<i", inflated, 8 + l_text)
+    o = 12 + l_text
+    for _ in range(n_ref):
+        o += 8 + struct.unpack_from("<i", inflated, o)[0]
+    starts, u = [], 0
+    for _, _, isz in members:
+        starts.append(u); u += isz
+    tids = [set() for _ in members]                              # the contigs of the records that start in each member
+    k = 0
+    while o + 36 <= len(inflated):
+        bs, tid = struct.unpack_from("<ii", inflated, o)
+        while k + 1 < len(members) and starts[k + 1] <= o:
+            k += 1
+        tids[k].add(tid); o += 4 + bs
+    cut = (len(bam) * 67 // 100 + 4095) & ~4095                  # where the second piece of the upload ends
+    target = min(i for i, t in enumerate(tids) if 2 in t)        # the seek of `-r 2` lands in this member: the range's first
+    t_off, t_payload, _ = members[target]
+    assert target > 4 and t_off + 18 + len(t_payload) + 16 <= cut, "the range's first member must arrive with the second piece"
+    behind = [i for i, t in enumerate(tids) if t == {2} and members[i][0] > cut]
+    d = behind[len(behind) // 2]
+    assert behind[0] < d < behind[-1]
+    coff, payload, isz = members[d]
+    b = bytearray(bam); b[coff + 18] |= 0x06                     # BFINAL / BTYPE are the first three bits of the stream
+    try:
+        zlib.decompressobj(-15).decompress(bytes(b[coff + 18: coff + 18 + len(payload)]))
+        raise AssertionError("the damaged member still inflates")
+    except zlib.error:
+        pass
+    p = str(tmp_path / "unreadable.bam")
+    open(p, "wb").write(bytes(b)); open(p + ".bai", "wb").write(bai)
+    return p, src
+
+
+@pytest.mark.gpu
+def test_member_that_does_not_inflate_in_a_later_piece_of_the_upload(gpu_ctx, tmp_path):
+    """What a member that did not inflate reports carries its index in the call's range (kernels.hip report_bad_member): a piece's launch adds
+    where the piece begins (index_bias).  A region query reads that index -- its record stream ends where the member starts -- so `-r 2` over
+    unreadable_in_the_last_piece's file gives the oracle's rows only when the index is right: fewer rows than the sound file gives, more than
+    none.  Read from the file, and from host bytes that go up in pieces (a child process lowers the threshold); the whole-file read beside it."""
+    import json
+    import sys
+    from test_gpu_parity import gpu_extract
+    from test_gpu_gate import CHILD
+    p, sound = unreadable_in_the_last_piece(tmp_path)
+    jobs, want = [], []
+    for reg in ("2", None):
+        args = ["-s", "XS"] + (["-r", reg] if reg else [])
+        orc, exp, _ = run_oracle(args + [p])
+        full = run_oracle(args + [sound])[1]
+        assert orc == 0 and 20 < exp.count(b"\n") < full.count(b"\n") - 20, reg      # (the stream ends at the member: rows in front of it, none behind)
+        rc, out, _ = gpu_extract(gpu_ctx, p, args)
+        assert rc == orc and out == exp, reg
+        jobs.append(dict(bam=p, kw=dict(strandness=0, **({"region": reg} if reg else {}))))
+        want.append(exp)
+    jf, of = str(tmp_path / "jobs.json"), str(tmp_path / "out.json")
+    json.dump(jobs, open(jf, "w"))
+    env = dict(os.environ, REGTOOLS_AMD_OVERLAP="0,64", REGTOOLS_AMD_TRACE="1", PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", CHILD, jf, of], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    assert b"first chunk enqueued" in r.stderr and b"gated" not in r.stderr, "the calls did not go up in ungated pieces:\n" + r.stderr.decode()[-2000:]
+    # (the whole-file read is speculative: the failed member makes it start over device-resident)
+    assert b"inflate verdict: not clean" in r.stderr, "no launch met the member that does not inflate:\n" + r.stderr.decode()[-2000:]
+    for exp, res in zip(want, json.load(open(of))):
+        for one in res:
+            assert one["rc"] == 0 and one["bed"].encode("latin1") == exp
+
+
 # ---- a seek target that does not exist (file truncated in front of the region): empty result, and nothing may be written for the member the
 #      end of the file cuts off (its claimed size is ~0; handing that to the decoder as an output capacity was a GPU memory fault) -------------
 def truncated(tmp_path):

@@ -1,4 +1,4 @@
-"""BGZF member discovery on the device (kernels.hip a1: k_magic_count, k_magic_fill, k_member_link, k_member_jump, k_member_compact, k_member_fix,
+"""BGZF member discovery on the device (members_kernels.hip: k_magic_count, k_magic_fill, k_member_link, k_member_jump, k_member_compact, k_member_fix,
 k_member_upos, k_member_query, k_member_stop, driven by MemberDiscovery as EventsRun::stage_members drives it) through the stage entry
 rgx_k_members, against the serial restatement of tests/members_ref.py: every output -- the candidate offsets, the member list (cpos, upos, clen,
 isize), the counts, the inflated total, the three queries and the stop -- compared with == on integers.  The files are the ones no compressor
