@@ -14,6 +14,7 @@ int EventsRun::run() {
     if (bam_len < 28) return fail(err, errlen, RGX_ERR_OPEN, "%s", kMsgOpen);
     // (the arena the last call's data lay in, after it lost its place)
     if (c->arena_retired) { c->arena_retired->release(); delete c->arena_retired; c->arena_retired = nullptr; }
+    // (anything but kGoOn: an error, or kRestart -- prepare_events builds the next attempt)
     { const int rc = stage_upload(); if (rc != kGoOn) return rc; }
     { const int rc = stage_members(); if (rc != kGoOn) return rc; }
     { const int rc = stage_range_and_inflate(); if (rc != kGoOn) return rc; }
@@ -105,18 +106,12 @@ int EventsRun::calibrate_arena() {
 }
 
 int EventsRun::stage_upload() {
-    // -- index: ~1 ms of host parsing for a 5 MB .bai, done on a second host thread while this one feeds the device the member scan --
-    bai_thread = std::thread([this] {
-        bai_ok = bai && normalize_index(bai, bai_len, index_image, bai, bai_len) && parse_bai(bai, bai_len, bi, /*collect_anchors=*/false);
-    });
     // -- upload ----------------------------------------------------------------------------------------------------------
     // Host input: the file goes up in chunks on the copy stream from a helper thread (a pageable source makes hipMemcpyAsync block), while
     // this thread finds the members on the host (scan_members_parallel) -- the inflate of chunk k's members then runs while chunk k+1 is
     // still on the bus (SURVEY 8d times the path from file bytes in host memory).  A file the host scan does not vouch for waits for the
     // whole upload and takes the device's member discovery, as does device input.
     d_bam = d_bam_in;
-    // the host scan's member list (overlap only; the context keeps its pages: a fresh 4 MB is a thousand page faults per call)
-    std::vector<Member> &hm = c->hm_scratch;
     hm.clear();
     if (!d_bam) {
         DevBuf &b = c->buf(Buf::bam);
@@ -125,7 +120,7 @@ int EventsRun::stage_upload() {
         mark("file buffer in HBM");
         if (c->link) { c->wire_hold.take(&c->link->wire); mark("the link is ours"); }
         const size_t overlap_min = overlap_knobs().min_bytes;
-        if (allow_overlap && !d_true_sizes && bam_len >= overlap_min) {
+        if (!d_true_sizes && bam_len >= overlap_min) {
             HIP_TRY(ensure_upload_streams(c));
             if (c->copy_stream) copy_q = c->copy_stream;
             mark("upload streams");
@@ -133,15 +128,15 @@ int EventsRun::stage_upload() {
             // range between its two cuts (stage_members' cuts: shard_cut_targets, from the index) -- N shards then move the file once, not N times.
             UploadRange ur{0, bam_len, 0};
             if (shared && p->n_shards > 1 && p->shard >= 0 && p->shard < p->n_shards) {
-                if (bai_thread.joinable()) bai_thread.join();
+                ix.join();
                 BamHeader hh; size_t hb = 0;
-                if (bai_ok && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hh, &hb)) {
+                if (ix.ok && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hh, &hb)) {
                     const RegionKind kind = region_kind(p->region);
                     uint64_t sv = 0;
                     if (kind == RegionKind::rest && bi.have_nocoor) sv = bi.nocoor_voff; else if (kind == RegionKind::whole && bi.have_start) sv = bi.start_voff;
                     uint64_t tgt[2], got[2];
                     shard_cut_targets(bam_len, p->shard, p->n_shards, sv ? sv : 1, tgt);
-                    bai_first_anchor_ge(bai, bai_len, tgt, 2, got);
+                    bai_first_anchor_ge(ix.bai, ix.bai_len, tgt, 2, got);
                     const std::vector<Member> &sm = *shared->members;
                     size_t m4_end = 0;
                     if (!sm.empty()) { const Member &m4 = sm[std::min<size_t>(sm.size(), 4) - 1]; m4_end = (size_t)m4.cpos + m4.clen + 8; }
@@ -170,7 +165,6 @@ int EventsRun::stage_upload() {
             up.lo = up_lo; up.hi = up_hi; up.hdr_hi = hdr_hi;
             while (c->chunk_ev.size() < up.end.size()) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->chunk_ev.push_back(e); }
             uint8_t *dst = b.as<uint8_t>();
-            up.copy_stream = copy_q;
             uint32_t *gate_flags = gated ? c->buf(Buf::gate_flags).as<uint32_t>() : nullptr;
             const uint32_t gate_epoch = c->gate_epoch;
             hipStream_t gate_q = c->side[0] ? c->side[0] : copy_q;
@@ -232,7 +226,6 @@ int EventsRun::stage_upload() {
 
 int EventsRun::stage_members() {
     // -- BGZF member discovery on the device (replaces the serial BSIZE walk, bgzf.c:421-546) -------------------------------
-    std::vector<Member> &hm = c->hm_scratch;
     DevBuf &b_members = c->buf(Buf::members);
     if (overlap) {
         // the member list came from the host scan: what the discovery kernels would have left in HBM.  It goes there from page-locked host memory
@@ -263,14 +256,13 @@ int EventsRun::stage_members() {
     h_members = overlap ? (const Member *)c->pinned_members : nullptr;
     from_members = overlap ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
     if (!overlap) disc.chain(UINT64_MAX);
-    if (bai_thread.joinable()) bai_thread.join();
-    if (!bai_ok) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_INDEX, "%s", kMsgIndex);
+    ix.join();
+    if (!ix.ok) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_INDEX, "%s", kMsgIndex);
     mark("parse_bai");
     // (whole and rest both read to the end of the file without a predicate)
     const bool rest = region_kind(p->region) == RegionKind::rest;
     whole = region_kind(p->region) != RegionKind::query;
     // where the record stream starts (hts.c:1721-1741)
-    seek = false; seek_voff = 0;
     if (rest) {
         if (bi.have_nocoor) { seek_voff = bi.nocoor_voff; seek = seek_voff != 0; }
         else if (!bi.n_no_coor) return (void)hipStreamSynchronize(st), fail(err, errlen, RGX_ERR_REGION, "%s", kMsgRegion);
@@ -286,7 +278,7 @@ int EventsRun::stage_members() {
             p->shard, p->n_shards);
         uint64_t tgt[2], got[2];
         shard_cut_targets(bam_len, p->shard, p->n_shards, seek ? seek_voff : 1, tgt);
-        bai_first_anchor_ge(bai, bai_len, tgt, 2, got);
+        bai_first_anchor_ge(ix.bai, ix.bai_len, tgt, 2, got);
         if (p->shard > 0) cut_lo = got[0];
         if (p->shard + 1 < p->n_shards) cut_hi = got[1];
         if (cut_hi < cut_lo) cut_hi = cut_lo;
@@ -299,7 +291,6 @@ int EventsRun::stage_members() {
     // every chunk becomes its own record chain (SegGeom) and k_decode_seg applies the end rule.  Needs the contig names before the
     // launch: the header is inflated on the host from the head of the file.  A header that cannot be read that way leaves the range
     // alone: the whole file is read and filtered by overlap (such a header is not readable upstream either).
-    chunked = false;
     geom_chunked_hint = !whole;                    // (region queries keep the checked path: their chunk table wants the members' verdicts)
     if (!whole && p->region) {
         const size_t head_len = std::min<size_t>(bam_len, (size_t)8 << 20);
@@ -311,7 +302,7 @@ int EventsRun::stage_members() {
         // (the one parse of a call that talks: what sam_itr_querys -> hts_parse_decimal says about the region's numbers, once per query)
         if (host_bam_header(head, head_len, hh) && parse_region(hh, p->region, tid, beg, end,
             /*say=*/p->n_shards <= 1 || p->shard == 0) && tid < bi.n_ref && end >= beg &&
-            region_chunks(bai, bai_len, tid, beg, end, chunks)) {
+            region_chunks(ix.bai, ix.bai_len, tid, beg, end, chunks)) {
             chunked = true;
             if (p->n_shards > 1) {
                 // a region query over several shards: the iterator's chunk list is dealt out in order, in runs of about equal compressed size;
@@ -337,7 +328,6 @@ int EventsRun::stage_members() {
         mark("region chunks");
     }
 
-    empty_stream = false;
     auto query = [&]() -> hipError_t {
         uint64_t q[3] = {seek ? (seek_voff >> 16) : 0, cut_lo >> 16, cut_hi == UINT64_MAX ? UINT64_MAX - 64 : (cut_hi >> 16)};
         if (overlap) {
@@ -351,17 +341,9 @@ int EventsRun::stage_members() {
         return disc.query(q);
     };
     HIP_TRY(query());
-    if (overlap && seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
-        // the index points at something that is no member of this (well-formed) file: the device's discovery decides what that means
-        up.th.join();
-        HIP_TRY(complete_upload());
-        HIP_TRY(hipStreamSynchronize(copy_q));
-        HIP_TRY(hipStreamSynchronize(st));
-        const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, nullptr, false, region_to_file_end);
-        P.t_begin = t_begin;
-        return rc2;
-    }
     if (seek && (seek_voff >> 16) != 0 && h_sc->q_index[0] >= h_sc->n_members) {
+        // the host scan's list: the index points at something that is no member of this (well-formed) file -- the device's discovery decides what that means
+        if (overlap) { mark("index points at no member: starting over device-resident"); return restart(Restart::index_points_at_no_member); }
         // the seek target is no member of the chain from offset 0: something in front of it is broken.  bgzf_seek (hts_itr_next, hts.c:1935)
         // goes there regardless -- take it as a second chain root.  (Only damaged files get here.)
         disc.chain(seek_voff >> 16);
@@ -388,25 +370,15 @@ int EventsRun::stage_members() {
 
 int EventsRun::stage_range_and_inflate() {
     // -- member range of this call ---------------------------------------------------------------------------------------------
-    std::vector<Member> &hm = c->hm_scratch;
     DevBuf &b_arena = c->buf(Buf::arena);
-    member_range(cut_lo, cut_hi, h_sc->q_index, stop, n_members_all, chunked, region_to_file_end, m_lo, m_hi);
-    if (overlap && (up.lo || up.hi < bam_len) && m_hi > m_lo) {
-        // only a byte range of the file went up (a shard of a shared scan): it must hold every member of this call's range
-        if (!upload_covers_members(hm.data(), m_lo, m_hi, up.lo, up.hi)) {
-            mark("shard range does not cover its members: whole-file upload");
-            up.th.join();
-            HIP_TRY(hipStreamSynchronize(copy_q));
-            HIP_TRY(hipStreamSynchronize(st));
-            const int rc2 = prepare_events(c, d_bam_in, h_bam, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, d_true_sizes, allow_overlap,
-                region_to_file_end, nullptr);
-            P.t_begin = t_begin;
-            return rc2;
-        }
+    member_range(cut_lo, cut_hi, h_sc->q_index, stop, n_members_all, chunked, path.to_file_end, m_lo, m_hi);
+    // only a byte range of the file went up (a shard of a shared scan): it must hold every member of this call's range
+    if (overlap && (up.lo || up.hi < bam_len) && m_hi > m_lo && !upload_covers_members(hm.data(), m_lo, m_hi, up.lo, up.hi)) {
+        mark("shard range does not cover its members: whole-file upload");
+        return restart(Restart::shard_range_uncovered);
     }
     // arena offsets of the range ends
     uint64_t upos_hi = 0;
-    upos_lo = 0;
     HIP_TRY(upos_of(m_lo, upos_lo));
     HIP_TRY(upos_of(m_hi, upos_hi));
     total = upos_hi - upos_lo;

@@ -38,6 +38,7 @@
 #include "host_io.h"
 #include "worker_pool.h"
 #include <sys/stat.h>
+#include "call_path.h"
 #include "carve.h"
 #include "kernels.h"
 #include "scalars.h"
@@ -355,7 +356,6 @@ struct rgx_ctx {
     bool gate_distrust = false, early_distrust = false;
                                                        // the waiting waves and the kernels that release them share a hardware queue would cost every call its
                                                        // 2 s time-out)
-    bool walk_strict = false;             // set around the re-run of a call whose block_size-only framing met a record bam_read1 refuses (prepare_events)
     bool one_shot = false;                             // REGTOOLS_AMD_ONE_SHOT at creation: no streams besides `stream` (ensure_upload_streams)
     std::vector<hipEvent_t> chunk_ev;
     uint32_t gate_epoch = 0;                           // arrival gate of the overlapped upload (kernels.h InflateGate): this context's call counter
@@ -426,17 +426,36 @@ struct Prep {
     // in the first window that reads one (ExtractCfg::odd_count; empty on every file that is not damaged)
     struct OddAux { int32_t tid, pos, end; };
     std::vector<OddAux> odd_aux;
-    // the file's bytes in HBM as this call left them (the context's "bam" block, or the caller's device buffer): whole only for an unsharded call.  identify
-    // on a
-    // damaged file reads every window through the index on its own from here (cse_join.cpp window_join_by_seeks)
+    // the file's bytes in HBM as this call left them (the context's "bam" block, or the caller's device buffer): whole only for an unsharded call.
+    // identify on a damaged file reads every window through the index on its own from here (cse_join.cpp window_join_by_seeks)
     const uint8_t *d_file = nullptr;
 };
 
-int prepare_events(rgx_ctx *c, const uint8_t *d_bam_in, const uint8_t *h_bam, size_t bam_len, const uint8_t *bai, size_t bai_len,
-                          const rgx_extract_params *p, bool want_read_span, Prep &P, char *err, size_t errlen, const uint32_t *d_true_sizes = nullptr,
-                          bool allow_overlap = true, bool region_to_file_end = false, const SharedMembers *shared = nullptr);
+// What prepare_events takes: the file's bytes in HBM or in host memory (one of the two), its index as the caller read it, and `shared`, the member list of a
+// caller that scanned the file once for several shards.  A caller names what it means and leaves `path` alone: the call sets and moves it (call_path.h).
+struct EventsArgs {
+    rgx_ctx *c = nullptr;
+    const uint8_t *d_bam_in = nullptr, *h_bam = nullptr, *index = nullptr; size_t bam_len = 0, index_len = 0;
+    const rgx_extract_params *p = nullptr; bool want_read_span = false;
+    const SharedMembers *shared = nullptr; CallPath path;
+};
+int prepare_events(const EventsArgs &args, Prep &P, char *err, size_t errlen);
 
-constexpr int kGoOn = -1;                                  // a stage of EventsRun: nothing to report, the next one
+// a stage of EventsRun: nothing to report, the next one / start the call over for the reason in `why` (anything else is the call's result)
+constexpr int kGoOn = -1, kRestart = -2;
+
+// The call's index: a .csi or a compressed index rewritten as a plain BAI image and parsed (~1 ms for a 5 MB .bai) on a second host thread while the
+// first feeds the device, once per call -- an attempt that starts the call over meets the image, the pointer into it and the parse of the attempt before
+// it (normalising a plain image again gives the same pointer, parsing the same bytes the same BaiInfo).  Read behind join() only.
+struct CallIndex {
+    const uint8_t *bai; size_t bai_len;
+    std::vector<uint8_t> image; BaiInfo bi; bool ok = false;
+    std::thread th;
+    CallIndex(const uint8_t *index, size_t index_len) : bai(index), bai_len(index_len), th([this] {
+        ok = bai && normalize_index(bai, bai_len, image, bai, bai_len) && parse_bai(bai, bai_len, bi, /*collect_anchors=*/false); }) {}
+    void join() { if (th.joinable()) th.join(); }
+    ~CallIndex() { join(); }
+};
 
 // BGZF member discovery over a file that lies in HBM (members_kernels.hip), in the form its two callers share: EventsRun::stage_members, and the stage entry
 // rgx_k_members (api_stage.cpp) that hands it files no compressor writes.  candidates() costs one host wait (the candidate count sizes the buffers),
@@ -506,48 +525,54 @@ struct MemberDiscovery {
     }
 };
 
-// One call of the front half of the pipeline: file bytes -> junction events in file order.  The stages run in the order of
-// run(); each returns kGoOn, or the call's result (an error, or the result of the call starting over on another path: a file whose footers
-// lie, a record the lite walk must not accept, a shard whose range was not uploaded).  What one stage leaves for the next are the members below.
-struct EventsRun {
-    // -- the call's arguments (prepare_events) --
-    rgx_ctx *c; const uint8_t *d_bam_in; const uint8_t *h_bam; size_t bam_len; const uint8_t *bai; size_t bai_len;
-    const rgx_extract_params *p; bool want_read_span; Prep &P; char *err; size_t errlen; const uint32_t *d_true_sizes;
-    bool allow_overlap, region_to_file_end; const SharedMembers *shared;
-    // -- what the stages leave for one another --
+// One attempt at the front half of the pipeline: file bytes -> junction events in file order, on the path its arguments name.
+// The stages run in the order of run(); each returns kGoOn, the call's result (an error; RGX_OK from the last), or kRestart with the reason in `why`: a
+// stage that wants the call started over on another path (call_path.h) says so and does nothing else.  prepare_events (api_records.cpp) loops over the
+// attempts: it quiesces this one, asks next_path, lets the run be destroyed and builds the next.  What outlives an attempt is the caller's (P), the
+// context's (the file in "bam", the probe's sizes) or the loop's (the index, the link turns' give-back); what one stage leaves the next are the members below.
+struct EventsRun : EventsArgs {
+    Prep &P; char *err; size_t errlen; CallIndex &ix; const BaiInfo &bi = ix.bi;      // (the index: read behind ix.join())
+    const uint32_t *d_true_sizes;                            // path.true_sizes: what the probe of an earlier attempt left in the context's block
+    EventsRun(const EventsArgs &a, Prep &P_, char *err_, size_t errlen_, CallIndex &ix_) : EventsArgs(a), P(P_), err(err_), errlen(errlen_), ix(ix_),
+        d_true_sizes(a.path.true_sizes ? a.c->buf(Buf::probe_sizes).as<uint32_t>() : nullptr) { if (path.own_scan) shared = nullptr; }
+    // (what a stage tests before it asks is modelled by can_ask() in tests/test_call_path_host.py: a change to such a condition changes it there too)
+    Restart why{}; int restart(Restart r) { why = r; return kRestart; }
     hipStream_t st = nullptr, copy_q = nullptr;               // the pipeline's stream; where the file's upload goes
     double t_begin = 0, t_last = 0; bool trace = false;
     void mark(const char *what) { if (trace) { double t = now_ms(); fprintf(stderr, "[rgx trace] %-28s +%8.3f ms  (at %8.3f)%s\n", what, t - t_last,
         t - t_begin, c->link ? (" clock " + std::to_string(fmod(t, 1e5))).c_str() : ""); t_last = t; } }
-    // stage_upload: the index (parsed on a second host thread), the file on its way to HBM, the host's member scan
-    BaiInfo bi; bool bai_ok = false;
-    std::vector<uint8_t> index_image;                        // a .csi (or a compressed index) rewritten as a plain BAI image
-    std::thread bai_thread;
+    // stage_upload: the file on its way to HBM, the host's member scan
     const uint8_t *d_bam = nullptr;
+    // the host scan's member list (overlap only; the context keeps its pages: a fresh 4 MB is a thousand page faults per call)
+    std::vector<Member> &hm = c->hm_scratch;
     struct Upload {
         std::thread th; std::atomic<uint32_t> recorded{0}; std::atomic<int> err{0};
         std::vector<size_t> end;                            // end[j] = bytes [lo, end[j]) resident once chunk event j has fired
         size_t lo = 0, hi = 0, hdr_hi = 0;                  // the byte range that goes up (a shard's, + the header's [0, hdr_hi); the whole file otherwise)
-        hipStream_t copy_stream = nullptr;
-        // every way out of this function: the helper has enqueued its copies and the DMA out of the caller's buffer is over (the caller
-        // may free or reuse that buffer as soon as the call returns)
-        ~Upload() { if (th.joinable()) th.join(); if (copy_stream) (void)hipStreamSynchronize(copy_stream); }
     } up;
     bool overlap = false, gated = false;
     size_t gate_chunk = 0;
     uint64_t hm_total = 0;
     Scalars *d_sc = nullptr, *h_sc = nullptr;                // the call's scalars in HBM and their pinned host mirror (scalars.h)
     template <class T> hipError_t fetch(T &host_member) { return fetch_scalar(d_sc, h_sc, host_member, st); }
-    // before anything looks at the file through the device (the fallbacks of damaged files): the bytes a shard did not send
-    hipError_t complete_upload() {
-        if (!h_bam || !(up.lo || (up.hi && up.hi < bam_len))) return hipSuccess;
+    // the whole-range launch's verdict (both slots: a seek's front reports apart), enqueued / once the stream has been waited for
+    hipError_t fetch_verdict() { const hipError_t e = fetch(h_sc->inflate); return e == hipSuccess ? fetch(h_sc->inflate_early) : e; }
+    bool verdict_clean() const { return h_sc->inflate.first_bad == 0xffffffffu && h_sc->inflate_early.first_bad == 0xffffffffu; }
+    // Behind a kRestart, before the next attempt is built: nothing this one enqueued is still in flight, and a next attempt that reads the file from HBM
+    // finds all of it there (what a shard did not send goes up now, behind the copy stream's wait as complete_upload did it: the copies block, the second
+    // wait would find nothing).  kGoOn, or the call's error (a failed upload helper included); waits some restart would not need cost damaged files only.
+    int quiesce(bool next_device_resident) {
+        HIP_TRY(join_B());
         if (up.th.joinable()) up.th.join();
-        hipError_t e = hipStreamSynchronize(copy_q);
-        uint8_t *dst = c->buf(Buf::bam).as<uint8_t>();
-        if (e == hipSuccess && up.lo > up.hdr_hi) e = hipMemcpy(dst + up.hdr_hi, h_bam + up.hdr_hi, up.lo - up.hdr_hi, hipMemcpyHostToDevice);
-        if (e == hipSuccess && up.hi < bam_len) e = hipMemcpy(dst + up.hi, h_bam + up.hi, bam_len - up.hi, hipMemcpyHostToDevice);
-        up.lo = 0; up.hi = bam_len; up.hdr_hi = 0;
-        return e;
+        if (up.err) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: upload failed\n");
+        HIP_TRY(hipStreamSynchronize(copy_q));
+        if (next_device_resident && h_bam && (up.lo || (up.hi && up.hi < bam_len))) {
+            uint8_t *dst = c->buf(Buf::bam).as<uint8_t>();
+            if (up.lo > up.hdr_hi) HIP_TRY(hipMemcpy(dst + up.hdr_hi, h_bam + up.hdr_hi, up.lo - up.hdr_hi, hipMemcpyHostToDevice));
+            if (up.hi < bam_len) HIP_TRY(hipMemcpy(dst + up.hi, h_bam + up.hi, bam_len - up.hi, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        return kGoOn;
     }
     // stage_members: the member list (device discovery, or the host scan's), the record stream's start, cuts and chunks
     uint32_t n_cand = 0;
@@ -587,10 +612,10 @@ struct EventsRun {
         return hipStreamWaitEvent(st, split_ev, 0);
     }
     // stage_footers_and_header / stage_bounds_and_chains
-    bool spec = false; uint32_t mean_rec = 0;
+    bool spec = false; uint32_t mean_rec = 0;                // mean size of the file's first records (0 = unknown: 16 KiB segments)
     BamHeader hdr; int32_t n_ref = 0;
     uint64_t lim = 0, pos0 = 0; bool chain_ended = false;
-    ExtractCfg cfg; SegGeom geom; uint32_t seg_bytes = 0;
+    ExtractCfg cfg{}; SegGeom geom{}; uint32_t seg_bytes = 0;
     std::vector<SegChunk> seg_chunks;
     // stage_framing (+ early tail) / stage_decode / stage_emit
     const uint8_t *arena = nullptr; uint64_t span = 0; uint32_t n_seg = 0, n_rec = 0; bool lite_walk = false;
@@ -600,8 +625,8 @@ struct EventsRun {
     uint32_t *seg_iter_e = nullptr, *seg_long_e = nullptr, *seg_long_base_e = nullptr;
     uint16_t *seg_cp = nullptr;
     int cur = 0;
-    // One framing: the walk of segments [walk_from, n_s), then verification sweeps over [0, n_s) until the chain agrees.  Returns -1 to go on,
-    // anything else is the call's result (a restart on another path has run, or an error).  `ended` = the chain ends inside [0, n_s).
+    // One framing: the walk of segments [walk_from, n_s), then verification sweeps over [0, n_s) until the chain agrees.  Returns kGoOn, kRestart (the
+    // speculative launch's verdict was not clean) or the call's error.  `ended` = the chain ends inside [0, n_s).
     int frame(uint32_t n_s, uint32_t walk_from, bool &ended) {
         DevBuf &b_tmp = c->buf(Buf::tmp);
         launch_seg_walk(arena, geom, n_s, n_ref, seg_start[cur], seg_exit[cur], seg_cnt[cur], seg_cp, st, walk_from);
@@ -613,23 +638,14 @@ struct EventsRun {
             launch_scan_u32(seg_cnt[cur], seg_base, n_s, &d_sc->n_rec, b_tmp.as<uint32_t>(), st);
             HIP_TRY(fetch(h_sc->n_rec));
             HIP_TRY(fetch(h_sc->framing));
-            if (spec && iter == 0) {
-                HIP_TRY(fetch(h_sc->inflate));
-                HIP_TRY(fetch(h_sc->inflate_early));
-            }
+            if (spec && iter == 0) HIP_TRY(fetch_verdict());
             HIP_TRY(hipStreamSynchronize(st));
-            if (spec && iter == 0 && (h_sc->inflate.first_bad != 0xffffffffu || h_sc->inflate_early.first_bad != 0xffffffffu)) {
+            if (spec && iter == 0 && !verdict_clean()) {
                 // some member did not inflate to its footer's length: nothing enqueued since is worth anything
                 mark("inflate verdict: not clean, starting over device-resident");
                 if (gated) { c->gate_distrust = true; if (trace) fprintf(stderr,
                     "[rgx trace] arrival gate: verdict not clean, this context no longer uses it\n"); }
-                HIP_TRY(join_B());
-                HIP_TRY(complete_upload());
-                HIP_TRY(hipStreamSynchronize(copy_q));
-                HIP_TRY(hipStreamSynchronize(st));
-                const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, nullptr, false, region_to_file_end);
-                P.t_begin = t_begin;
-                return rc2;
+                return restart(Restart::verdict_not_clean);
             }
             ++P.framing_sweeps;
             const Scalars::Framing &fr = h_sc->framing;
@@ -646,12 +662,12 @@ struct EventsRun {
             if (fr.disagree == 0xffffffffu) break;
             if (iter > 1 << 20) return fail(err, errlen, RGX_ERR_FORMAT, "regtools_amd: record framing did not converge\n");
         }
-        return -1;
+        return kGoOn;
     }
     uint32_t sA = 0;                                          // early tail: segments [0, sA) are framed, verified and decoded
     // early tail: rows [0, emit_rows) have their events out, in emit_parts parts
     bool emit_parts_ok = false; uint32_t emit_parts = 0, emit_rows = 0; size_t ev_lay = 0;
-    EventSoA ev_e;
+    EventSoA ev_e{};
     // bytes of one event row in the "events" block: eight u32 columns (tid, start, ilen_cls, ts, te; rpos, rend; read) and the strand byte -- sized for all
     // of them, whichever of the optional ones a call lays out
     static constexpr size_t kEventRowBytes = 8 * sizeof(uint32_t) + 1;
@@ -665,7 +681,7 @@ struct EventsRun {
         return v;
     }
     size_t soa_cap = 0;                                       // rows the SoA columns are laid out for (early tail: an estimate made from the prefix)
-    ReadSoA soa;
+    ReadSoA soa{};
     uint32_t *ev_base = nullptr, *long_list = nullptr;
     // bytes of one decoded row in the "soa" block: cig_off (u64), six u32 columns (tid, pos, flag_nc, n_ev, ev_base, long_list) and the strand byte; with
     // barcodes, rec_off (u64) as well
@@ -683,12 +699,12 @@ struct EventsRun {
         return kGoOn;
     }
     uint32_t n_events = 0, n_long = 0; uint64_t n_iterated = 0;
-    // every way out while the side stream's launch may still run (an error in the prefix's framing, say: the next call on this context must not meet
-    // it) and while the index thread runs; `up` joins its helper and waits for the DMA out of the caller's buffer itself
+    // every way out: the side stream's launch is over (an error in the prefix's framing, say: the next attempt or call on this context must not meet it),
+    // the upload's helper has enqueued its copies and the DMA out of the caller's buffer is over (the caller may free or reuse it when the call returns)
     ~EventsRun() {
         if (split_B && split_ev) (void)hipEventSynchronize(split_ev);
-        if (bai_thread.joinable()) bai_thread.join();
-        if (c->link && !d_bam_in) { c->wire_hold.give(); c->chip_hold.give(); }      // (a call that ended early: the other contexts must not wait for it)
+        if (up.th.joinable()) up.th.join();
+        if (!up.end.empty()) (void)hipStreamSynchronize(copy_q);         // (chunks were planned: the helper ran)
     }
     int run();
     int calibrate_arena();

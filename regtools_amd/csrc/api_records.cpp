@@ -12,13 +12,11 @@ int EventsRun::stage_footers_and_header() {
     // does), and the launch's verdict is read with the framing's counts: anything else starts over on the device-resident path below.
     DevBuf &b_arena = c->buf(Buf::arena), &b_hdr = c->buf(Buf::hdr_arena), &b_lens = c->buf(Buf::inflate_scratch);
     BamHeader hdr_host;
-    mean_rec = 0;                                    // mean size of the file's first records (0 = unknown: 16 KiB segments)
     spec = overlap && !d_true_sizes && !geom_chunked_hint && host_bam_header(h_bam, std::min<size_t>(bam_len, (size_t)8 << 20), hdr_host, nullptr, &mean_rec);
     if (spec) h_sc->inflate = h_sc->inflate_early = InflateStatus{0xffffffffu, 0xffffffffu};
     else {
         HIP_TRY(join_B());
-        HIP_TRY(fetch(h_sc->inflate));
-        HIP_TRY(fetch(h_sc->inflate_early));
+        HIP_TRY(fetch_verdict());
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (!d_true_sizes) {
@@ -44,10 +42,7 @@ int EventsRun::stage_footers_and_header() {
             launch_inflate_probe(d_bam, d_members, n_members_all, b_slots.as<uint8_t>(), b_lens.as<uint32_t>(), b_sizes.as<uint32_t>(), st);
             HIP_TRY(hipStreamSynchronize(st));
             b_slots.release();                                  // 64 KiB per member: not kept
-            const int rc2 = prepare_events(c, d_bam_in, h_bam, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, b_sizes.as<uint32_t>(), true,
-                region_to_file_end);
-            P.t_begin = t_begin;
-            return rc2;
+            return restart(Restart::footers_lie);               // (the next attempt reads b_sizes: EventsRun::d_true_sizes)
         }
     }
 
@@ -121,7 +116,6 @@ int EventsRun::stage_bounds_and_chains() {
     else pos0 = hdr.end;                 // no seek: records start right after the header (range starts at member 0)
     // Did the stream stop for a reason that ends iteration upstream, rather than at this shard's upper cut?  (A later shard is a seek past
     // that point; the merge drops the shards behind one that ended, so that a damaged file gives the same table whatever the shard count.)
-    chain_ended = false;
     P.stream_ended = empty_stream;
     if (cut_hi != UINT64_MAX) {
         const uint64_t cut_lim = arena_of(cut_hi, h_sc->q_index[2], q_upos[2]);
@@ -137,7 +131,6 @@ int EventsRun::stage_bounds_and_chains() {
     if (pos0 > lim) pos0 = lim;
     if (empty_stream) lim = pos0;            // the seek target does not exist: no record is read
 
-    memset(&cfg, 0, sizeof cfg);
     cfg.n_ref = n_ref; cfg.strandness = p->strandness; cfg.tag0 = (uint8_t)p->strand_tag[0]; cfg.tag1 = (uint8_t)p->strand_tag[1];
     // (`junctions extract` only: identify's per-window extractions upstream meet such a read only inside a window -- DESIGN 8)
     if ((p->strandness == 0 || p->barcodes) && !want_read_span) { cfg.abort_out = &d_sc->abort_row; HIP_TRY(hipMemsetAsync(&d_sc->abort_row, 0xff, 4, st)); }
@@ -190,7 +183,6 @@ int EventsRun::stage_bounds_and_chains() {
     // -- region queries: one record chain per chunk of the iterator -----------------------------------------------------------------
     // chunk c = virtual offsets [u, v): a seek to u (bgzf_seek: the member at u >> 16, the offset inside it clipped to its length; no such
     // member = the read fails and the iteration is over), then records while the position in front of the next one is below v.
-    memset(&geom, 0, sizeof geom);
     const int env_seg = decode_knobs().seg_bytes;                   // (tests) 16384 or 131072
     seg_bytes = env_seg == (int)kSegBytes || env_seg == (int)kSegBytesLong ? (uint32_t)env_seg : (mean_rec >= kLongRecordBytes ? kSegBytesLong : kSegBytes);
     geom.seg_bytes = seg_bytes;
@@ -251,7 +243,7 @@ int EventsRun::stage_framing() {
     span = lim - pos0;
     n_seg = (uint32_t)((span + seg_bytes - 1) / seg_bytes);
     geom.pos0 = pos0; geom.lim = lim; geom.data_end = lim; geom.seg_bytes = seg_bytes;
-    lite_walk = !c->walk_strict;
+    lite_walk = !path.strict_walk;
     geom.lite_walk = lite_walk ? 1u : 0u;
     if (geom.chunks) {
         span = 0;
@@ -260,7 +252,6 @@ int EventsRun::stage_framing() {
         n_seg = lastc.seg_base + (uint32_t)((lastc.b - lastc.a + seg_bytes - 1) / seg_bytes);
         geom.data_end = total;
     }
-    n_rec = 0;
     DevBuf &b_seg = c->buf(Buf::seg), &b_tmp = c->buf(Buf::tmp);
     HIP_TRY(hipEventRecord(c->ev[2], st));
     // Early tail (round 4): while the side stream's launch still inflates the members of the last upload chunks, the segments that lie wholly
@@ -268,12 +259,6 @@ int EventsRun::stage_framing() {
     // reads further is only a guess) are framed, verified and decoded -- exact for the same reason the whole chain is: segment 0 starts at
     // an exact offset.  Plain whole-file calls on 16 KiB segments only; anything unusual in the prefix (the chain ends there, sweeps beyond
     // the usual one) drops back to the one-pass order.
-    sA = 0;
-    emit_parts_ok = false; emit_parts = 0; emit_rows = 0; ev_lay = 0;
-    memset(&ev_e, 0, sizeof ev_e);
-    soa_cap = 0;
-    memset(&soa, 0, sizeof soa);
-    ev_base = nullptr; long_list = nullptr;
     if (n_seg) {
         const size_t per = (size_t)n_seg;
         HIP_TRY(b_seg.ensure(per * (8 + 8 + 4) * 2 + per * 4 + per * 12 + 64));
@@ -303,7 +288,7 @@ int EventsRun::stage_framing() {
             bool ended_J = false;
             const uint32_t sweeps0 = P.framing_sweeps;
             const int rcJ = frame(sJ, sA, ended_J);
-            if (rcJ != -1) return rcJ;
+            if (rcJ != kGoOn) return rcJ;
             const uint32_t n_rec_J = h_sc->n_rec;
             // Where the last record that STARTS in the prefix ends = the verified chain's exit from its last segment.  The margin between the prefix
             // and the part of the arena still being inflated is one member; a record that reaches past it (a CIGAR of tens of thousands of
@@ -327,7 +312,6 @@ int EventsRun::stage_framing() {
             if (!sA) {
                 // rows for the whole file, estimated from the first part (+ 1/8); when the estimate turns out short the decode is simply made again below
                 { const int rc = soa_layout((size_t)((double)n_rec_J * ((double)n_seg / sJ) * 1.125) + 65536); if (rc != kGoOn) return rc; }
-                cfg.insane_out = nullptr;
                 if (lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
             }
             launch_decode_seg(arena, geom, sJ, seg_start[cur], seg_base, seg_cnt[cur], cfg, soa, seg_iter_e, seg_long_e, seg_cp, /*staged=*/true, st, sA);
@@ -352,30 +336,23 @@ int EventsRun::stage_framing() {
         }
         HIP_TRY(join_B());
         const int rcF = frame(n_seg, sA, chain_ended);
-        if (rcF != -1) return rcF;
+        if (rcF != kGoOn) return rcF;
         n_rec = h_sc->n_rec;
     } else HIP_TRY(join_B());
     if (spec && !n_seg) {                                     // (no framing, no sync yet: the inflate's verdict is still due)
-        HIP_TRY(fetch(h_sc->inflate));
-        HIP_TRY(fetch(h_sc->inflate_early));
+        HIP_TRY(fetch_verdict());
         HIP_TRY(hipStreamSynchronize(st));
-        if (h_sc->inflate.first_bad != 0xffffffffu || h_sc->inflate_early.first_bad != 0xffffffffu) {
-            HIP_TRY(complete_upload());
-            HIP_TRY(hipStreamSynchronize(copy_q));
-            const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, nullptr, false, region_to_file_end);
-            P.t_begin = t_begin;
-            return rc2;
+        if (!verdict_clean()) {
+            mark("inflate verdict: not clean, nothing framed, starting over device-resident");
+            return restart(Restart::verdict_not_clean_unframed);
         }
     }
     if (chain_ended) P.stream_ended = true;
-    if (chain_ended && geom.chunks && m_hi < n_members_all && !region_to_file_end) {
+    if (chain_ended && geom.chunks && m_hi < n_members_all && !path.to_file_end) {
         // a chunk's chain stopped -- possibly only because a record runs past the members the index asked for (an index that does not
         // describe this file): once more with everything up to the end of the file inflated
         mark("region: chain ended, re-reading to the end of the file");
-        if (overlap) { HIP_TRY(complete_upload()); HIP_TRY(hipStreamSynchronize(copy_q)); }
-        const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, d_true_sizes, false, true);
-        P.t_begin = t_begin;
-        return rc2;
+        return restart(Restart::region_chain_ended);
     }
     HIP_TRY(hipEventRecord(c->ev[3], st));
     mark("framing (sync)");
@@ -386,14 +363,11 @@ int EventsRun::stage_framing() {
 int EventsRun::stage_decode() {
     // -- decode + count -----------------------------------------------------------------------------------------------------
     DevBuf &b_tmp = c->buf(Buf::tmp);
-    n_events = 0; n_long = 0;
-    n_iterated = 0;
     if (n_rec) {
         const size_t R = n_rec;
         // (early tail: the prefix is decoded already, into columns laid out for an estimate of the row count; when that was short, or the chain
         //  ended after all, everything is decoded again)
-        uint32_t s_from = sA;
-        if (sA && (R > soa_cap || chain_ended)) s_from = 0;
+        const uint32_t s_from = sA && (R > soa_cap || chain_ended) ? 0 : sA;
         if (!s_from) { const int rc = soa_layout(R); if (rc != kGoOn) return rc; emit_parts_ok = false; }
         HIP_TRY(b_tmp.ensure(scan_tmp_words(n_rec) * 4 + 64));
         // per-segment outputs (no hot atomics): reuse the spare segment arrays as seg_iter / seg_long
@@ -407,10 +381,7 @@ int EventsRun::stage_decode() {
             HIP_TRY(hipMemsetAsync(&d_sc->stop_rule.index, 0xff, 4, st));
             HIP_TRY(hipMemsetAsync(&d_sc->stop_rule.last_pass, 0, 4, st));
         }
-        if (!s_from) {
-            cfg.insane_out = nullptr;
-            if (lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
-        }
+        if (!s_from && lite_walk) { cfg.insane_out = &d_sc->insane; HIP_TRY(hipMemsetAsync(&d_sc->insane, 0, 4, st)); h_sc->insane = 0; }
         for (int pass = 0; pass < 2; ++pass) {
             launch_decode_seg(arena, geom, n_seg, seg_start[cur], seg_base, seg_cnt[cur], cfg, soa, seg_iter, seg_long, seg_cp,
                               /*staged=*/span / n_rec <= kSparseRecordBytes, st, s_from);
@@ -433,13 +404,7 @@ int EventsRun::stage_decode() {
                 // a record the reference's reader would not have accepted (sam.c:421-423) lies on the chain the block_size walk followed:
                 // the whole call again with the framing making the full test (damaged files only)
                 mark("decode: a record fails bam_read1's test, starting over with the full walk");
-                if (overlap) { HIP_TRY(complete_upload()); HIP_TRY(hipStreamSynchronize(copy_q)); }
-                c->walk_strict = true;
-                const int rc2 = prepare_events(c, d_bam, nullptr, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, d_true_sizes, false,
-                    region_to_file_end);
-                c->walk_strict = false;
-                P.t_begin = t_begin;
-                return rc2;
+                return restart(Restart::record_fails_full_test);
             }
             if (pass || !cfg.stop_out || h_sc->stop_rule.index == 0xffffffffu || h_sc->stop_rule.last_pass <= h_sc->stop_rule.index + 1) break;
             cfg.stop_index = h_sc->stop_rule.index;
@@ -515,10 +480,24 @@ int EventsRun::stage_emit() {
     return RGX_OK;
 }
 
-int prepare_events(rgx_ctx *c, const uint8_t *d_bam_in, const uint8_t *h_bam, size_t bam_len, const uint8_t *bai, size_t bai_len,
-                          const rgx_extract_params *p, bool want_read_span, Prep &P, char *err, size_t errlen, const uint32_t *d_true_sizes,
-                          bool allow_overlap, bool region_to_file_end, const SharedMembers *shared) {
-    EventsRun r{c, d_bam_in, h_bam, bam_len, bai, bai_len, p, want_read_span, P, err, errlen, d_true_sizes, allow_overlap, region_to_file_end, shared};
-    return r.run();
+// The call: attempts on one path after another (call_path.h) until one does not ask to start over.  An attempt is quiesced and destroyed before the next is
+// built; the next reads the file from this one's buffer in HBM when its path is device-resident, from the caller's bytes otherwise.
+int prepare_events(const EventsArgs &args, Prep &P, char *err, size_t errlen) {
+    EventsArgs a = args;
+    a.path = first_path(a.d_bam_in != nullptr, a.shared != nullptr);
+    CallIndex ix(a.index, a.index_len);
+    // the link's turns go back at the call's end at the latest (one that ended early: the other contexts must not wait); between attempts they stay held
+    struct GiveTurns { rgx_ctx *c; ~GiveTurns() { if (c) { c->wire_hold.give(); c->chip_hold.give(); } } };
+    const GiveTurns give_turns{a.c->link && !a.d_bam_in ? a.c : nullptr};
+    double t_first = 0;
+    for (int attempt = 0;; ++attempt) {
+        EventsRun r(a, P, err, errlen, ix);
+        const int rc = r.run();
+        if (!attempt) t_first = r.t_begin;
+        if (rc != kRestart) { if (attempt) P.t_begin = t_first; return rc; }
+        if (!next_path(a.path, r.why, a.path))
+            return fail(err, errlen, RGX_ERR_FORMAT, "regtools_amd: the call started over twice for one reason (%s)\n", restart_name(r.why));
+        { const int rcq = r.quiesce(a.path.device_resident); if (rcq != kGoOn) return rcq; }
+        if (a.path.device_resident) { a.d_bam_in = r.d_bam; a.h_bam = nullptr; }
+    }
 }
-

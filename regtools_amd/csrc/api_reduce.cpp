@@ -277,7 +277,12 @@ int run_pipeline(rgx_ctx *c, const uint8_t *d_bam_in, const uint8_t *h_bam, size
     *out = nullptr;
     c->last_rows_valid = false;
     Prep P;
-    int rc = prepare_events(c, d_bam_in, h_bam, bam_len, bai, bai_len, p, false, P, err, errlen, nullptr, true, false, shared);
+    EventsArgs a;
+    a.c = c; a.p = p;
+    a.d_bam_in = d_bam_in; a.h_bam = h_bam; a.bam_len = bam_len;
+    a.index = bai; a.index_len = bai_len;
+    a.shared = shared;
+    int rc = prepare_events(a, P, err, errlen);
     if (rc != RGX_OK) return rc;
     hipStream_t st = c->stream;
     const int32_t n_ref = (int32_t)P.hdr.names.size();

@@ -32,6 +32,13 @@ struct IdentifyRun {
     int rc_bam = RGX_OK;
     char err_bam[512];
     rgx_extract_params ep;
+    EventsArgs whole_file_args() {                                // the BAM's events from the file's host bytes, unsharded, with `ep`
+        EventsArgs a;
+        a.c = c; a.p = &ep; a.want_read_span = true;
+        a.h_bam = bam.data(); a.bam_len = bam.size();
+        a.index = bai.data(); a.index_len = bai.size();
+        return a;
+    }
     // stage_annotation: the pool of the host stages from here on, the annotated VCF on its way out (a side thread that only reads V)
     PoolScope stage_pool;
     std::thread t_vcfout;
@@ -113,7 +120,7 @@ int IdentifyRun::stage_inputs() {
         RGX_ERR_INDEX, "%s", kMsgIndex);
     else if (shards && shards->size() > 1) rc_bam = prepare_events_sharded(*shards, bam.data(), bam.size(), bai.data(), bai.size(), &ep, P, err_bam,
         sizeof err_bam);
-    else rc_bam = prepare_events(c, nullptr, bam.data(), bam.size(), bai.data(), bai.size(), &ep, true, P, err_bam, sizeof err_bam);
+    else rc_bam = prepare_events(whole_file_args(), P, err_bam, sizeof err_bam);
     lap(S.ms_extract);
     return kGoOn;
 }
@@ -291,7 +298,7 @@ int IdentifyRun::windows_by_seeks(size_t w_bad) {
     // (a sharded extraction left no whole copy of the file in HBM: once more, unsharded)
     Prep P0;
     if (!d_file) {
-        const int rc0 = prepare_events(c, nullptr, bam.data(), bam.size(), bai.data(), bai.size(), &ep, true, P0, err, errlen);
+        const int rc0 = prepare_events(whole_file_args(), P0, err, errlen);
         if (rc0 != RGX_OK) { echo_variants(1); return rc0; }
         d_file = P0.d_file;
     }

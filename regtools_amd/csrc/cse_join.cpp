@@ -159,7 +159,11 @@ int window_join_by_seeks(rgx_ctx *c, const uint8_t *d_file, size_t bam_len, cons
         rgx_extract_params q = ep0;
         q.region = w_region[w].c_str(); q.shard = 0; q.n_shards = 1;
         Prep Pw;
-        const int rc = prepare_events(c, d_file, nullptr, bam_len, bai, bai_len, &q, true, Pw, err, errlen);
+        EventsArgs a;
+        a.c = c; a.p = &q; a.want_read_span = true;
+        a.d_bam_in = d_file; a.bam_len = bam_len;
+        a.index = bai; a.index_len = bai_len;
+        const int rc = prepare_events(a, Pw, err, errlen);
         if (rc != RGX_OK) return rc;
         if (!Pw.odd_aux.empty()) { w_abort = w; break; }
         const size_t n = Pw.n_events;
@@ -189,7 +193,11 @@ extern "C" int rgx_window_join(rgx_ctx *c, const char *bam_path, const rgx_extra
     rgx_extract_params ep = *p;
     ep.region = "."; ep.shard = 0; ep.n_shards = 1;
     Prep P;
-    int rc = prepare_events(c, nullptr, bam.data(), bam.size(), bai.data(), bai.size(), &ep, true, P, err, errlen);
+    EventsArgs a;
+    a.c = c; a.p = &ep; a.want_read_span = true;
+    a.h_bam = bam.data(); a.bam_len = bam.size();
+    a.index = bai.data(); a.index_len = bai.size();
+    int rc = prepare_events(a, P, err, errlen);
     if (rc != RGX_OK) return rc;
     std::vector<int32_t> w_tid((size_t)n_windows), w_beg(beg, beg + n_windows), w_end(end, end + n_windows);
     for (uint64_t w = 0; w < n_windows; ++w) {
@@ -280,10 +288,14 @@ int assoc_join(rgx_ctx *c, const std::vector<int32_t> &wch, const std::vector<ui
 int prepare_events_sharded(const std::vector<rgx_ctx *> &cs, const uint8_t *bam, size_t bam_len, const uint8_t *bai, size_t bai_len,
                            const rgx_extract_params *ep, Prep &P, char *err, size_t errlen) {
     const int n = (int)cs.size();
+    EventsArgs a;
+    a.c = cs[0]; a.p = ep; a.want_read_span = true;
+    a.h_bam = bam; a.bam_len = bam_len;
+    a.index = bai; a.index_len = bai_len;
     std::vector<Member> members; uint64_t total_inflated = 0;
     if (bam_len < ((size_t)8 << 20) || !scan_members_parallel(bam, bam_len, (int)usable_threads(24), members, total_inflated))
         // a file the host scan does not vouch for: one device, its own member discovery
-        return prepare_events(cs[0], nullptr, bam, bam_len, bai, bai_len, ep, true, P, err, errlen);
+        return prepare_events(a, P, err, errlen);
     SharedMembers sm{&members, total_inflated};
     std::vector<Prep> parts((size_t)n);
     std::vector<int> rcs((size_t)n, RGX_OK);
@@ -291,8 +303,8 @@ int prepare_events_sharded(const std::vector<rgx_ctx *> &cs, const uint8_t *bam,
     auto run = [&](int g) {
         rgx_extract_params q = *ep;
         q.shard = g; q.n_shards = n;
-        rcs[(size_t)g] = prepare_events(cs[(size_t)g], nullptr, bam, bam_len, bai, bai_len, &q, true, parts[(size_t)g], &errs[(size_t)g][0], 512, nullptr,
-            true, false, &sm);
+        EventsArgs ag = a; ag.c = cs[(size_t)g]; ag.p = &q; ag.shared = &sm;
+        rcs[(size_t)g] = prepare_events(ag, parts[(size_t)g], &errs[(size_t)g][0], 512);
     };
     bool distinct = true;
     for (int a = 0; a < n; ++a) for (int b = a + 1; b < n; ++b) if (cs[(size_t)a]->device == cs[(size_t)b]->device) distinct = false;

@@ -467,3 +467,23 @@ extern "C" size_t emu_front_early_parts(const rgx::Member *hm, uint32_t m_lo, ui
 extern "C" uint32_t emu_front_early_prefix_segments(uint64_t part_upos, uint64_t pos0, uint32_t seg_bytes, uint32_t n_seg, uint32_t s_done, int small_ok) {
     return rgx::early_prefix_segments(part_upos, pos0, seg_bytes, n_seg, s_done, small_ok != 0);
 }
+
+// call_path.h on its own: the path of an attempt of an extract call as five bits (1 device_resident, 2 own_scan, 4 true_sizes, 8 to_file_end, 16 strict_walk)
+#include "../../regtools_amd/csrc/call_path.h"
+static rgx::CallPath call_path_of(unsigned bits) {
+    rgx::CallPath p;
+    p.device_resident = bits & 1; p.own_scan = bits & 2; p.true_sizes = bits & 4; p.to_file_end = bits & 8; p.strict_walk = bits & 16;
+    return p;
+}
+static unsigned call_path_bits(const rgx::CallPath &p) {
+    return (p.device_resident ? 1u : 0u) | (p.own_scan ? 2u : 0u) | (p.true_sizes ? 4u : 0u) | (p.to_file_end ? 8u : 0u) | (p.strict_walk ? 16u : 0u);
+}
+extern "C" unsigned emu_call_first_path(int device_bytes, int shared_list) { return call_path_bits(rgx::first_path(device_bytes != 0, shared_list != 0)); }
+// why: 1..7 in the order of enum Restart.  The function's value: 1 and *next, or 0 (the flag the reason sets is set already)
+extern "C" int emu_call_next_path(unsigned cur, int why, unsigned *next) {
+    rgx::CallPath n;
+    const bool ok = rgx::next_path(call_path_of(cur), (rgx::Restart)(why - 1), n);
+    *next = call_path_bits(n);
+    return ok ? 1 : 0;
+}
+extern "C" const char *emu_call_restart_name(int why) { return rgx::restart_name((rgx::Restart)(why - 1)); }

@@ -60,8 +60,9 @@ def test_oracle_equals_reference_on_lying_footers(tmp_path):
 
 
 @pytest.mark.gpu
-def test_product_equals_oracle_on_lying_footers(gpu_ctx, tmp_path):
+def test_product_equals_oracle_on_lying_footers(gpu_ctx, tmp_path, monkeypatch, capfd):
     from test_gpu_parity import gpu_extract
+    monkeypatch.setenv("REGTOOLS_AMD_TRACE", "1")
     whole = None
     for name, p in variants(tmp_path):
         for args in (["-s", "XS"], ["-s", "RF", "-a", "3"]):
@@ -71,6 +72,7 @@ def test_product_equals_oracle_on_lying_footers(gpu_ctx, tmp_path):
         if name == "isize_all":
             whole = out
     assert whole and whole.count(b"\n") > 100                  # nothing was lost although no footer was right
+    assert "footer mismatch: probing" in capfd.readouterr().err  # (the calls did start over with the probe's sizes: call_path.h footers_lie)
 
 
 # ---- damage in front of a region: the iterator seeks past it (hts_itr_next -> bgzf_seek, hts.c:1935-1946) ---------------------------------------
@@ -210,6 +212,82 @@ def test_member_that_does_not_inflate_in_a_later_piece_of_the_upload(gpu_ctx, tm
             assert one["rc"] == 0 and one["bed"].encode("latin1") == exp
 
 
+def from_host_bytes_in_pieces(tmp_path, bam, regions):
+    """The file read once per region from page-locked host bytes that go up in ungated pieces behind the host's member scan (a child process lowers
+    the threshold), traced: (the child's stderr, the oracle's answers, the product's)."""
+    import json
+    import sys
+    from test_gpu_gate import CHILD
+    jobs = [dict(bam=bam, kw=dict(strandness=0, **({"region": reg} if reg else {}))) for reg in regions]
+    want = [run_oracle(["-s", "XS"] + (["-r", reg] if reg else []) + [bam]) for reg in regions]
+    jf, of = str(tmp_path / "jobs.json"), str(tmp_path / "out.json")
+    json.dump(jobs, open(jf, "w"))
+    env = dict(os.environ, REGTOOLS_AMD_OVERLAP="0,64", REGTOOLS_AMD_TRACE="1", PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", CHILD, jf, of], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    assert b"first chunk enqueued" in r.stderr and b"host member scan" in r.stderr, "the calls did not go up in pieces:\n" + r.stderr.decode()[-2000:]
+    return r.stderr, want, json.load(open(of))
+
+
+@pytest.mark.gpu
+def test_index_whose_first_offset_is_no_member_of_a_sound_file(gpu_ctx, tmp_path):
+    """A sound file whose header member was written again, stored instead of compressed, after the file was indexed: the host's member scan vouches
+    for it, and the offset at which the index says the records begin lies inside the new first member.  The call that found its members on the host
+    starts over device-resident, where the discovery kernels judge the offset (bgzf_seek goes there; the read behind it fails): the oracle's answer
+    from host bytes as from the file."""
+    import zlib
+    from test_gpu_parity import gpu_extract
+    src = str(tmp_path / "hsrc.bam")
+    synth.write(src, 16000, shape="fuzz", seed=21)
+    bam, bai = open(src, "rb").read(), open(src + ".bai", "rb").read()
+    coff, payload, isz = next(iter(bamio.bgzf_members(bam)))
+    old_len = struct.unpack_from("<H", bam, 16)[0] + 1
+    stored = bamio.bgzf_member(zlib.decompress(payload, -15), level=0)
+    assert coff == 0 and len(stored) > old_len + 64                    # the index's first offset (old_len << 16) now lies inside member 0
+    p = str(tmp_path / "stale_header.bam")
+    open(p, "wb").write(stored + bam[old_len:]); open(p + ".bai", "wb").write(bai)
+    assert len(bamio.inflate_all(p)) == len(bamio.inflate_all(src))     # (still one sound chain of members)
+    stderr, want, got = from_host_bytes_in_pieces(tmp_path, p, [None, "2"])
+    assert b"index points at no member" in stderr, "the host scan's list held the index's first offset:\n" + stderr.decode()[-2000:]
+    for (orc, exp, _), res, reg in zip(want, got, (None, "2")):
+        rc, out, _ = gpu_extract(gpu_ctx, p, ["-s", "XS"] + (["-r", reg] if reg else []))
+        assert (rc != 0) == (orc != 0) and out == exp, reg
+        for one in res:
+            assert (one["rc"] != 0) == (orc != 0) and one["bed"].encode("latin1") == exp, reg
+
+
+@pytest.mark.gpu
+def test_member_that_does_not_inflate_in_front_of_a_read_with_nothing_to_frame(gpu_ctx, tmp_path):
+    """`-r "*"` on a file without unplaced reads seeks behind the last record: nothing is framed, so the speculative launch's verdict is read on its
+    own.  A file of a handful of members is inflated from its first member on (the header's sake), and one of them, in front of the seek's target,
+    does not inflate: the call starts over device-resident and answers what the oracle answers."""
+    import zlib
+    from test_gpu_parity import gpu_extract
+    src = str(tmp_path / "nsrc.bam")
+    synth.write(src, 700, shape="short", seed=21)                   # (reads on the last contig, none unplaced: the index knows where they end)
+    bam, bai = open(src, "rb").read(), open(src + ".bai", "rb").read()
+    members = list(bamio.bgzf_members(bam))
+    assert 4 <= len(members) <= 5, len(members)                        # header, two or three of records, the EOF marker: the range starts at member 0
+    assert run_oracle(["-s", "XS", "-r", "*", src])[:2] == (0, b"")
+    coff, payload, isz = members[2]
+    b = bytearray(bam); b[coff + 18] |= 0x06                            # the reserved block type, as above
+    with pytest.raises(zlib.error):
+        zlib.decompressobj(-15).decompress(bytes(b[coff + 18: coff + 18 + len(payload)]))
+    p = str(tmp_path / "unreadable_small.bam")
+    open(p, "wb").write(bytes(b)); open(p + ".bai", "wb").write(bai)
+    stderr, want, got = from_host_bytes_in_pieces(tmp_path, p, ["*"])
+    assert b"not clean, nothing framed" in stderr, "the read framed something, or met no bad member:\n" + stderr.decode()[-2000:]
+    (orc, exp, _), res = want[0], got[0]
+    rc, out, _ = gpu_extract(gpu_ctx, p, ["-s", "XS", "-r", "*"])
+    assert (rc != 0) == (orc != 0) and out == exp
+    for one in res:
+        assert (one["rc"] != 0) == (orc != 0) and one["bed"].encode("latin1") == exp
+    # (the same file read whole ends at the member, with rows in front of it)
+    orc_w, exp_w, _ = run_oracle(["-s", "XS", p])
+    rc_w, out_w, _ = gpu_extract(gpu_ctx, p, ["-s", "XS"])
+    assert rc_w == orc_w == 0 and out_w == exp_w and exp_w.count(b"\n") > 5
+
+
 # ---- a seek target that does not exist (file truncated in front of the region): empty result, and nothing may be written for the member the
 #      end of the file cuts off (its claimed size is ~0; handing that to the decoder as an output capacity was a GPU memory fault) -------------
 def truncated(tmp_path):
@@ -335,8 +413,9 @@ def test_oracle_equals_reference_on_unbelievable_heads(tmp_path):
 
 
 @pytest.mark.gpu
-def test_product_does_not_follow_unbelievable_heads(gpu_ctx, tmp_path):
+def test_product_does_not_follow_unbelievable_heads(gpu_ctx, tmp_path, monkeypatch, capfd):
     from test_gpu_parity import gpu_extract
+    monkeypatch.setenv("REGTOOLS_AMD_TRACE", "1")
     rows = 0
     for name, p in unbelievable_heads(tmp_path):
         for args in (["-s", "XS"], ["-s", "RF", "-a", "3"]):
@@ -345,3 +424,4 @@ def test_product_does_not_follow_unbelievable_heads(gpu_ctx, tmp_path):
             assert rc == orc and out == exp, (name, args)
             rows += out.count(b"\n")
     assert rows > 100
+    assert "a record fails bam_read1's test, starting over" in capfd.readouterr().err      # (call_path.h record_fails_full_test)

@@ -482,7 +482,7 @@ def test_host_bytes_overlapped_upload_equals_device_resident_path(gpu_ctx):
     pin.close()
 
 
-def test_multi_device_host_equals_single_gpu(gpu_ctx, synth_dir):
+def test_multi_device_host_equals_single_gpu(gpu_ctx, synth_dir, monkeypatch, capfd):
     """rgx_extract_multi (the C++ host of junctions_main.cc:45-59 on a multi-GPU node): a host thread per device, one RCCL
     all-gather of the shards' packed rows, device merge.  With N >= 2 visible GPUs the collective runs on all of them; on a one-GPU box
     the same device is listed several times (the shards take turns, the exchange is a device copy) -- every other line is the same.
@@ -514,9 +514,13 @@ def test_multi_device_host_equals_single_gpu(gpu_ctx, synth_dir):
             assert kind().startswith("hipMemcpyPeerAsync") and "REGTOOLS_AMD_RCCL=off" in kind(), kind()
         finally:
             del os.environ["REGTOOLS_AMD_RCCL"]
+    monkeypatch.setenv("REGTOOLS_AMD_TRACE", "1")
     for args, kw in ((["-s", "RF", "-a", "20"], dict(strandness=1, min_anchor_length=20)), (["-s", "XS", "-r", "chr3"], dict(strandness=0, region="chr3"))):
         exp = gpu_extract(gpu_ctx, p, args)[1]
         assert regtools_amd.extract_multi(lists[-1], bam=p, **kw).bed12() == exp, args
+    monkeypatch.delenv("REGTOOLS_AMD_TRACE")
+    # (a region's shards follow the index's chunks, not the bytes they sent: the first ones start over with the whole file, call_path.h shard_range_uncovered)
+    assert "shard range does not cover its members: whole-file upload" in capfd.readouterr().err
     os.environ["REGTOOLS_AMD_RCCL"] = "selftest"           # one rank through ncclCommInitAll / ncclAllGather (librccl.so.1 loaded at run time) + device merge
     try:
         assert regtools_amd.extract_multi([0], bam=p, strandness=0).bed12() == single

@@ -86,12 +86,13 @@ def test_stale_index_region_queries_equal_oracle(gpu_ctx, tmp_path, shape, n, se
     assert checked == 2 * sc.N_VARIANTS
 
 
-def test_empty_member_between_chunks_ends_one_chunk_only(gpu_ctx, tmp_path):
+def test_empty_member_between_chunks_ends_one_chunk_only(gpu_ctx, tmp_path, monkeypatch, capfd):
     """An empty BGZF member reads as the end of the file for the reader that runs into it (bgzf.c:548-578) -- a later chunk is a seek past
     it.  The index is made AFTER the member went in, so it describes the file."""
     base = str(tmp_path / "base.bam")
     synth.write(base, 30000, shape="short", seed=9)
     path = str(tmp_path / "case.bam")
+    monkeypatch.setenv("REGTOOLS_AMD_TRACE", "1")
     for case, data in sc.empty_member_variants(open(base, "rb").read()):
         open(path, "wb").write(data)
         if os.path.exists(path + ".bai"):
@@ -108,3 +109,5 @@ def test_empty_member_between_chunks_ends_one_chunk_only(gpu_ctx, tmp_path):
             if rc == 0:
                 assert out == orc_out, (case, region)
                 assert gpu_extract_sharded(gpu_ctx, path, args, 2) == (0, orc_out), (case, region)
+    # (a chunk's chain that ends at the empty member makes the call read to the file's end once more: call_path.h region_chain_ended)
+    assert "region: chain ended, re-reading to the end of the file" in capfd.readouterr().err
