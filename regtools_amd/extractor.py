@@ -308,10 +308,13 @@ class Pipeline(object):
         return ticket.value
 
     def wait(self, ticket):
-        je, _, _ = self._open.pop(ticket)
+        je = self._open[ticket][0]                       # (the entry keeps the file's bytes alive: the upload may still be reading them)
         tab = C.POINTER(_ffi.JunctionTable)()
         err = C.create_string_buffer(512)
-        rc = self._lib.rgx_extract_wait(self._h, ticket, C.byref(tab), err, len(err))
+        try:
+            rc = self._lib.rgx_extract_wait(self._h, ticket, C.byref(tab), err, len(err))
+        finally:
+            del self._open[ticket]                       # the library has returned: it no longer reads them
         if rc != 0:
             raise RegtoolsError(rc, err.value.decode())
         je._table = tab

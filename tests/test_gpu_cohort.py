@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cohort_ref
 from cohort_common import STRANDNESS, cohort_files, expected_texts, table_from_rows  # noqa: F401  (cohort_files is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -201,8 +202,8 @@ def _by_numpy(all_cols, first_names):
         keep = (start - ts >= ANCHOR) & (te - end >= ANCHOR)
         cls = np.where(strand == ord("+"), 0, np.where(strand == ord("-"), 1, 2))
         key = (((ctid_of_name[name] << 20 | start) << 8 | (end - start)) << 2 | cls)[keep]
-        parts.append((key, np.full(keep.sum(), g), ts[keep], te[keep], count[keep], start[keep], end[keep], ctid_of_name[name][keep]))
-    key, sample, ts, te, count, start, end, ctid = [np.concatenate(x) for x in zip(*parts)]
+        parts.append((key, np.full(keep.sum(), g), ts[keep], te[keep], count[keep], start[keep], end[keep], ctid_of_name[name][keep], strand[keep]))
+    key, sample, ts, te, count, start, end, ctid, chars = [np.concatenate(x) for x in zip(*parts)]
     uniq, inv, n_with = np.unique(key, return_inverse=True, return_counts=True)
     order = np.lexsort((sample, inv))
     total = np.zeros(len(uniq), np.uint64); np.add.at(total, inv, count.astype(np.uint64))
@@ -210,6 +211,7 @@ def _by_numpy(all_cols, first_names):
     hi = np.zeros(len(uniq), np.int64); np.maximum.at(hi, inv, te)
     first = np.zeros(len(uniq), np.int64); first[inv[order][::-1]] = order[::-1]          # (any triple of the key: start / end / tid are the key's)
     return dict(n=len(uniq), n_triples=len(key), n_with=n_with, total=total, thick_start=lo, thick_end=hi, start=start[first], end=end[first], tid=ctid[first],
+                strand=cohort_ref.last_sample_strand(inv, sample, chars, len(uniq)),          # the character of the highest-numbered sample that has the key
                 row_begin=np.concatenate([[0], np.cumsum(n_with)]), col_sample=sample[order], val_count=count[order])
 
 
@@ -217,6 +219,7 @@ def _check(m, want):
     assert (m.n, m.n_triples) == (want["n"], want["n_triples"])
     for k in ("row_begin", "col_sample", "val_count", "total", "n_with", "thick_start", "thick_end", "start", "end", "tid"):
         assert np.array_equal(getattr(m, k).astype(np.int64), want[k].astype(np.int64)), k
+    assert m.strand.shape == want["strand"].shape and np.array_equal(m.strand, want["strand"]), "strand"
 
 
 def test_six_million_triples_twice(gpu_ctx):

@@ -76,6 +76,27 @@ def test_interleaved_files_equal_sequential_calls(gpu_ctx, tmp_path, depth):
         pl.close()
 
 
+def test_submitted_temporaries_live_until_their_wait_returns(gpu_ctx, tmp_path):
+    """submit() is handed bytes objects nobody else refers to: the pipeline's own reference is the only thing between the upload and freed memory
+    until wait() has returned (tests/test_cohort_edge_cases_host.py pins the order of events without a device)."""
+    import gc
+    import regtools_amd
+    files = [f for f in _files(tmp_path) if f["kind"] == "ok"][3:5]
+    want = [_sequential(gpu_ctx, f) for f in files]
+    pl = regtools_amd.Pipeline(0, 2)
+    try:
+        tickets = [pl.submit(bam_bytes=bytes(bytearray(f["bam"])), bai_bytes=bytes(bytearray(f["bai"])), strandness=f["strand"]) for f in files]
+        gc.collect()
+        garbage = [b"\xa5" * len(f[k]) for f in files for k in ("bam", "bai") for _ in range(3)]          # same-sized blocks, filled
+        got = []
+        for t in tickets:
+            je = pl.wait(t)
+            got.append(("ok", je.bed12(False), je.stats["n_records"]))
+        assert got == want and len(garbage) == 12 and not pl._open
+    finally:
+        pl.close()
+
+
 def test_pipeline_destroy_with_files_in_flight(gpu_ctx, tmp_path):
     """Tables nobody waited for are released, queued files run to their end (their buffers were promised to the pipeline)."""
     import regtools_amd
