@@ -190,9 +190,10 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
     *out = nullptr;
     std::lock_guard<std::mutex> lock(co->mu);
     const double t0 = now_ms();
-    HIP_ENTER(co->device);
-    hipStream_t st = co->stream;
-    const bool trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+    CohortRun run(co, "cohort", err, errlen);                           // (the device, the stream, and the fill mode of the two workspaces cut below)
+    if (int rc = run.enter()) return rc;
+    hipStream_t st = run.st;
+    const bool trace = run.trace;
     double t_last = t0;
     auto mark = [&](const char *what) { if (trace) { (void)hipStreamSynchronize(st); const double t = now_ms(); fprintf(stderr,
         "[rgx trace] cohort: %-28s +%8.3f ms\n", what, t - t_last); t_last = t; } };
@@ -211,10 +212,15 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         const size_t tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;
         if (co->sort.ensure((Nn * (2 + 2 + 7) + tmp_words) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory to sort %u triples\n", N); }
-        Carve w(co->sort);
+        // first writers: key0, key1, perm0, perm1 the sort's passes (launch_cohort_key gathers every key word); s.* k_cohort_gather; then, the sort
+        // over, key0 (heads) k_cohort_gather, key1 (seg) the scan, the spare permutation k_cohort_row_start; tmp: scratch.  All [0, N); the 64 pad
+        // elements of every array are never touched.  Not filled: the blocks of `add` with d_blocks, d_fill and the tid maps, which hold the
+        // cohort's triples from add to finish, and `image` below, which holds the matrix for the calls that follow.
+        Carve w = run.carve(co->sort);
         uint32_t *key0 = w.u32(Nn), *key1 = w.u32(Nn), *perm0 = w.u32(Nn), *perm1 = w.u32(Nn);
         CohortSorted s; s.tid = w.u32(Nn); s.start = w.u32(Nn); s.end = w.u32(Nn); s.ts = w.u32(Nn); s.te = w.u32(Nn); s.count = w.u32(Nn); s.ss = w.u32(Nn);
         uint32_t *tmp = w.u32(tmp_words); CARVE_TRY(w, "cohort sort");
+        if (int rc = run.carved(w, "cohort sort")) return rc;
         FinishTotals *d_tot = (FinishTotals *)(co->d_fill + 16);
         // stable LSD radix sort by (tid, start, end, class): the triples of one key keep the order they were appended in, which is sample order.
         // Each key word is gathered through the permutation once; its 8-bit passes then stream (key, permutation) pairs.
@@ -236,9 +242,11 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         const size_t Un = (size_t)U + 64;
         if (co->rows.ensure(Un * (2 + 6) * 4 + 256) != hipSuccess) { (void)hipGetLastError(); return fail(err, errlen, RGX_ERR_DEVICE,
             "regtools_amd: no device memory for %u cohort rows\n", U); }
-        Carve q(co->rows);
+        // first writers: r.* k_cohort_reduce, out_row and nnz_excl the scans, all [0, U)
+        Carve q = run.carve(co->rows);
         CohortRows r; r.total = (unsigned long long *)q.u64(Un); r.ts = q.u32(Un); r.te = q.u32(Un); r.keep = q.u32(Un); r.kept_nnz = q.u32(Un);
         uint32_t *out_row = q.u32(Un), *nnz_excl = q.u32(Un); CARVE_TRY(q, "cohort rows");
+        if (int rc = run.carved(q, "cohort rows")) return rc;
         launch_cohort_reduce(s, row_start, N, U, co->p.min_samples, co->p.min_total, r, st);
         launch_scan_u32(r.keep, out_row, U, &d_tot->kept.rows, tmp, st);
         launch_scan_u32(r.kept_nnz, nnz_excl, U, &d_tot->kept.nnz, tmp, st);
@@ -256,9 +264,11 @@ extern "C" int rgx_cohort_finish(rgx_cohort *co, rgx_cohort_matrix **out, char *
         m = matrix_alloc(co->contigs, co->sample_names, Uk, NNZ, /*pinned=*/true);
         if (!m) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the cohort matrix\n"); }
         CopyBack back{st};
+        run.guards_back(back);
         back((uint8_t *)m->total - L.total, b, L.bytes);                // (the whole image, where matrix_alloc pointed the members)
         const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_matrix_free(m); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s finishing the cohort\n", hipGetErrorString(e_)); }
+        if (int rc = run.guards_check()) { rgx_cohort_matrix_free(m); return rc; }
         co->image_serial = matrix_serial(m);
         mark("rows out + copy");
     } else {

@@ -116,7 +116,13 @@ struct ClusterRun : CohortRun {
         const size_t tmp_words = radix_tmp_words(n) + scan_tmp_words(n) + 64;
         if (int rc = grow(co->cl_rows, (Nn * (8 + 13 + (refine ? 4 : 0)) + 8 + 64 + tmp_words) * 4 + 256,
                           "regtools_amd: no device memory to cluster %u rows\n", n)) return rc;
-        Carve w(co->cl_rows);
+        // first writers: the scalars' flags the memset of every search batch, their counts the scans (n_alive: launch_refine_compact, read only
+        // behind a second search); cls k_cluster_class; perm0 .. perm3, key0, key1 the sorts' passes; alive k_refine_eligible; pos the compaction's
+        // scan; ea*, eb* the edge kernels [0, n_edges); parent k_cc_init; tot and cnt (= ea0) the memsets of mark_weak and finish, then the tallies;
+        // keep, is_root the root kernels; cid_excl and the counts' scans the scans; cluster, sort_key, cl_count, cl_total k_cluster_assign
+        // (cl_count and cl_total [0, C)); o_cl_begin k_cluster_widen, o_cs_begin k_cluster_cs_begin, each [0, C]; len, ent_off k_cluster_row_len and
+        // its scan; tmp: the passes' and scans' scratch.  All [0, n) unless said; the 64 pad elements of every array are never touched.
+        Carve w = carve(co->cl_rows);
         tot = (unsigned long long *)w.u64(Nn); cl_total = (unsigned long long *)w.u64(Nn); o_cl_begin = (unsigned long long *)w.u64(Nn + 1);
         o_cs_begin = (unsigned long long *)w.u64(Nn + 1);
         d_sc = (ClusterScalars *)w.u32(64);
@@ -124,6 +130,7 @@ struct ClusterRun : CohortRun {
         key0 = w.u32(Nn); key1 = w.u32(Nn); cls = w.u32(Nn); cluster = w.u32(Nn); cl_count = w.u32(Nn); tmp = w.u32(tmp_words);
         if (refine) { perm2 = w.u32(Nn); perm3 = w.u32(Nn); alive = w.u32(Nn); pos = w.u32(Nn); }
         CARVE_TRY(w, "cluster rows");
+        if (int rc = carved(w, "cluster rows")) return rc;
         return RGX_OK;
     }
 
@@ -233,11 +240,15 @@ struct ClusterRun : CohortRun {
             const size_t Mn = (size_t)M + 64;
             const size_t etmp_words = radix_tmp_words(M) + scan_tmp_words(M) + 64;
             if (int rc = grow(co->cl_entries, (Mn * (2 + 7) + etmp_words) * 4 + 256, "regtools_amd: no device memory for the clusters' %u counts\n", M)) return rc;
-            Carve q(co->cl_entries);
+            // first writers: e_cluster, e_sample, e_count k_cluster_expand [0, M); eperm*, ekey* the sort's passes; then ekey0 (heads)
+            // k_cluster_cs_heads, ekey1 (seg) the scan, the spare permutation k_cohort_row_start, each [0, M); then ekey0 (seg_cluster), ekey1
+            // (samples) and sums k_cluster_cs_sum [0, n_cs); etmp: scratch.  The 64 pad elements of every array are never touched.
+            Carve q = carve(co->cl_entries);
             unsigned long long *sums = (unsigned long long *)q.u64(Mn);
             uint32_t *e_cluster = q.u32(Mn), *e_sample = q.u32(Mn), *e_count = q.u32(Mn), *eperm0 = q.u32(Mn), *eperm1 = q.u32(Mn), *ekey0 = q.u32(Mn),
                      *ekey1 = q.u32(Mn), *etmp = q.u32(etmp_words);
             CARVE_TRY(q, "cluster entries");
+            if (int rc = carved(q, "cluster entries")) return rc;
             launch_cluster_expand(cluster, in.row_begin, in.col_sample, in.val_count, ent_off, n, wave_per_row, e_cluster, e_sample, e_count, st);
             // stable LSD sort by (cluster, sample): the entries of one pair end up side by side
             RadixSort by_pair{{eperm0, eperm1}, etmp, M, st, {ekey0, ekey1}};
@@ -260,12 +271,14 @@ struct ClusterRun : CohortRun {
         rgx_cohort_clusters *c = clusters_alloc(n, C, n_kept, n_cs, /*pinned=*/true);
         if (!c) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the clusters\n"); }
         CopyBack back{st};
+        guards_back(back);
         back(c->cluster, cluster, (size_t)n * 4); back(c->cl_begin, o_cl_begin, ((size_t)C + 1) * 8); back(c->cs_begin, o_cs_begin, ((size_t)C + 1) * 8);
         back(c->cl_total, cl_total, (size_t)C * 8); back(c->cl_row, cl_row, (size_t)n_kept * 4); back(c->cs_sample, cs_sample, (size_t)n_cs * 4);
         back(c->cs_total, cs_total, (size_t)n_cs * 8);
         const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_clusters_free(c); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s clustering the cohort\n", hipGetErrorString(e_)); }
         mark("copy");
+        if (int rc = guards_check()) { rgx_cohort_clusters_free(c); return rc; }
         c->n_rounds = n_rounds; c->n_components = n_components; c->ms_cluster = now_ms() - t0;
         *out = c;
         return RGX_OK;

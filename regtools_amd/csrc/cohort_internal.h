@@ -143,7 +143,49 @@ struct CohortRun {
         fprintf(stderr, "[rgx trace] %s: %-28s +%8.3f ms\n", name, what, t - t_last); t_last = t;
     }
     // the cohort's device and stream, in front of the run's first device call
-    int enter() { HIP_ENTER(co->device); st = co->stream; trace = getenv("REGTOOLS_AMD_TRACE") != nullptr; return RGX_OK; }
+    int enter() {
+        HIP_ENTER(co->device); st = co->stream; trace = getenv("REGTOOLS_AMD_TRACE") != nullptr;
+        const char *f = getenv("REGTOOLS_AMD_FILL"); fill = f && *f && strcmp(f, "0") != 0;
+        return RGX_OK;
+    }
+    // The fill mode (REGTOOLS_AMD_FILL, read per call, off by default; DESIGN.md "Workspace words").  A workspace word is written in the call that
+    // reads it or never read; with the mode on a word that breaks the rule shows in the result instead of reading as the zero of fresh memory or
+    // as what the call before left.  Every workspace is cut with carve() and handed to carved() behind its CARVE_TRY, in front of the first upload
+    // or launch into it: carved() enqueues the fills -- a quiet NaN over every floating-point array, the value 1 in every element of an integer
+    // array, the guard byte from the end of the last array to the buffer's capacity -- and notes the guard's first bytes, which guards_back()
+    // puts in front of the call's one wait and guards_check() reads behind it: a changed byte fails the call.
+    // Exempt, because their contents live from one call to the next: `image` (the matrix in HBM), the blocks of `add` with d_blocks and d_fill,
+    // and the tid maps.  `up`, `cl_in` and the other upload buffers that are not cut with Carve are written whole by their copies.
+    bool fill = false; CarveLog carve_log;
+    struct Guard { const char *what; const uint8_t *base, *at; size_t n; };
+    static constexpr uint32_t kMaxGuards = 12;
+    Guard guard[kMaxGuards]; uint32_t n_guards = 0; uint8_t guard_host[kMaxGuards][kCarveGuardWindow];
+    Carve carve(const DevBuf &b) { return Carve(b.p, b.cap, fill ? &carve_log : nullptr); }
+    int carved(const Carve &w, const char *what) {
+        if (!fill) return RGX_OK;
+        const CarveLog &lg = carve_log;
+        const size_t cap = (size_t)(w.at - w.base) + w.left;
+        if (w.log != &lg || lg.full || lg.end > cap) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: the %s buffer has more arrays than the fill mode's log\n", what);
+        for (uint32_t i = 0; i < lg.n; ++i) {
+            const CarveLog::Array &a = lg.a[i];
+            if (a.kind == CarveKind::fp) launch_fill_elems(w.base + a.off, 4, 0x7ff80000u, a.bytes / 4, st);
+            else launch_fill_elems(w.base + a.off, (uint32_t)a.kind, 1, a.bytes / (size_t)a.kind, st);
+        }
+        if (cap > lg.end) HIP_TRY(hipMemsetAsync(w.base + lg.end, kCarveGuardByte, cap - lg.end, st));
+        uint32_t g = 0;
+        while (g < n_guards && strcmp(guard[g].what, what) != 0) ++g;       // (a workspace cut again in the same call, grown or not: its newest guard counts)
+        if (g == kMaxGuards) return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: more workspaces in one call than the fill mode's guards (%s)\n", what);
+        guard[g] = Guard{what, w.base, w.base + lg.end, std::min(kCarveGuardWindow, cap - lg.end)};
+        if (g == n_guards) ++n_guards;
+        return RGX_OK;
+    }
+    void guards_back(CopyBack &back) { for (uint32_t g = 0; g < n_guards; ++g) back(guard_host[g], guard[g].at, guard[g].n); }
+    // behind the wait of the CopyBack that guards_back() went into
+    int guards_check() {
+        for (uint32_t g = 0; g < n_guards; ++g)
+            if (!carve_guard_check(guard_host[g], guard[g].n, guard[g].what, err, errlen)) return RGX_ERR_DEVICE;
+        return RGX_OK;
+    }
     // b holds `bytes` or the call fails with this message
     int grow(DevBuf &b, size_t bytes, const char *fmt, ...) {
         if (b.ensure(bytes) == hipSuccess) return RGX_OK;

@@ -146,22 +146,28 @@ struct PcsRun : CohortRun {
         const size_t n_entries = (size_t)K * S, n_T = (size_t)(2 * K - 1);
         if (int rc = grow(co->pc_in, n_T * 8 + n_entries * 4 + 256, "regtools_amd: no device memory for a table of %llu rows and %u samples\n",
                   (unsigned long long)K, S)) return rc;
-        Carve u(co->pc_in);
+        Carve u = carve(co->pc_in);                          // (both arrays written whole by their uploads)
         double *t_up = u.take<double>(n_T); uint32_t *r_up = u.u32(n_entries);
         CARVE_TRY(u, "principal component input");
+        if (int rc = carved(u, "principal component input")) return rc;
         HIP_TRY(hipMemcpyAsync(r_up, ph->rank2, n_entries * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(t_up, T.data(), n_T * 8, hipMemcpyHostToDevice, st));
         rank2 = r_up; d_T = t_up;
         const size_t n_pairs = (size_t)n_tiles * (n_tiles + 1) / 2, tile = (size_t)kPcaTile * kPcaTile, S_pad = (size_t)n_tiles * kPcaTile;
         if (int rc = grow(co->pc_part, (n_pairs * n_chunks * tile + (size_t)n_chunks * S_pad) * 8 + 256,
                   "regtools_amd: no device memory for the %u chunk partials of %u samples\n", n_chunks, S)) return rc;
-        Carve w(co->pc_part);
+        // first writers: part and col_part k_pca_gram, every (tile pair, chunk) partial and every chunk's S_pad column sums; k_pca_reduce reads
+        // them all
+        Carve w = carve(co->pc_part);
         part = w.take<double>(n_pairs * n_chunks * tile); col_part = w.take<double>((size_t)n_chunks * S_pad);
         CARVE_TRY(w, "principal component partials");
+        if (int rc = carved(w, "principal component partials")) return rc;
         if (int rc = grow(co->pc_out, ((size_t)S * S + S + 1) * 8 + 256, "regtools_amd: no device memory for the Gram matrix of %u samples\n", S)) return rc;
-        Carve o(co->pc_out);                                 // (in the order of the result's block: one copy takes the three)
+        // first writers: gram (both triangles) and col_sum k_pca_reduce (whole); the flag word the memset below, then k_pca_gram
+        Carve o = carve(co->pc_out);                         // (in the order of the result's block: one copy takes the three)
         gram = o.take<double>((size_t)S * S); col_sum = o.take<double>(S); bad = (uint32_t *)o.take<double>(1);
         CARVE_TRY(o, "principal component output");
+        if (int rc = carved(o, "principal component output")) return rc;
         HIP_TRY(hipMemsetAsync(bad, 0, 8, st));
         mark("rank2 + quantiles in HBM");
         return RGX_OK;
@@ -175,11 +181,13 @@ struct PcsRun : CohortRun {
         rgx_pheno_pcs *p = pcs_alloc(K, S, n_pcs, /*pinned=*/true);
         if (!p) { (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the principal components\n"); }
         CopyBack back{st};
+        guards_back(back);
         back(p->gram, gram, ((size_t)S * S + S + 1) * 8);                // (gram, col_sum and the flag: pcs_alloc)
         const hipError_t e_ = back.wait();
         if (e_ != hipSuccess) { rgx_cohort_pheno_pcs_free(p); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s building the Gram matrix\n",
             hipGetErrorString(e_)); }
         mark("copy");
+        if (int rc = guards_check()) { rgx_cohort_pheno_pcs_free(p); return rc; }
         if (*pcs_flag(p)) { rgx_cohort_pheno_pcs_free(p); return bad_rank(K, err, errlen); }
         const double t1 = now_ms();
         p->ms_gram = t1 - t_gram;

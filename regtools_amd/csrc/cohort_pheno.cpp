@@ -73,10 +73,11 @@ struct PhenoRun : CohortRun {
         const size_t C = (size_t)cl->n_clusters, n_cs = (size_t)cl->cs_begin[C];
         if (int rc = grow(co->ph_in, (C + 1 + n_cs) * 8 + ((size_t)n + n_cs) * 4 + 256,
                   "regtools_amd: no device memory to upload the clusters (%zu clusters, %zu denominators)\n", C, n_cs)) return rc;
-        Carve u(co->ph_in);
+        Carve u = carve(co->ph_in);                          // (every array written whole by its upload; the denominators have no bytes when there are none)
         unsigned long long *cs_begin = (unsigned long long *)u.u64(C + 1), *cs_total = (unsigned long long *)u.u64(n_cs);
         uint32_t *cluster = u.u32(n), *cs_sample = u.u32(n_cs);
         CARVE_TRY(u, "phenotype clusters");
+        if (int rc = carved(u, "phenotype clusters")) return rc;
         HIP_TRY(hipMemcpyAsync(cs_begin, cl->cs_begin, (C + 1) * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(cluster, cl->cluster, (size_t)n * 4, hipMemcpyHostToDevice, st));
         if (n_cs) {
@@ -89,11 +90,15 @@ struct PhenoRun : CohortRun {
 
         const size_t Nn = (size_t)n + 64, tmp_words = scan_tmp_words(n) + 64;
         if (int rc = grow(co->ph_rows, (Nn * (4 * 2 + 6) + 64 + tmp_words) * 4 + 256, "regtools_amd: no device memory for the statistics of %u rows\n", n)) return rc;
-        Carve w(co->ph_rows);
+        // first writers: keep, drop_na k_pheno_row_stats (whole); n_na, mean, sd the same kernel, but for rows without a cluster, whose keep is 0:
+        // k_pheno_scatter reads them for kept rows alone; pos and the scalars the scans; o_row, o_n_na, o_mean, o_sd k_pheno_scatter [0, K), the
+        // rest left and not read: k_pheno_z and the copies stop at K; tmp: the scans' scratch.  The 64 pad elements of every array are never touched.
+        Carve w = carve(co->ph_rows);
         mean = w.take<double>(Nn); sd = w.take<double>(Nn); o_mean = w.take<double>(Nn); o_sd = w.take<double>(Nn);
         d_sc = (PhenoScalars *)w.u32(64);
         keep = w.u32(Nn); drop_na = w.u32(Nn); pos = w.u32(Nn); n_na = w.u32(Nn); o_row = w.u32(Nn); o_n_na = w.u32(Nn); tmp = w.u32(tmp_words);
         CARVE_TRY(w, "phenotype rows");
+        if (int rc = carved(w, "phenotype rows")) return rc;
         return RGX_OK;
     }
 
@@ -116,10 +121,14 @@ struct PhenoRun : CohortRun {
         const uint32_t N = K * S;                                        // (at most n_clustered * S: checked)
         const size_t Nn = (size_t)N + 64, tmp_words = radix_tmp_words(N) + scan_tmp_words(N) + 64;
         if (int rc = grow(co->ph_entries, (Nn * 7 + tmp_words) * 4 + 256, "regtools_amd: no device memory to rank %u rows of %u samples\n", K, S)) return rc;
-        Carve q(co->ph_entries);
+        // first writers: z_lo, z_hi, e_sample k_pheno_z [0, N); perm0, perm1, key0, key1 the sort's passes; then, the sort over, key0 (heads)
+        // k_pheno_tie_heads, key1 (seg) the scan, the spare permutation (run starts) k_cohort_row_start, e_sample (rank2) k_pheno_rank, each
+        // [0, N); etmp: the passes' and the scan's scratch.  The 64 pad elements of every array are never touched.
+        Carve q = carve(co->ph_entries);
         uint32_t *z_lo = q.u32(Nn), *z_hi = q.u32(Nn), *e_sample = q.u32(Nn), *perm0 = q.u32(Nn), *perm1 = q.u32(Nn), *key0 = q.u32(Nn), *key1 = q.u32(Nn),
                  *etmp = q.u32(tmp_words);
         CARVE_TRY(q, "phenotype entries");
+        if (int rc = carved(q, "phenotype entries")) return rc;
         launch_pheno_z(in, o_row, o_mean, o_sd, K, S, z_lo, z_hi, e_sample, st);
         RadixSort by_column{{perm0, perm1}, etmp, N, st, {key0, key1}};
         by_column.by_keyed(z_lo, 32); by_column.by_keyed(z_hi, 32); by_column.by_keyed(e_sample, std::max<uint32_t>(1, bitlen(S - 1)));
@@ -140,12 +149,14 @@ struct PhenoRun : CohortRun {
         if (!p) { if (st) (void)hipStreamSynchronize(st); return fail(err, errlen, RGX_ERR_DEVICE, "regtools_amd: no memory for the phenotype table\n"); }
         if (K) {
             CopyBack back{st};
+            guards_back(back);
             back(p->row, o_row, (size_t)K * 4); back(p->n_na, o_n_na, (size_t)K * 4); back(p->mean, o_mean, (size_t)K * 8);
             back(p->sd, o_sd, (size_t)K * 8); back(p->rank2, rank2, (size_t)K * S * 4);
             const hipError_t e_ = back.wait();
             if (e_ != hipSuccess) { rgx_cohort_phenotypes_free(p); return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s building the phenotype table\n",
                 hipGetErrorString(e_)); }
             mark("copy");
+            if (int rc = guards_check()) { rgx_cohort_phenotypes_free(p); return rc; }
         }
         p->n_clustered = n_clustered; p->n_drop_na = S ? n_drop_na : n_clustered; p->n_drop_sd = n_clustered - p->n_drop_na - K;
         p->ms_pheno = now_ms() - t0;

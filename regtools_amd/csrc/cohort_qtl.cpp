@@ -51,9 +51,11 @@ struct NominalRun : QtlPrep {
             "regtools_amd: %llu tiles of 64 rows and 64 variants; the sQTL scan takes at most 2^31 - 1 (rows far out of position order)\n",
             (unsigned long long)n_tiles);
         if (int rc = grow(co->qt_out, (size_t)P * 20 + (size_t)K * 4 + 256, "regtools_amd: no device memory for %llu pairs\n", (unsigned long long)P)) return rc;
-        Carve o(co->qt_out);
+        // first writers: r, slope, pair_variant k_qtl_pairs (every pair lies in one tile); best k_qtl_best (whole)
+        Carve o = carve(co->qt_out);
         r = o.take<double>(P); slope = o.take<double>(P); pair_variant = o.u32(P); best = o.u32(K);
         CARVE_TRY(o, "sQTL pair");
+        if (int rc = carved(o, "sQTL pair")) return rc;
         return RGX_OK;
     }
     // 5. one workgroup per tile, then a wave per row

@@ -205,10 +205,17 @@ struct CondRun : PermRun {
         if (int rc = grow(co->qc_in, (2 * N + 1 + M) * 4 + 256, no_memory, sr.N, cap, B)) return rc;
         if (int rc = grow(co->qc_ws, ((N * kQtlMaxCond + N) * S + 3 * N + (kQtlMaxCond + 1) * cap + n_out) * 8 + (6 * N + 6 + n_tmp) * 4 + N + 256,
                           no_memory, sr.N, cap, B)) return rc;
-        Carve in(co->qc_in);
+        Carve in = carve(co->qc_in);                          // (every array written whole by its upload)
         uint32_t *row = in.u32(N), *begin = in.u32(N + 1), *var = in.u32(M);
         CARVE_TRY(in, "conditional series");
-        Carve w(co->qc_ws);
+        if (int rc = carved(in, "conditional series")) return rc;
+        // Cut anew by every round of the forward-backward pass; no round reads what the one before left.  First writers: z k_qtl_cond_basis, the
+        // m vectors of a series that is not collinear (the rest left: every reader stops at m or at a status); yc, yyc, status the same kernel
+        // (yc left for a collinear series, whose status keeps every reader away); beta, ggc k_qtl_cond_beta, the places [0, pb[N]) of series
+        // with status 0 and the planes j < m (the rest left: the readers go by status and m); perm_r, best_u k_qtl_perm_cond (whole); best_r,
+        // best_slope, best_variant, n_cis, n_window k_qtl_cond_best (whole); cnt k_qtl_cond_counts (whole, cnt[N] = 0); pb, total[0] the scan
+        // (total[1] left, never read); cflag the memset below; scan_tmp: the scan's scratch
+        Carve w = carve(co->qc_ws);
         d.N = sr.N; d.S = S; d.series_row = row; d.cond_begin = begin; d.cond_variant = var; d.lo = lo; d.count = count; d.u_var = u_var; d.cap = cap;
         d.z = w.take<double>(N * kQtlMaxCond * S); d.yc = w.take<double>(N * S); d.yyc = w.take<double>(N);
         d.beta = w.take<double>(kQtlMaxCond * cap); d.ggc = w.take<double>(cap);
@@ -218,6 +225,7 @@ struct CondRun : PermRun {
         uint32_t *total = w.u32(2), *scan_tmp = w.u32(n_tmp);
         d.status = w.u8(N); d.pb = pb;
         CARVE_TRY(w, "conditional sQTL");
+        if (int rc = carved(w, "conditional sQTL")) return rc;
         rel.resize(N + 1);
         for (size_t c = 0; c <= N; ++c) rel[c] = sr.begin[c] - sr.begin[0];
         HIP_TRY(hipMemcpyAsync(row, sr.row, N * 4, hipMemcpyHostToDevice, st));

@@ -116,10 +116,11 @@ int PermRun::stage_perms() {
     for (uint32_t b = 0; b <= B; ++b) for (uint32_t s = 0; s < S; ++s) permT[(size_t)s * ldp + b] = perm[(size_t)b * S + s];
     const size_t n_begin = mem ? (size_t)N + 1 : 0, n_mem = mem ? mem->row.size() : 0;
     if (int rc = grow(co->qp_in, permT.size() * 2 + (n_begin + n_mem) * 4 + 256, kNoPermMemory, B, N, series)) return rc;
-    Carve in(co->qp_in);
+    Carve in = carve(co->qp_in);                              // (every array written whole by its upload)
     d_permT = in.take<uint16_t>(permT.size());
     if (mem) { d_begin = in.u32(n_begin); d_row = in.u32(n_mem); }
     CARVE_TRY(in, mem ? "grouped sQTL permutation" : "sQTL permutation");
+    if (int rc = carved(in, mem ? "grouped sQTL permutation" : "sQTL permutation")) return rc;
     HIP_TRY(hipMemcpyAsync(d_permT, permT.data(), permT.size() * 2, hipMemcpyHostToDevice, st));
     if (mem) { HIP_TRY(hipMemcpyAsync(d_begin, mem->begin.data(), n_begin * 4, hipMemcpyHostToDevice, st)); }
     if (n_mem) { HIP_TRY(hipMemcpyAsync(d_row, mem->row.data(), n_mem * 4, hipMemcpyHostToDevice, st)); }
@@ -131,10 +132,13 @@ int PermRun::series_products() {
     const uint32_t N = n_series;
     const size_t n_out = (size_t)N * ((size_t)B + 1);
     if (int rc = grow(co->qp_out, n_out * 8 + (size_t)N * (mem ? 28 : 24) + 256, kNoPermMemory, B, N, series)) return rc;
-    Carve o(co->qp_out);
+    // first writers: perm_r, best_row, best_u k_qtl_perm (every series, +0.0 and RGX_NO_PAIR without pairs); best_variant, best_r, best_slope
+    // k_qtl_perm_best (every series)
+    Carve o = carve(co->qp_out);
     perm_r = o.take<double>(n_out); best_r = o.take<double>(N); best_slope = o.take<double>(N); best_u = o.u32(N); best_variant = o.u32(N);
     if (mem) best_row = o.u32(N);
     CARVE_TRY(o, mem ? "grouped sQTL permutation result" : "sQTL permutation result");
+    if (int rc = carved(o, mem ? "grouped sQTL permutation result" : "sQTL permutation result")) return rc;
     HIP_TRY(ev_products.create());
     HIP_TRY(hipEventRecord(ev_products[0], st));
     // (without lists all three of d_begin, d_row and best_row are null: series g is table row g alone)

@@ -59,11 +59,16 @@ struct TransRun : QtlPrep {
         const size_t n_tmp = scan_tmp_words(n_tiles);
         if (int rc = grow(co->qx_tiles, 64 + (6 * (size_t)n_tiles + 2 + n_tmp) * 4 + 256,
                           "regtools_amd: no device memory for %u tiles of the trans scan\n", n_tiles)) return rc;
-        Carve w(co->qx_tiles);
+        // first writers: totals k_qtl_trans_totals (words 0 .. 4; 5 .. 7 left, never read); tile_hits, tile_tested, tile_flag k_qtl_trans_count
+        // (one workgroup per tile through trans_tile_of, a tile behind the last usable variant gets three zeros); tile_place, tile_off the scans
+        // (whole); hit_tile k_qtl_trans_hit_tiles [0, *n_hit), the rest left and not read: the emit's grid is *n_hit; n_hit[0] the scan, n_hit[1]
+        // left, never read; tile_tmp: the scans' scratch
+        Carve w = carve(co->qx_tiles);
         totals = (unsigned long long *)w.u64(8);
         tile_hits = w.u32(n_tiles); tile_tested = w.u32(n_tiles); tile_flag = w.u32(n_tiles); tile_off = w.u32(n_tiles); tile_place = w.u32(n_tiles);
         hit_tile = w.u32(n_tiles); n_hit = w.u32(2); tile_tmp = w.u32(n_tmp);
         CARVE_TRY(w, "trans sQTL tile");
+        if (int rc = carved(w, "trans sQTL tile")) return rc;
         uint64_t r_min_bits = qtl_abs_bits(x.r_min);
         tiles = QtlTransTiles{Yt, ldy, Gt, ldg, S, K, n_blocks, n_vt, regions, yy, u_gg, u_key,
                               n_usable(), r_min_bits, x.exclude_cis ? 1u : 0u, x.exclude_window};
@@ -91,13 +96,16 @@ struct TransRun : QtlPrep {
         const size_t n_rtmp = row_bits ? radix_tmp_words(n) : 0;
         if (int rc = grow(co->qt_out, (size_t)H * (4 * 8 + 6 * 4) + ((size_t)K + 1 + n_rtmp) * 4 + 256, "regtools_amd: no device memory for %llu hits\n",
                             (unsigned long long)H)) return rc;
-        Carve o(co->qt_out);
+        // first writers: hit_row, hit_u, hit_r, hit_slope k_qtl_trans_emit (every hit has one place); perm the radix passes; row_sorted,
+        // hit_variant, r, slope k_qtl_trans_gather (whole); hit_begin k_qtl_trans_begin (whole); rtmp: the passes' scratch
+        Carve o = carve(co->qt_out);
         double *hit_r = o.take<double>(H), *hit_slope = o.take<double>(H);
         r = o.take<double>(H); slope = o.take<double>(H);
         uint32_t *hit_row = o.u32(H), *hit_u = o.u32(H), *perm[2] = {o.u32(H), o.u32(H)}, *row_sorted = o.u32(H);
         hit_variant = o.u32(H); hit_begin = o.u32((size_t)K + 1);
         uint32_t *rtmp = o.u32(n_rtmp);
         CARVE_TRY(o, "trans sQTL hit");
+        if (int rc = carved(o, "trans sQTL hit")) return rc;
         HIP_TRY(hipEventRecord(ev_hits[1], st));
         launch_qtl_trans_emit(tiles, hit_tile, n_hit_tiles, tile_off, hit_row, hit_u, hit_r, hit_slope, st);
         mark("hit tiles");

@@ -199,6 +199,8 @@ void launch_reduce_finish(EventSoA ev, const uint32_t *perm, uint32_t n, uint32_
 void launch_name_rank(uint32_t n_unique, const uint32_t *flag_scan, UniqueSoA u, hipStream_t stream);
 void launch_gather_u32(uint32_t n, const uint32_t *table, const uint32_t *idx, uint32_t *out, hipStream_t stream);
 void launch_fill_u32(uint32_t *p, uint32_t v, size_t n, hipStream_t stream);
+// p[i] = v for n elements of `width` bytes (1, 2, 4 or 8) at any alignment the width allows: the cohort runs' fill mode
+void launch_fill_elems(void *p, uint32_t width, uint64_t v, size_t n, hipStream_t stream);
 // ten u32 columns of n rows each, in `order`: tid,start,end,ts,te,count,name_rank,first_seen,last_seen,strand
 void launch_rows_out(UniqueSoA u, const uint32_t *order, uint32_t n, uint32_t *out, hipStream_t stream);
 // The result table's host block, written on the device so that ONE copy fills every column (api_ctx.cpp table_alloc): m = padded row count;

@@ -149,27 +149,36 @@ int QtlPrep::open() {
     const size_t n_T = 2 * (size_t)K - 1, n_Q = (size_t)C * S, n_ks = (size_t)K * S, n_vs = (size_t)V * S;
     if (int rc = grow(co->qt_in, (n_T + n_Q) * 8 + (n_ks + 3 * (size_t)K + 2 * (size_t)V) * 4 + n_vs + 256,
               "regtools_amd: no device memory for a table of %u rows, %u variants and %u samples\n", K, V, S)) return rc;
-    Carve u(co->qt_in);
+    Carve u = carve(co->qt_in);                               // (every array written whole by its upload; vt, vp and the dosages have no bytes without variants)
     double *t_up = u.take<double>(n_T), *q_up = u.take<double>(n_Q);
     uint32_t *r_up = u.u32(n_ks), *g_up = u.u32(3 * (size_t)K), *vt_up = u.u32(V), *vp_up = u.u32(V); int8_t *d_up = u.take<int8_t>(n_vs);
     CARVE_TRY(u, "sQTL input");
+    if (int rc = carved(u, "sQTL input")) return rc;
     const size_t n_scan = std::max<size_t>(std::max<size_t>((size_t)K + 1, V), (size_t)n_blocks + 1);
     if (int rc = grow(co->qt_rows, (n_ks + n_vs + K + 2 * (size_t)V) * 8 + (size_t)V * 8 + 32 +
                            (3 * (size_t)V + 2 * (size_t)K + 1 + 2 * (size_t)n_blocks + 1 + own_words + scan_tmp_words((uint32_t)n_scan)) * 4 + V + 256,
               "regtools_amd: no device memory for the residuals of %u rows and %u variants\n", K, V)) return rc;
-    Carve w(co->qt_rows);
+    // first writers: Y, yy k_qtl_residual_pheno (whole); G k_qtl_residual_geno, but for the rows of constant variants, which are read only through
+    // u_var; gg, usable, verdict the same kernel (whole); place the scan (whole); u_var, u_key, u_gg k_qtl_compact [0, U), the rest left and read
+    // only below *n_usable or inside [lo, lo + count); head the memset below, then the scan (n_usable), the residual kernels (flags) and k_qtl_totals;
+    // lo, count k_qtl_plan (whole, count[K] = 0); blk_lo, tile_count k_qtl_tiles (whole, tile_count[n_blocks] = 0); own: the deriving run's; tmp:
+    // the scans' scratch, written by each scan in front of its reads
+    Carve w = carve(co->qt_rows);
     Y = w.take<double>(n_ks); G = w.take<double>(n_vs); yy = w.take<double>(K); gg = w.take<double>(V); u_gg = w.take<double>(V);
     u_key = w.u64(V); head = w.u64(4);
     usable = w.u32(V); place = w.u32(V); u_var = w.u32(V); lo = w.u32(K); count = w.u32((size_t)K + 1);
     blk_lo = w.u32(n_blocks); tile_count = w.u32((size_t)n_blocks + 1); own = w.u32(own_words);
     tmp = w.u32(scan_tmp_words((uint32_t)n_scan)); verdict = w.u8(V);
     CARVE_TRY(w, "sQTL row");
+    if (int rc = carved(w, "sQTL row")) return rc;
     const size_t ldy_used = want_Yt ? ldy : 0;
     if (int rc = grow(co->qt_t, (size_t)S * (ldy_used + ldg) * 8 + 256,
               "regtools_amd: no device memory for the sample-major residuals of %u rows and %u variants\n", K, V)) return rc;
-    Carve t(co->qt_t);
+    // first writers: Yt and Gt k_qtl_transpose, every word of S x ld with +0.0 in the pad columns
+    Carve t = carve(co->qt_t);
     Yt = t.take<double>((size_t)S * ldy_used); Gt = t.take<double>((size_t)S * ldg);
     CARVE_TRY(t, "sQTL panel");
+    if (int rc = carved(t, "sQTL panel")) return rc;
     HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(hipMemcpyAsync(r_up, a.ph->rank2, n_ks * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(t_up, T.data(), n_T * 8, hipMemcpyHostToDevice, st));
@@ -205,9 +214,10 @@ int QtlPrep::plan_launch() {
     return RGX_OK;
 }
 int QtlPrep::wait(CopyBack &back, std::initializer_list<Interval> intervals, const char *where) {
+    guards_back(back);
     hipError_t e_ = back.wait();
     for (const Interval &i : intervals) if (e_ == hipSuccess) e_ = hipEventElapsedTime(i.ms, i.from, i.to);
     if (e_ != hipSuccess) return fail(err, errlen, RGX_ERR_DEVICE, "HIP error %s in the %s\n", hipGetErrorString(e_), where);
     mark("copies");
-    return RGX_OK;
+    return guards_check();
 }

@@ -8,6 +8,7 @@
 //   k_reduce_partials, k_reduce_finish_partials   the same two over partial rows (sum / min / max of what k_preagg gathered)
 //   k_name_rank               1-based rank of a row's first occurrence, from the scan of the marks
 //   k_gather_u32, k_fill_u32  out[r] = table[idx[r]]; p[i] = v
+//   k_fill_elems<T>           p[i] = v for elements of 1, 2, 4 or 8 bytes: the fill mode of the cohort runs (cohort_internal.h)
 //   k_rows_out                the unique rows in final order as ten u32 columns (the shards' form, merge_kernels.hip reads it)
 //   k_rows_table              the same rows in the host table block's layout (kernels.h table_block_rows)
 // Constant owned here: kAggEmpty; the tile size of k_preagg is chosen at its launch.
@@ -212,6 +213,10 @@ __global__ void k_fill_u32(uint32_t *p, uint32_t v, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
 }
+template <class T> __global__ void k_fill_elems(T *p, T v, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
 
 void launch_heads(EventSoA ev, const uint32_t *perm, uint32_t n, uint32_t *head, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(k_heads, dim3((n + 255) / 256), dim3(256), 0, stream, ev, perm, n, head);
@@ -249,6 +254,16 @@ void launch_reduce_finish_partials(const uint8_t *ev_strand, uint32_t n_unique, 
 }
 void launch_fill_u32(uint32_t *p, uint32_t v, size_t n, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, v, n);
+}
+template <class T> static void fill_elems(void *p, uint64_t v, size_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(k_fill_elems<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (T *)p, (T)v, n);
+}
+void launch_fill_elems(void *p, uint32_t width, uint64_t v, size_t n, hipStream_t stream) {
+    if (!n) return;
+    if (width == 1) fill_elems<uint8_t>(p, v, n, stream);
+    else if (width == 2) fill_elems<uint16_t>(p, v, n, stream);
+    else if (width == 4) fill_elems<uint32_t>(p, v, n, stream);
+    else fill_elems<uint64_t>(p, v, n, stream);
 }
 
 }  // namespace rgx

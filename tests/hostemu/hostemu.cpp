@@ -315,6 +315,36 @@ extern "C" int emu_carve(size_t cap, size_t n_takes, const uint32_t *width, cons
     return w.over ? 1 : 0;
 }
 
+// The same with a log attached.  type[k]: 1, 2, 4, 8 an integer of that width, 16 a float, 17 a double.  Returns `over` (bit 0) and the log's `full`
+// (bit 1), -1 for a type there is none of; off as emu_carve; the log's arrays as (offset, bytes, kind) in log_rows (room for log_cap rows, *n_log
+// receives the log's count) and where its last array ends in *end.  The log starts out dirty: the Carve has to reset it.
+extern "C" int emu_carve_log(size_t cap, size_t n_takes, const uint32_t *type, const size_t *count, size_t *off, size_t *log_rows, size_t log_cap,
+                             size_t *n_log, size_t *end) {
+    std::vector<uint8_t> mem(cap ? cap : 1);
+    CarveLog lg; lg.n = 7; lg.end = 99; lg.full = true;
+    Carve w(mem.data(), cap, &lg);
+    for (size_t k = 0; k < n_takes; ++k) {
+        const uint8_t *r = nullptr;
+        if (type[k] == 1) r = (const uint8_t *)w.take<int8_t>(count[k]);
+        else if (type[k] == 2) r = (const uint8_t *)w.take<uint16_t>(count[k]);
+        else if (type[k] == 4) r = (const uint8_t *)w.u32(count[k]);
+        else if (type[k] == 8) r = (const uint8_t *)w.u64(count[k]);
+        else if (type[k] == 16) r = (const uint8_t *)w.take<float>(count[k]);
+        else if (type[k] == 17) r = (const uint8_t *)w.take<double>(count[k]);
+        else return -1;
+        off[k] = (size_t)(r - mem.data());
+    }
+    *n_log = lg.n; *end = lg.end;
+    for (uint32_t i = 0; i < lg.n && i < log_cap; ++i) { log_rows[3 * i] = lg.a[i].off; log_rows[3 * i + 1] = lg.a[i].bytes; log_rows[3 * i + 2] = (size_t)lg.a[i].kind; }
+    return (w.over ? 1 : 0) | (lg.full ? 2 : 0);
+}
+extern "C" uint32_t emu_carve_log_cap() { return CarveLog::kCap; }
+
+// carve_guard_check over a window of n bytes: 1 untouched, 0 touched with the message in msg
+extern "C" int emu_carve_guard(const uint8_t *window, size_t n, const char *what, char *msg, size_t msglen) {
+    return carve_guard_check(window, n, what, msg, msglen) ? 1 : 0;
+}
+
 // cse_table.h on its own: the first-insert junction table of `identify` / `associate`.  names / vnames: contig names of the junctions and of the variants
 // (equal names may repeat); cand: n_cand x (contig, start, end, variant contig, variant pos, src), indices into names / vnames, in arrival order.
 // threads: the pool finish() sorts on (0 = none given: its own).  rows: per junction in table order (contig, start, end, src of the row that stayed,

@@ -313,6 +313,85 @@ def test_carve_hands_out_running_offsets_and_refuses_what_does_not_fit(emu):
     assert carve(0, [(8, 0)]) == ([0], False)
 
 
+def _carve_log(emu, cap, takes):
+    """takes: (type, count) with type 1, 2, 4, 8 an integer of that width, 16 a float, 17 a double -> (offsets, over, full, log rows, end)"""
+    P = ctypes.POINTER
+    emu.emu_carve_log.restype = ctypes.c_int
+    emu.emu_carve_log.argtypes = [ctypes.c_size_t, ctypes.c_size_t, P(ctypes.c_uint32), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t),
+                                  ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    n = max(len(takes), 1)
+    type_ = (ctypes.c_uint32 * n)(*[t for t, _ in takes])
+    count = (ctypes.c_size_t * n)(*[c for _, c in takes])
+    off = (ctypes.c_size_t * n)()
+    rows = (ctypes.c_size_t * (3 * n))()
+    n_log, end = ctypes.c_size_t(), ctypes.c_size_t()
+    rc = emu.emu_carve_log(cap, len(takes), type_, count, off, rows, n, ctypes.byref(n_log), ctypes.byref(end))
+    assert 0 <= rc <= 3
+    log = [tuple(rows[3 * i:3 * i + 3]) for i in range(min(n_log.value, n))]
+    return list(off)[:len(takes)], bool(rc & 1), bool(rc & 2), log, end.value
+
+
+def test_carve_log_records_offset_length_and_kind_of_every_array(emu):
+    """With a log attached a Carve writes down, per array that fitted, its offset, its byte length and its kind (0 floating point, else the
+    integer's width), and where the last array ends: what the fill mode of the cohort runs fills by (csrc/cohort_internal.h)."""
+    FP = 0
+    takes = [(17, 5), (4, 7), (1, 3), (16, 2), (2, 9), (8, 1), (17, 1)]
+    width = {1: 1, 2: 2, 4: 4, 8: 8, 16: 4, 17: 8}
+    kind = {1: 1, 2: 2, 4: 4, 8: 8, 16: FP, 17: FP}
+    sums = [0]
+    for t, n in takes:
+        sums.append(sums[-1] + width[t] * n)
+    want = [(sums[i], width[t] * n, kind[t]) for i, (t, n) in enumerate(takes)]
+    # mixed takes that fit exactly, and with room to spare: the log is the arrays in order, the end is the running sum (the log handed in was dirty)
+    for cap in (sums[-1], sums[-1] + 300):
+        assert _carve_log(emu, cap, takes) == (sums[:-1], False, False, want, sums[-1])
+    # a take that does not fit sets `over` and logs nothing; the end stays where the last array that fitted left it, and a later one that fits is logged
+    off, over, full, log, end = _carve_log(emu, sums[3] + 3, takes[:3] + [(4, 1), (17, 1), (1, 2)])
+    assert over and not full and off == sums[:3] + [sums[3], sums[3], sums[3]]
+    assert log == want[:3] + [(sums[3], 2, 1)] and end == sums[3] + 2
+    # a take of no elements is no array: neither logged nor the end
+    assert _carve_log(emu, 64, [(4, 0), (4, 3), (17, 0), (1, 0)]) == ([0, 0, 12, 12], False, False, [(0, 12, 4)], 12)
+    assert _carve_log(emu, 0, []) == ([], False, False, [], 0)
+    # more arrays than the log holds: `full`, nothing written behind its capacity, the end still moves
+    emu.emu_carve_log_cap.restype = ctypes.c_uint32
+    cap = emu.emu_carve_log_cap()
+    off, over, full, log, end = _carve_log(emu, 4 * (cap + 2), [(4, 1)] * (cap + 2))
+    assert not over and full and off == [4 * i for i in range(cap + 2)]
+    assert log == [(4 * i, 4, 4) for i in range(cap)] and end == 4 * (cap + 2)
+    off, over, full, log, end = _carve_log(emu, 4 * cap, [(4, 1)] * cap)
+    assert not over and not full and len(log) == cap and end == 4 * cap
+
+
+def test_carve_guard_window_names_the_workspace_and_the_byte(emu):
+    """The guard bytes behind a workspace's last array (fill mode): untouched means every byte of the window is 0xA5; a changed byte fails with the
+    workspace's name, the first changed byte's place and its value."""
+    emu.emu_carve_guard.restype = ctypes.c_int
+    emu.emu_carve_guard.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+
+    def check(window, what=b"sQTL row"):
+        msg = ctypes.create_string_buffer(b"untouched", 256)
+        ok = emu.emu_carve_guard(bytes(window), len(window), what, msg, len(msg))
+        return bool(ok), msg.value.decode()
+
+    clean = bytearray([0xA5]) * 256
+    assert check(clean) == (True, "untouched")
+    assert check(b"") == (True, "untouched")                           # (a workspace whose arrays end at its capacity has no window)
+    for at, value in ((0, 0x00), (1, 0xA4), (128, 0x01), (255, 0xFF)):
+        w = bytearray(clean)
+        w[at] = value
+        ok, msg = check(w, b"trans sQTL tile")
+        assert not ok
+        assert "trans sQTL tile buffer" in msg and "wrote behind" in msg and "byte %d " % at in msg and "0x%02x," % value in msg
+    # the first changed byte is the one named; a window shorter than 256 bytes is judged over its own length
+    w = bytearray(clean)
+    w[7] = 0
+    w[9] = 0
+    assert "byte 7 " in check(w)[1]
+    assert check(w[:7]) == (True, "untouched") and not check(w[:8])[0]
+    # a message buffer of no bytes is left alone
+    assert emu.emu_carve_guard(bytes(w), len(w), b"x", None, 0) == 0
+
+
 def _jtable(emu, names, vnames, cands, threads):
     emu.emu_jtable.restype = ctypes.c_long
     emu.emu_jtable.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
